@@ -9,15 +9,24 @@ in HBM before the timed region.  For N>1 each rank renders its own view of the r
 and the step ends with the SUM of the per-view parameter gradients on every rank: by
 default through an RCCL all-gather of 64-byte per-visible-splat records and a deterministic
 per-splat reduction (brush_amd/dist.py), with --dense-allreduce through one all-reduce of the dense
-block; scaling is weak (per-GPU work fixed).  Rank 0 prints ONE JSON line; `train` in it is the full
-training iteration (loss + Adam) at the same N.  At N=1 `value` is ONE fixed launch mode: the K steps as eager launches
-through the C ABI after W warm-up steps — how the reference's host drives its kernels, and the mode BENCH_r03's value was
-in (0.3475 ms; r01 / r02 quoted a hipGraph replay).  The same K steps replayed as one captured hipGraph are timed beside
-it (`whole_path.graph_ms_per_step`; r02 0.374, r03 0.354-0.356 ms), so both series can be followed round to round.  `stage_ms` are IN-SITU stage times: the captured prefixes
+block; scaling is weak (per-GPU work fixed).  Rank 0 prints ONE JSON line.  At N=1 `value` is ONE fixed launch mode: the
+K steps as eager launches through the C ABI after W warm-up steps — how the reference's host drives its kernels, and the
+mode BENCH_r03's value was in (0.3475 ms; r01 / r02 quoted a hipGraph replay); `ms_per_step` is one timed step.  At N>1
+the three gradient-exchange forms (records padded / records packed / dense all-reduce) are timed in the same run
+(`exchange_variants`) and `value` is the fastest.
+
+A plain run does only that: set up, warm up (0.1 s of untimed steps, then the W), time the K steps, write the outputs
+(--dump-outputs DIR: the last timed step's image, the parameter gradients of a fixed seeded sample of 65 536 splat rows
+and the visible / intersection counts, as DIR/<name>.npy) and print the headline line.  Everything below is measured
+with --full only.
+
+--full: `train` is the full training iteration (loss + Adam) at the same N.  The same K steps replayed as one captured
+hipGraph are timed beside the eager ones (`whole_path.graph_ms_per_step`; r02 0.374, r03 0.354-0.356 ms), so both series
+can be followed round to round.  `stage_ms` are IN-SITU stage times: the captured prefixes
 cull .. stage k of the step are timed as replayed graphs and differenced (brush_profiler_stop_after), so they add up to
 the step; `stage_ms_events` are the hipEvent times of eager passes that earlier rounds reported (every event record adds
-~3-5 us to its stage).  At N>1 the three gradient-exchange forms (records padded / records packed / dense all-reduce)
-are timed in the same run (`exchange_variants`) and `value` is the fastest.
+~3-5 us to its stage).  Then the roofline of the dominant kernel, the device copy bandwidth, the extra workloads
+(dense scene, c3, S3) and the CPU baseline (the oracle).
 """
 from __future__ import annotations
 
@@ -63,7 +72,56 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the extra workloads (dense scene, S3) of the N=1 line")
     ap.add_argument("--no-graph", action="store_true",
                     help="enqueue every launch from the host instead of replaying one captured hipGraph per step")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: graph replay, stage times, roofline, "
+                         "training iteration, extra workloads, CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32/float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_GRAD_ROWS = 1 << 16      # seeded sample of splat rows of the gradients (61 floats each at SH degree 3)
+DUMP_MAX_PIXELS = 1 << 21     # full image up to ~2.1 Mpixel (1920x1080 fits) ...
+DUMP_PIXEL_SAMPLE = 1 << 20   # ... a seeded sample of this many pixels beyond
+
+
+def collect_outputs(out, aux, block, n, C, with_xy):
+    """Host copies of what a caller of the timed path receives: the image, the parameter gradients of a fixed seeded
+    sample of splat rows, and the visible / intersection counts.  Under 64 MB in all at any size."""
+    from brush_amd import render as R
+
+    res = {}
+    img = out.detach().float().reshape(-1, out.shape[-1])
+    if img.shape[0] > DUMP_MAX_PIXELS:
+        px = np.sort(np.random.default_rng(1).choice(img.shape[0], DUMP_PIXEL_SAMPLE, replace=False))
+        res["image_index"] = px.astype(np.float64)
+        res["image"] = img[torch.as_tensor(px, device=img.device)].cpu().numpy()
+    else:
+        res["image"] = out.detach().float().cpu().numpy()
+    rows = np.arange(n) if n <= DUMP_GRAD_ROWS else np.sort(
+        np.random.default_rng(0).choice(n, DUMP_GRAD_ROWS, replace=False))
+    res["grad_index"] = rows.astype(np.float64)
+    ridx = torch.as_tensor(rows, device=block.device)
+    layout, _ = R.grad_block_layout(n, C)
+    shapes = {"v_means": (n, 3), "v_scales": (n, 3), "v_quats": (n, 4), "v_opac": (n,), "v_sh": (n, C, 3), "v_xy": (n, 2)}
+    for name, shape in shapes.items():
+        if name == "v_xy" and not with_xy:
+            continue
+        off, sz = layout[name]
+        res[name] = block[off:off + sz].view(shape)[ridx].cpu().numpy()
+    res["counts"] = np.array([aux.read_num_visible(), aux.read_num_intersections(), int(aux.overflow.item())],
+                             dtype=np.float64)
+    return res
+
+
+def write_outputs(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def synthetic_cloud(n, sh_degree, seed=4, mean_mult=1.0):
@@ -192,15 +250,27 @@ def main():
         return sec
 
     def timed(fn, steps, warmup):
-        """W untimed + K timed calls bracketed by barrier + synchronize on both sides, max over ranks."""
+        """W untimed + K timed calls bracketed by barrier + synchronize on both sides, max over ranks.
+        Returns the seconds and what the last timed call returned."""
         for _ in range(warmup):
             fn()
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn()
+            last = None  # free the previous step's results first, as a discarded return value would be
+            last = fn()
         barrier()
-        return max_over_ranks(time.perf_counter() - t0)
+        return max_over_ranks(time.perf_counter() - t0), last
+
+    def settle(fn, seconds=0.1):
+        """Untimed steps for `seconds` before the W warm-up steps of the headline: a GPU that idled through the set-up
+        needs more than a handful of steps to run at its steady rate (5 warm-up steps alone read ~2.5 % slow at K=20;
+        the graph replay that used to precede the eager steps did this implicitly)."""
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < seconds:
+            for _ in range(10):
+                fn()
+            torch.cuda.synchronize()
 
     class Workload:
         """One view of one cloud: forward (+ dense backward) as eager launches or as one replayed hipGraph."""
@@ -223,7 +293,7 @@ def main():
             out, aux, u = self.forward()
             R._backward_impl(u, aux, q["means"], q["log_scales"], q["quats"], q["raw_opac"], self.C, out, self.v_out,
                              self.block)
-            return aux
+            return out, aux  # the image and the aux; the gradients are in self.block
 
         def _capture(self, fn):
             side = torch.cuda.Stream()
@@ -240,7 +310,7 @@ def main():
         def capture(self):
             # The op never syncs, allocates or reads a count back, so one fwd+bwd is a capturable launch sequence:
             # replaying it as a hipGraph removes the ~3.5 us/launch host enqueue cost (DESIGN.md "launch floor").
-            self.graph, self.graph_aux = self._capture(self.fwd_bwd)
+            self.graph, self.graph_res = self._capture(self.fwd_bwd)
 
         def capture_forward(self):
             self.graph_fwd, self.fwd_res = self._capture(self.forward)
@@ -248,19 +318,23 @@ def main():
         def step(self):
             if self.graph is not None:
                 self.graph.replay()
-                return self.graph_aux
+                return self.graph_res
             return self.fwd_bwd()
 
     wl = Workload(p, n, w, h, cam, cap)
     exchange_mode = None
     exchange_variants = None
     graph_ms = None
+    dumped = None  # host copies of the timed path's last-step outputs (--dump-outputs)
+    want_dump = args.dump_outputs is not None and rank == 0
     if world == 1:
-        if not args.no_graph:  # the same K steps as one replayed hipGraph, reported beside the headline
+        if args.full and not args.no_graph:  # the same K steps as one replayed hipGraph, reported beside the headline
             wl.capture()
-            graph_ms = timed(wl.step, args.steps, args.warmup) * 1e3 / args.steps
-        step = wl.fwd_bwd
-        elapsed = timed(step, args.steps, args.warmup)
+            graph_ms = timed(wl.step, args.steps, args.warmup)[0] * 1e3 / args.steps
+        settle(wl.fwd_bwd)
+        elapsed, (out, aux) = timed(wl.fwd_bwd, args.steps, args.warmup)
+        if want_dump:
+            dumped = collect_outputs(out, aux, wl.block, n, C, with_xy=True)
     else:
         # N > 1: one view per rank; the step ends with the SUM of the per-view parameter gradients on every rank.  Three
         # exchange forms, each W warm-up + K timed steps in this run; `value` is the fastest (the ranking on xGMI is not
@@ -287,13 +361,13 @@ def main():
                 xchg.backward_records(u, aux, p["means"], p["log_scales"], p["quats"], p["raw_opac"], out, wl.v_out)
                 xchg.gather()
                 xchg.reduce_dense(p["means"], wl.block)
-                return aux
+                return out, aux
             return record_step
 
         def dense_step():
-            aux = wl.fwd_bwd()  # eager: the forward graph above and a fwd+bwd graph would double the captured pools
+            res = wl.fwd_bwd()  # eager: the forward graph above and a fwd+bwd graph would double the captured pools
             BD.allreduce_param_grads(wl.block, n, C)
-            return aux
+            return res
 
         xchgs = {"records_padded": BD.ViewExchange(n, C, dev, packed=False),
                  "records_packed": BD.ViewExchange(n, C, dev, packed=True)}
@@ -302,7 +376,7 @@ def main():
         todo = ["dense_allreduce"] if args.dense_allreduce else list(steps_by_name)
         exchange_variants, best = {}, None
         for name in todo:
-            sec = timed(steps_by_name[name], args.steps, args.warmup)
+            sec, (last_out, last_aux) = timed(steps_by_name[name], args.steps, args.warmup)
             exchange_variants[name] = {"ms_per_step": round(sec * 1e3 / args.steps, 4),
                                        "views_per_s": round(n_gpus * args.steps / sec, 3), "what": NAMES[name]}
             x = xchgs.get(name)
@@ -310,11 +384,14 @@ def main():
                 exchange_variants[name]["host_waits"] = x.host_waits
                 exchange_variants[name]["host_wait_ms_per_step"] = round(x.host_wait_s * 1e3 / (args.steps + args.warmup), 4)
             if best is None or sec < best[1]:
-                best = (name, sec)
-        step, elapsed = steps_by_name[best[0]], best[1]
+                best = (name, sec, last_aux)
+                if want_dump:  # the next form overwrites the block: keep the fastest form's outputs now
+                    dumped = collect_outputs(last_out, last_aux, wl.block, n, C, with_xy=False)
+        elapsed, aux = best[1], best[2]
         exchange_mode = NAMES[best[0]] + (" — fastest of the forms timed in this run" if len(todo) > 1 else "")
-    aux = step()
     torch.cuda.synchronize()
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     ms_per_step = elapsed * 1e3 / args.steps
     value = n_gpus * args.steps / elapsed  # whole-job views/s
 
@@ -324,6 +401,33 @@ def main():
 
     eager_ms = ms_per_step if world == 1 else None
     launch_used = None
+
+    def headline():
+        launch = launch_used if launch_used else (
+            "eager launches through the C ABI (hipGraph replay of the same step: whole_path.graph_ms_per_step, --full)"
+            if world == 1 else
+            "record forms: hipGraph replay of the forward, then backward, exchange and reduction enqueued per step; dense "
+            "all-reduce form: eager launches")
+        return {
+            "metric": "fwd+bwd views/s (train-iter rate of the rasterizer path), 1M splats @1080p",
+            "value": round(value, 3), "unit": "views/s", "n_gpus": n_gpus, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
+            "config": {"workload": f"{'S1' if (n, w, h, deg, args.mean_mult) == (1 << 20, 1920, 1080, 3, 1.0) else 'custom'}: {n} splats @{w}x{h}, SH degree {deg}, seed 4, mean_mult {args.mean_mult}, "
+                                   f"fwd+bwd per view", "views_per_step": n_gpus,
+                       "parallelism": f"view-sharded dp{n_gpus}" if n_gpus > 1 else "single GPU",
+                       "gradient_exchange": exchange_mode, "launch": launch,
+                       "num_visible": V, "num_intersections": I, "max_intersects": aux.max_intersects,
+                       "overflow": overflow},
+            "exchange_variants": exchange_variants,
+        }
+
+    if not args.full:  # a plain run: the headline only
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- per-stage device time (hipEvents on the op's stream), separate untimed steps ----
     def profile_stages(workload, steps):
@@ -540,8 +644,8 @@ def main():
                 pp = {k: torch.as_tensor(v, device=dev) for k, v in cl.items()}
                 del cl
                 x = Workload(pp, c["n"], c["w"], c["h"], view_camera(0, c["w"], c["h"]), c["cap"])
-                sec = timed(x.fwd_bwd, c["steps"], 2)  # eager launches, like the headline
-                ax = x.fwd_bwd()
+                sec = timed(x.fwd_bwd, c["steps"], 2)[0]  # eager launches, like the headline
+                ax = x.fwd_bwd()[1]
                 torch.cuda.synchronize()
                 Vx, Ix = ax.read_num_visible(), ax.read_num_intersections()
                 Px, Tx = c["w"] * c["h"], (-(-c["w"] // 16)) * (-(-c["h"] // 16))
@@ -590,21 +694,8 @@ def main():
                                   f"algorithm, OpenMP; not wgpu/lavapipe), {cpu_s * 1e3:.0f} ms/view"}
 
     if rank == 0:
-        launch = launch_used if launch_used else (
-            "eager launches through the C ABI (hipGraph replay of the same step: whole_path.graph_ms_per_step)" if world == 1 else
-            "record forms: hipGraph replay of the forward, then backward, exchange and reduction enqueued per step; dense "
-            "all-reduce form: eager launches")
-        line = {
-            "metric": "fwd+bwd views/s (train-iter rate of the rasterizer path), 1M splats @1080p",
-            "value": round(value, 3), "unit": "views/s", "n_gpus": n_gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{'S1' if (n, w, h, deg, args.mean_mult) == (1 << 20, 1920, 1080, 3, 1.0) else 'custom'}: {n} splats @{w}x{h}, SH degree {deg}, seed 4, mean_mult {args.mean_mult}, "
-                                   f"fwd+bwd per view", "views_per_step": n_gpus,
-                       "parallelism": f"view-sharded dp{n_gpus}" if n_gpus > 1 else "single GPU",
-                       "gradient_exchange": exchange_mode, "launch": launch,
-                       "num_visible": V, "num_intersections": I, "max_intersects": aux.max_intersects,
-                       "overflow": overflow},
+        line = headline()
+        line.update({
             "roofline": roofline, "cpu_baseline": cpu_baseline, "whole_path": whole_path, "train": train,
             "stage_ms": {k: round(v, 5) for k, v in stage_ms.items()},
             "stage_ms_method": ("in situ: differences of replayed prefix graphs cull..stage (brush_profiler_stop_after); sum = "
@@ -614,8 +705,8 @@ def main():
             "small_stages_ms": {"in_situ": round(sum(stage_ms[k] for k in SMALL_STAGES), 5),
                                 "events": round(sum(stage_ms_events[k] for k in SMALL_STAGES), 5),
                                 "stages": list(SMALL_STAGES)},
-            "exchange_variants": exchange_variants, "extra_workloads": extra,
-        }
+            "extra_workloads": extra,
+        })
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -147,3 +147,55 @@ def test_product_and_bench_do_not_import_the_oracle():
     # the bench and the tools do not depend on the test package either
     for f in ["bench.py"] + [os.path.join("tools", t) for t in os.listdir(os.path.join(root, "tools")) if t.endswith(".py")]:
         assert not re.search(r"^\s*(from|import)\s+tests\b", open(os.path.join(root, f)).read(), flags=re.M), f
+
+
+def test_bench_dump_outputs_are_float_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float32/float64 files only, the same seeded sample of gradient rows and pixels on every
+    run, the sampled rows read from the right segments of the gradient block, and under 64 MB at the headline image size
+    and beyond it."""
+    import importlib.util
+
+    import torch
+
+    from brush_amd import render as R
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    B = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(B)
+
+    class Aux:
+        overflow = torch.zeros(1, dtype=torch.int32)
+
+        def read_num_visible(self):
+            return 7
+
+        def read_num_intersections(self):
+            return 11
+
+    n, ncoef = 100_000, 16
+    layout, total = R.grad_block_layout(n, ncoef)
+    block = torch.rand(total, generator=torch.Generator().manual_seed(0))
+    for w, h in ((1920, 1080), (2100, 1100)):
+        out = torch.rand((h, w, 4), generator=torch.Generator().manual_seed(1))
+        a = B.collect_outputs(out, Aux(), block, n, ncoef, with_xy=True)
+        again = B.collect_outputs(out, Aux(), block, n, ncoef, with_xy=True)
+        d = tmp_path / f"{w}x{h}"
+        B.write_outputs(str(d), a)
+        files = sorted(os.listdir(d))
+        assert files == sorted(f"{k}.npy" for k in a)
+        assert sum(os.path.getsize(d / f) for f in files) < 64e6
+        for k, v in a.items():
+            assert v.dtype in (np.float32, np.float64), k
+            assert np.array_equal(v, again[k]), k
+            assert np.array_equal(np.load(d / f"{k}.npy"), v), k
+        rows = a["grad_index"].astype(np.int64)
+        assert len(rows) == B.DUMP_GRAD_ROWS and np.all(np.diff(rows) > 0)
+        for name, shape in (("v_means", (n, 3)), ("v_opac", (n,)), ("v_sh", (n, ncoef, 3)), ("v_xy", (n, 2))):
+            off, sz = layout[name]
+            assert np.array_equal(a[name], block[off:off + sz].view(shape).numpy()[rows]), name
+        if w * h <= B.DUMP_MAX_PIXELS:
+            assert "image_index" not in a and np.array_equal(a["image"], out.numpy())
+        else:
+            px = a["image_index"].astype(np.int64)
+            assert np.array_equal(a["image"], out.reshape(-1, 4).numpy()[px])
+        assert a["counts"].tolist() == [7.0, 11.0, 0.0]

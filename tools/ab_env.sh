@@ -11,7 +11,7 @@ OUT=gpurun_out/ab_$VAR
 rm -rf $OUT; mkdir -p $OUT
 for r in $(seq 1 $REPS); do
   for v in "${VALS[@]}"; do
-    env $VAR=$v python3 bench.py --no-extra --no-cpu-baseline --train-steps 0 --steps 200 --profile-steps 40 "$@" > $OUT/$v.$r.json 2> $OUT/$v.$r.err || { tail -5 $OUT/$v.$r.err; exit 1; }
+    env $VAR=$v python3 bench.py --full --no-extra --no-cpu-baseline --train-steps 0 --steps 200 --profile-steps 40 "$@" > $OUT/$v.$r.json 2> $OUT/$v.$r.err || { tail -5 $OUT/$v.$r.err; exit 1; }
   done
 done
 python3 - "$OUT" "$REPS" "${VALS[@]}" <<'PY'

@@ -8,7 +8,7 @@ OUT=gpurun_out/pmcq_$TAG
 REPO=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp && cd "$REPO"
 mkdir -p "$OUT"
-B="bench.py --no-graph --steps 4 --warmup 2 --profile-steps 0 --train-steps ${TRAIN_STEPS:-0} --no-cpu-baseline $*"
+B="bench.py --full --no-graph --steps 4 --warmup 2 --profile-steps 0 --train-steps ${TRAIN_STEPS:-0} --no-cpu-baseline $*"
 export KERNEL_RE=${KERNEL_RE:-k_rasterize[a-z0-9_]*}
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE --output-format csv -d "$OUT/sq1" -o p -- python3 $B > /dev/null 2> "$OUT/sq1.err"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INST_LEVEL_VMEM SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d "$OUT/sq2" -o p -- python3 $B > /dev/null 2> "$OUT/sq2.err"

@@ -6,7 +6,7 @@ OUT=gpurun_out/pmc_sort_s3
 REPO=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp && cd "$REPO"
 mkdir -p "$OUT"
-B="bench.py --splats 20971520 --width 3840 --height 2160 --max-intersects 24000000 --no-graph --steps 3 --warmup 1 --profile-steps 3 --train-steps 0 --no-cpu-baseline --no-extra"
+B="bench.py --splats 20971520 --width 3840 --height 2160 --max-intersects 24000000 --full --no-graph --steps 3 --warmup 1 --profile-steps 3 --train-steps 0 --no-cpu-baseline --no-extra"
 python3 $B > "$OUT/bench.json" 2> "$OUT/bench.err"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/w" -o p -- python3 $B > /dev/null 2> "$OUT/w.err"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/f" -o p -- python3 $B > /dev/null 2> "$OUT/f.err"

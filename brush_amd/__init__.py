@@ -8,6 +8,7 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
   Splats                     <- gaussian_splats.rs (render + from_safetensors only)
   radix_argsort              <- brush-sort/src/lib.rs:32-37
   prefix_sum                 <- brush-prefix-sum/src/lib.rs:17
+  eval_stats / EvalStats     <- brush-train/src/eval.rs (also `python -m brush_amd.eval`)
 
 All compute goes through the C ABI of include/brush_hip.h (libbrush_hip.so, hand-written HIP for
 gfx950).  There is no CPU fallback: importing the compute entry points without the built
@@ -21,5 +22,16 @@ from .prefix_sum import prefix_sum  # noqa: F401
 from .gaussian_splats import Splats  # noqa: F401
 from .train import SplatTrainer, TrainConfig  # noqa: F401
 from . import dataset  # noqa: F401
+
+# brush_amd.eval is imported on first use: importing it here would load the module before `python -m brush_amd.eval`
+# runs it as __main__ (runpy then warns that it is loaded twice).
+_EVAL_NAMES = ("eval_metrics", "eval_stats", "EvalStats", "EvalView")
+
+
+def __getattr__(name):
+    if name in _EVAL_NAMES:
+        from . import eval as _eval
+        return getattr(_eval, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

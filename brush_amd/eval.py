@@ -1,0 +1,200 @@
+"""Evaluation on held-out views — mirror of crates/brush-train/src/eval.rs.
+
+`eval_stats` renders each eval view of a Scene and scores it against the view's image with PSNR and SSIM
+(eval.rs:27-77); the metrics come from one fused HIP pass per view (include/brush_hip.h: brush_eval_metrics) and
+are read back once, after the last view (the reference syncs twice per view).
+
+Command line (prints one line per view, then the means):
+
+    python -m brush_amd.eval SPLATS DATASET [--format auto|nerf|colmap] [--eval-split-every K]
+                             [--max-resolution R] [--num-frames K] [--seed S] [--window 11] [--json OUT]
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def eval_metrics(pred: torch.Tensor, gt: torch.Tensor, window: int = 11,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """{mse, psnr, ssim} of pred's RGB against gt's RGB as a float32 [3] device tensor (brush_eval_metrics); does not
+    synchronise.  pred: [h,w,4] float32 (the op's output); gt: [h,w,3|4] uint8 (read as b / 255) or float32; the
+    alpha of both is ignored (eval.rs:50-57).  `window`: SSIM window, odd 3..15 (the reference's eval uses 11).
+    `out`: optional contiguous float32 [3] device tensor to write into (e.g. a row of a [V,3] tensor)."""
+    assert pred.is_cuda and gt.is_cuda, "brush_amd has no CPU path: tensors must live on the GPU"
+    if pred.dim() != 3 or gt.dim() != 3:
+        raise ValueError(f"pred must be [h,w,4] and gt [h,w,3|4], got {tuple(pred.shape)} / {tuple(gt.shape)}")
+    h, w = int(pred.shape[0]), int(pred.shape[1])
+    if tuple(pred.shape) != (h, w, 4) or tuple(gt.shape[:2]) != (h, w) or gt.shape[2] not in (3, 4):
+        raise ValueError(f"pred must be [h,w,4] and gt [h,w,3|4], got {tuple(pred.shape)} / {tuple(gt.shape)}")
+    if pred.dtype != torch.float32:
+        raise ValueError(f"pred must be float32, got {pred.dtype}")
+    dtypes = {torch.uint8: _lib.EVAL_GT_U8, torch.float32: _lib.EVAL_GT_F32}
+    if gt.dtype not in dtypes:
+        raise ValueError(f"gt must be uint8 or float32, got {gt.dtype}")
+    if int(window) not in (3, 5, 7, 9, 11, 13, 15):
+        raise ValueError(f"window must be an odd size 3..15, got {window}")
+    if out is None:
+        out = torch.empty(3, dtype=torch.float32, device=pred.device)
+    elif tuple(out.shape) != (3,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != pred.device:
+        raise ValueError("out must be a contiguous float32 [3] tensor on pred's device")
+    pred, gt = pred.contiguous(), gt.contiguous()
+    l = _lib.lib()
+    nbytes = C.c_size_t()
+    _lib.check(l.brush_eval_workspace_size(w, h, C.byref(nbytes)), "brush_eval_workspace_size")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=pred.device)
+    with torch.cuda.device(pred.device):
+        _lib.check(l.brush_eval_metrics(pred.data_ptr(), gt.data_ptr(), dtypes[gt.dtype], w, h, int(gt.shape[2]),
+                                        int(window), out.data_ptr(), ws.data_ptr(), nbytes.value,
+                                        torch.cuda.current_stream().cuda_stream),
+                   "brush_eval_metrics")
+    return out
+
+
+@dataclass
+class EvalView:
+    """eval.rs:11-20.  `rendered`: RGB [h,w,3] device tensor.  `aux`: the view's RenderAux, kept only when
+    eval_stats is called with keep_aux=True (None otherwise)."""
+    view: object  # dataset.SceneView
+    rendered: torch.Tensor
+    psnr: float
+    ssim: float
+    aux: object = None
+
+
+@dataclass
+class EvalStats:
+    """eval.rs:22-25"""
+    samples: List[EvalView] = field(default_factory=list)
+
+    def mean_psnr(self) -> float:
+        """Mean PSNR over the samples (what the viewer logs, rerun.rs:163-185); nan without samples."""
+        return float(np.mean([s.psnr for s in self.samples])) if self.samples else float("nan")
+
+    def mean_ssim(self) -> float:
+        """Mean SSIM over the samples (rerun.rs:163-185); nan without samples."""
+        return float(np.mean([s.ssim for s in self.samples])) if self.samples else float("nan")
+
+
+def select_views(num_views: int, num_frames: Optional[int] = None,
+                 rng: Optional[np.random.Generator] = None) -> List[int]:
+    """Indices of the views eval_stats scores (eval.rs:34-38): every view in order when num_frames is None or at least
+    num_views, else num_frames distinct views sampled with `rng` (a numpy Generator; a fresh one when None), in
+    ascending order."""
+    if num_frames is None or num_frames >= num_views:
+        return list(range(num_views))
+    if num_frames < 0:
+        raise ValueError(f"num_frames must be >= 0, got {num_frames}")
+    rng = np.random.default_rng() if rng is None else rng
+    return sorted(int(i) for i in rng.choice(num_views, size=int(num_frames), replace=False))
+
+
+def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np.random.Generator] = None,
+               window: int = 11, keep_aux: bool = False) -> EvalStats:
+    """eval.rs:27-77: render each selected view of `scene` (a dataset.Scene, e.g. Dataset.eval) at its image's size
+    through Splats.render under no_grad and score it against the image's RGB, uploaded as uint8, with eval_metrics.
+    The metrics of all views go into one [V,3] device tensor that is read back once, after the last view.
+
+    One deviation from the reference: `aux` is kept only with keep_aux=True, because a RenderAux holds the
+    intersection lists of its view (hundreds of MB for a large scene).
+
+    Trainer state: rendering goes through Splats.render, which applies the SH optimizer steps a SplatTrainer has
+    deferred (Splats.sync), exactly as any render or trainer.sync() does; nothing else of the trainer changes.  Call it
+    from the trainer's thread and stream, between step() calls."""
+    views = scene.views
+    idx = select_views(len(views), num_frames, rng)
+    dev = splats.means.device
+    metrics = torch.empty((len(idx), 3), dtype=torch.float32, device=dev)
+    rendered = []
+    with torch.no_grad():
+        for row, i in enumerate(idx):
+            v = views[i]
+            img = np.require(v.image, requirements=["C", "W"])  # decoded images are read-only views: torch wants a copy
+            if img.ndim != 3 or img.dtype != np.uint8 or img.shape[2] not in (3, 4):
+                raise ValueError(f"{v.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
+            h, w = int(img.shape[0]), int(img.shape[1])
+            gt = torch.from_numpy(img).to(dev)  # u8, as the reference uploads to_rgb8() (the kernel divides by 255)
+            pred, aux = splats.render(v.camera, (w, h), False)
+            eval_metrics(pred, gt, window, out=metrics[row])
+            rendered.append((pred[..., :3], aux if keep_aux else None))
+    host = metrics.cpu().numpy()  # the one readback
+    return EvalStats([EvalView(views[i], r, float(host[k, 1]), float(host[k, 2]), a)
+                      for k, (i, (r, a)) in enumerate(zip(idx, rendered))])
+
+
+# ---------------------------------------------------------------------------- command line
+def detect_format(dataset: str) -> str:
+    """'nerf' when the directory / zip holds a transforms_*.json, else 'colmap'."""
+    import os
+
+    from .dataset import DatasetFiles
+
+    files = DatasetFiles(dataset)
+    names = files._names
+    for n in names:
+        base = os.path.basename(n)
+        if base.startswith("transforms_") and base.endswith(".json"):
+            return "nerf"
+    return "colmap"
+
+
+def _load_dataset(args):
+    from . import dataset as D
+
+    fmt = detect_format(args.dataset) if args.format == "auto" else args.format
+    reader = D.read_nerf_synthetic if fmt == "nerf" else D.read_colmap
+    return reader(args.dataset, max_resolution=args.max_resolution, eval_split_every=args.eval_split_every)
+
+
+def main(argv=None) -> int:
+    import argparse
+    import json
+    import os
+    import sys
+
+    p = argparse.ArgumentParser(prog="python -m brush_amd.eval",
+                                description="PSNR / SSIM of a splat file on a dataset's eval views")
+    p.add_argument("splats", help=".ply or .safetensors splat file")
+    p.add_argument("dataset", help="dataset directory or .zip (NeRF-synthetic or COLMAP)")
+    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
+    p.add_argument("--eval-split-every", type=int, default=None)
+    p.add_argument("--max-resolution", type=int, default=None)
+    p.add_argument("--num-frames", type=int, default=None)
+    p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--window", type=int, default=11)
+    p.add_argument("--json", default=None, help="also write the results to this file")
+    args = p.parse_args(argv)
+
+    data = _load_dataset(args)  # before any GPU work
+    if data.eval is None or not data.eval.views:
+        print(f"{args.dataset}: the dataset has no eval views (try --eval-split-every K)", file=sys.stderr)
+        return 2
+    from .gaussian_splats import Splats
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if args.splats.endswith(".safetensors"):
+        splats = Splats.from_safetensors(args.splats, dev)
+    else:
+        splats = Splats.from_ply(args.splats, dev)
+    rng = np.random.default_rng(args.seed)
+    stats = eval_stats(splats, data.eval, args.num_frames, rng, args.window)
+    for s in stats.samples:
+        print(f"{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
+    print(f"mean ({len(stats.samples)} views)\tpsnr {stats.mean_psnr():.4f}\tssim {stats.mean_ssim():.6f}")
+    if args.json:
+        res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "window": args.window,
+               "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in stats.samples],
+               "mean_psnr": stats.mean_psnr(), "mean_ssim": stats.mean_ssim()}
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -275,6 +275,26 @@ int brush_l1_ssim_loss(const float *pred, const float *gt, uint32_t w, uint32_t 
                        float ssim_weight, uint32_t ssim_window, float grad_scale, float *loss, float *v_pred,
                        void *workspace, size_t workspace_bytes, brush_stream_t stream);
 
+/* ---- evaluation on held-out views (build extension) -------------------------------------- */
+/* The per-view metrics of eval_stats (crates/brush-train/src/eval.rs:27-77) in one metrics-only pass: writes
+ * out[0..2] = {mse, psnr, ssim} (device, f32) and nothing per pixel.
+ *   mse  = mean((pred_rgb - gt_rgb)^2) over h*w*3 elements (eval.rs:55-57);
+ *   psnr = ln(1 / mse) * 10 / LN_10 in f32 (eval.rs:59), +inf when mse == 0;
+ *   ssim = mean of the SSIM map of ssim.rs:42-101 with Ssim::new(ssim_window, 3): Gaussian window sigma 1.5, zero
+ *          padding div_ceil(window, 2) (map (h+2)x(w+2)x3), variances clamped at 0, C1 = 0.01^2, C2 = 0.03^2.
+ * pred: [h,w,4] f32, the op's output; only RGB is read.  gt: [h,w,gt_channels], gt_channels 3 or 4, elements u8
+ * (BRUSH_EVAL_GT_U8, read as (float)b / 255.0f with an IEEE division, as image_to_tensor) or f32 (BRUSH_EVAL_GT_F32).
+ * The alpha of both is ignored: the reference compares to_rgb8() images (eval.rs:50-57).  ssim_window: odd sizes 3..15
+ * (the reference's eval uses 11).  Sums are reduced per block, then by one workgroup in a fixed order: the same inputs
+ * give the same bits on every call; no allocation or synchronisation, so the call can be captured into a graph.
+ * Images of 2^28 pixels or more return BRUSH_ERR_INVALID_ARG. */
+#define BRUSH_EVAL_GT_U8 0u
+#define BRUSH_EVAL_GT_F32 1u
+int brush_eval_workspace_size(uint32_t w, uint32_t h, size_t *bytes);
+int brush_eval_metrics(const float *pred, const void *gt, uint32_t gt_dtype, uint32_t w, uint32_t h,
+                       uint32_t gt_channels, uint32_t ssim_window, float *out, void *workspace,
+                       size_t workspace_bytes, brush_stream_t stream);
+
 /* Hyper-parameters of one optimizer step: the five learning rates of train.rs:275-282, the lerp
  * factor 1/lr_coeffs_sh_scale for SH coefficients >= 1 (train.rs:336-351), Adam betas/epsilon
  * (AdamConfig::new().with_epsilon(1e-15), train.rs:184) and the 1-based step count. */

@@ -5,10 +5,13 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
 
   render_splats / RenderAux  <- Backend::render_splats, RenderAux (src/lib.rs:20-86)
   Camera                     <- camera.rs
-  Splats                     <- gaussian_splats.rs (render + from_safetensors only)
+  Splats                     <- gaussian_splats.rs (render, from_safetensors / from_ply, from_point_cloud,
+                                from_random_config)
   radix_argsort              <- brush-sort/src/lib.rs:32-37
   prefix_sum                 <- brush-prefix-sum/src/lib.rs:17
   eval_stats / EvalStats     <- brush-train/src/eval.rs (also `python -m brush_amd.eval`)
+  train_scene / TrainLog     <- brush-viewer/src/train_loop.rs (also `python -m brush_amd.train_loop`)
+  scene_loader.SceneLoader   <- brush-dataset/src/scene_loader.rs (training images resident on the device as u8)
 
 All compute goes through the C ABI of include/brush_hip.h (libbrush_hip.so, hand-written HIP for
 gfx950).  There is no CPU fallback: importing the compute entry points without the built
@@ -23,15 +26,20 @@ from .gaussian_splats import Splats  # noqa: F401
 from .train import SplatTrainer, TrainConfig  # noqa: F401
 from . import dataset  # noqa: F401
 
-# brush_amd.eval is imported on first use: importing it here would load the module before `python -m brush_amd.eval`
-# runs it as __main__ (runpy then warns that it is loaded twice).
+# brush_amd.eval and brush_amd.train_loop are imported on first use: importing them here would load the module before
+# `python -m brush_amd.eval` / `python -m brush_amd.train_loop` runs it as __main__ (runpy then warns that it is loaded
+# twice).
 _EVAL_NAMES = ("eval_metrics", "eval_stats", "EvalStats", "EvalView")
+_TRAIN_LOOP_NAMES = ("train_scene", "TrainLog", "TrainLoop")
 
 
 def __getattr__(name):
     if name in _EVAL_NAMES:
         from . import eval as _eval
         return getattr(_eval, name)
+    if name in _TRAIN_LOOP_NAMES:
+        from . import train_loop as _train_loop
+        return getattr(_train_loop, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("BRUSH_HIP_LIB") or os.path.join(_HERE, "lib", "libbru
 BRUSH_OK = 0
 AUX_DETERMINISTIC = 1  # BrushAux.flags: BRUSH_AUX_DETERMINISTIC
 AUX_ACCUM_ZEROED = 2   # BrushAux.flags: BRUSH_AUX_ACCUM_ZEROED (backward only)
-EVAL_GT_U8 = 0         # brush_eval_metrics gt_dtype: BRUSH_EVAL_GT_U8
+EVAL_GT_U8 = 0         # brush_eval_metrics / brush_l1_ssim_loss_gt gt_dtype: BRUSH_EVAL_GT_U8
 EVAL_GT_F32 = 1        # BRUSH_EVAL_GT_F32
 UNIFORM_WORDS = 28
 NUM_VISIBLE_WORD = 25
@@ -133,6 +133,9 @@ _SYMBOLS = [
     ("brush_eval_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     ("brush_eval_metrics", C.c_int,
      [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_size_t, _P]),
+    ("brush_l1_ssim_loss_gt", C.c_int,
+     [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_float, _P, _P, _P, C.c_size_t,
+      _P]),
     ("brush_adam_step", C.c_int,
      [C.POINTER(BrushAdamConfig), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("brush_render_backward_adam", C.c_int,

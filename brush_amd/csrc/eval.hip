@@ -25,11 +25,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
-// One ground-truth sample at a wave-uniform row plus a per-lane element index.  u8 is (float)b / 255.0f, a correctly
-// rounded division as image_to_tensor / to_rgb32f compute it (a reciprocal multiply gives different bits).
-__device__ __forceinline__ float ld_gt(const float *row, uint32_t idx) { return ld_off(row, idx * 4u); }
-__device__ __forceinline__ float ld_gt(const uint8_t *row, uint32_t idx) { return (float)row[idx] / 255.0f; }
-
 // SSIM map position (oy, ox) for oy in the block's kSegRows rows, ox in the wave's kOutCols columns; the squared error
 // of input pixel (iy, ix) is counted by the wave holding map position (iy+1, ix+1), as k_ssim_forward counts |pred-gt|.
 template <int WIN, typename GT>

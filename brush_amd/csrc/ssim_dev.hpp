@@ -1,5 +1,6 @@
 // ssim_dev.hpp — the pieces of the separable SSIM blur shared by the training loss (train_step.hip) and the
-// metrics-only evaluation pass (eval.hip): the window and its geometry, the wave-uniform-row loads, the wave reduction.
+// metrics-only evaluation pass (eval.hip): the window and its geometry, the wave-uniform-row loads (ground truth as f32
+// or u8), the wave reduction.
 #pragma once
 #include "common.hpp"
 
@@ -35,6 +36,15 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float ld_off(const float *base, uint32_t byte_off) {
     return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + byte_off);
 }
+
+// One ground-truth sample at a wave-uniform row plus a per-lane BYTE offset (element index * sizeof(GT)).  u8 is
+// (float)b / 255.0f, a correctly rounded division as image_to_tensor / to_rgb32f compute it (a reciprocal multiply
+// gives different bits), so a u8 target reaches the arithmetic with the bits of an f32 target holding u8 / 255.
+__device__ __forceinline__ float ld_gt_off(const float *row, uint32_t byte_off) { return ld_off(row, byte_off); }
+__device__ __forceinline__ float ld_gt_off(const uint8_t *row, uint32_t byte_off) { return (float)row[byte_off] / 255.0f; }
+// The same at a per-lane element index.
+template <typename GT>
+__device__ __forceinline__ float ld_gt(const GT *row, uint32_t idx) { return ld_gt_off(row, idx * (uint32_t)sizeof(GT)); }
 
 // LDS traffic inside one wave is in order; this only stops the compiler from moving accesses.
 // A fence would also wait for the prefetched global loads, so this is a pure compiler barrier.

@@ -8,6 +8,8 @@
 //       map of an odd window is (h+2)x(w+2); variances clamped at 0) and d loss / d pred.  The window is outer(g, g), so
 //       every blur is two 1-D passes (same linear operator, ssim.rs:17-32 notes it as a TODO): horizontal
 //       through a per-wave LDS row buffer, vertical over a register ring while the wave marches down.
+//       The ground truth is f32 or u8 (template GT; u8 is read as b / 255 with an IEEE division, ld_gt_off in
+//       ssim_dev.hpp, so a resident u8 training image gives the bits of its f32 twin; brush_l1_ssim_loss_gt).
 //   k_adam : Adam with the reference's five learning rates and the SH-rest lerp (train.rs:318-359) over
 //       the gradient arrays the backward writes; update rule of burn 0.16 `Adam::step`
 //       (m/(1-b1^t) / (sqrt(v/(1-b2^t)) + eps)), eps = 1e-15 (train.rs:184).  The single-view trainer uses
@@ -47,8 +49,8 @@ __device__ __forceinline__ void st_off(float *base, uint32_t byte_off, float v) 
 // three derivative maps (wrt blur(a), blur(a*a), blur(a*b); a = pred, b = gt) scaled by `coef`, and
 // per-wave partial sums of the SSIM map and of |pred - gt| (each input pixel owned by the wave
 // holding map position (iy+1, ix+1)).
-template <int WIN>
-__global__ __launch_bounds__(192) void k_ssim_forward(const float *__restrict__ pred, const float *__restrict__ gt,
+template <int WIN, typename GT>
+__global__ __launch_bounds__(192) void k_ssim_forward(const float *__restrict__ pred, const GT *__restrict__ gt,
                                                       uint32_t gt_channels, uint32_t w, uint32_t h, Window win,
                                                       float coef, float *__restrict__ dmaps,
                                                       float *__restrict__ partials) {
@@ -74,7 +76,8 @@ __global__ __launch_bounds__(192) void k_ssim_forward(const float *__restrict__ 
     const uint32_t ixc = (uint32_t)min(max(ix, 0), (int)w - 1);
     const uint32_t p_al = alpha_on ? 3u : (uint32_t)ch;
     const uint32_t pc_a = (ixc * 4u + (uint32_t)ch) * 4u, pc_al = (ixc * 4u + p_al) * 4u;  // pred column byte offsets
-    const uint32_t gc_a = (ixc * gt_channels + (uint32_t)ch) * 4u, gc_al = (ixc * gt_channels + p_al) * 4u;  // gt
+    constexpr uint32_t kGtB = sizeof(GT);  // gt column byte offsets
+    const uint32_t gc_a = (ixc * gt_channels + (uint32_t)ch) * kGtB, gc_al = (ixc * gt_channels + p_al) * kGtB;
     struct Row {
         float a, b, pa, ga;
     };
@@ -83,15 +86,15 @@ __global__ __launch_bounds__(192) void k_ssim_forward(const float *__restrict__ 
         const bool row_ok = iy >= 0 && iy < (int)h;
         const uint32_t iyc = (uint32_t)min(max(iy, 0), (int)h - 1);
         const float *prow = pred + (size_t)iyc * w * 4u;
-        const float *grow = gt + (size_t)iyc * w * gt_channels;
+        const GT *grow = gt + (size_t)iyc * w * gt_channels;
         const bool ok = col_ok && row_ok;
         Row v;
         v.a = ld_off(prow, pc_a);
-        v.b = ld_off(grow, gc_a);
+        v.b = ld_gt_off(grow, gc_a);
         v.pa = v.ga = 0.0f;
         if (alpha_on) {  // wave-uniform: the strided loads are what the kernel waits for (16 cache lines per instruction)
             v.pa = ld_off(prow, pc_al);
-            v.ga = ld_off(grow, gc_al);
+            v.ga = ld_gt_off(grow, gc_al);
             v.pa = ok ? v.pa : 0.0f, v.ga = ok ? v.ga : 0.0f;
         }
         v.a = ok ? v.a : 0.0f, v.b = ok ? v.b : 0.0f;
@@ -171,8 +174,8 @@ __global__ __launch_bounds__(192) void k_ssim_forward(const float *__restrict__ 
 // Image position (py, px): T[X](p) = sum_j g[j] X[p - kOff + j] per axis (the transposed blur; g is
 // symmetric) of the three derivative maps, combined with the L1 term into d loss / d pred.  Wave 0
 // of block (0,0) also reduces the partial sums into the loss value.
-template <int WIN>
-__global__ __launch_bounds__(192) void k_ssim_backward(const float *__restrict__ pred, const float *__restrict__ gt,
+template <int WIN, typename GT>
+__global__ __launch_bounds__(192) void k_ssim_backward(const float *__restrict__ pred, const GT *__restrict__ gt,
                                                        uint32_t gt_channels, uint32_t w, uint32_t h, Window win,
                                                        const float *__restrict__ dmaps, float l1_coef,
                                                        float *__restrict__ v_pred, const float *__restrict__ partials,
@@ -200,7 +203,8 @@ __global__ __launch_bounds__(192) void k_ssim_backward(const float *__restrict__
     const uint32_t g_al = alpha_on ? 3u : 0u;
     const bool alpha_row = alpha_on && ch == 0;  // the wave that writes v_pred's alpha
     const uint32_t pc_a = (pxc * 4u + (uint32_t)ch) * 4u, pc_al = (pxc * 4u + 3u) * 4u;  // byte offsets
-    const uint32_t gc_a = (pxc * gt_channels + (uint32_t)ch) * 4u, gc_al = (pxc * gt_channels + g_al) * 4u;
+    constexpr uint32_t kGtB = sizeof(GT);
+    const uint32_t gc_a = (pxc * gt_channels + (uint32_t)ch) * kGtB, gc_al = (pxc * gt_channels + g_al) * kGtB;
     const uint32_t oc = oxc * 4u;
     struct Row {
         float x0, x1, x2, a, b, pa, ga;
@@ -211,12 +215,12 @@ __global__ __launch_bounds__(192) void k_ssim_backward(const float *__restrict__
         const size_t orow = (size_t)(uint32_t)min(max(oy, 0), H2 - 1) * (uint32_t)W2;
         const uint32_t pyc = (uint32_t)min(max(py0 + r - (WIN - 1), 0), (int)h - 1);
         const float *prow = pred + (size_t)pyc * w * 4u;
-        const float *grow = gt + (size_t)pyc * w * gt_channels;
+        const GT *grow = gt + (size_t)pyc * w * gt_channels;
         Row v;
         v.x0 = ld_off(d0 + orow, oc), v.x1 = ld_off(d1 + orow, oc), v.x2 = ld_off(d2 + orow, oc);
-        v.a = ld_off(prow, pc_a), v.b = ld_off(grow, gc_a);
+        v.a = ld_off(prow, pc_a), v.b = ld_gt_off(grow, gc_a);
         v.pa = v.ga = 0.0f;
-        if (alpha_row) v.pa = ld_off(prow, pc_al), v.ga = ld_off(grow, gc_al);  // wave-uniform
+        if (alpha_row) v.pa = ld_off(prow, pc_al), v.ga = ld_gt_off(grow, gc_al);  // wave-uniform
         v.x0 = ok ? v.x0 : 0.0f, v.x1 = ok ? v.x1 : 0.0f, v.x2 = ok ? v.x2 : 0.0f;
         return v;
     };
@@ -271,17 +275,20 @@ __global__ __launch_bounds__(192) void k_ssim_backward(const float *__restrict__
     }
 }
 
-// L1-only form (ssim_weight == 0, train.rs:254-266): one thread per pixel.
-__global__ __launch_bounds__(256) void k_l1_backward(const float4 *__restrict__ pred, const float *__restrict__ gt,
+// L1-only form (ssim_weight == 0, train.rs:254-266): one thread per pixel.  A u8 target is read byte by byte (the
+// pixel is 3 or 4 bytes at any alignment the caller passes).
+template <typename GT>
+__global__ __launch_bounds__(256) void k_l1_backward(const float4 *__restrict__ pred, const GT *__restrict__ gt,
                                                      uint32_t gt_channels, uint32_t npix, float l1_coef,
                                                      float4 *__restrict__ v_pred, float *__restrict__ partials) {
     __shared__ float red[4];
     float l1 = 0.0f;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
         const float4 p = pred[i];
-        const float *gp = gt + (size_t)i * gt_channels;
+        const GT *gp = gt + (size_t)i * gt_channels;
         auto sgn = [](float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); };
-        const float d0 = p.x - gp[0], d1 = p.y - gp[1], d2 = p.z - gp[2], d3 = gt_channels == 4 ? p.w - gp[3] : 0.0f;
+        const float d0 = p.x - ld_gt(gp, 0), d1 = p.y - ld_gt(gp, 1), d2 = p.z - ld_gt(gp, 2),
+                    d3 = gt_channels == 4 ? p.w - ld_gt(gp, 3) : 0.0f;
         l1 += fabsf(d0) + fabsf(d1) + fabsf(d2) + fabsf(d3);
         v_pred[i] = make_float4(l1_coef * sgn(d0), l1_coef * sgn(d1), l1_coef * sgn(d2), l1_coef * sgn(d3));
     }
@@ -317,17 +324,22 @@ extern "C" int brush_loss_workspace_size(uint32_t w, uint32_t h, size_t *bytes) 
     return BRUSH_OK;
 }
 
-extern "C" int brush_l1_ssim_loss(const float *pred, const float *gt, uint32_t w, uint32_t h, uint32_t gt_channels,
-                                  float ssim_weight, uint32_t ssim_window, float grad_scale, float *loss,
-                                  float *v_pred, void *workspace, size_t workspace_bytes, brush_stream_t stream) {
+namespace brush {
+namespace {
+
+// Argument checks shared by both loss entry points (the workspace size is checked by the caller).
+int loss_args_ok(const float *pred, const void *gt, uint32_t w, uint32_t h, uint32_t gt_channels, float ssim_weight,
+                 uint32_t ssim_window, const float *loss, const float *v_pred, const void *workspace) {
     if (!pred || !gt || !loss || !v_pred || !workspace || w == 0 || h == 0) return BRUSH_ERR_INVALID_ARG;
     if (gt_channels != 3 && gt_channels != 4) return BRUSH_ERR_INVALID_ARG;
     if (ssim_weight > 0.0f && !window_ok(ssim_window)) return BRUSH_ERR_INVALID_ARG;  // odd sizes 3..15
     if (9ull * (w + 2ull) * (h + 2ull) >= (1ull << 32)) return BRUSH_ERR_INVALID_ARG;   // 32-bit element offsets (477 M pixels)
-    size_t need = 0;
-    brush_loss_workspace_size(w, h, &need);
-    if (workspace_bytes < need) return BRUSH_ERR_WORKSPACE_SMALL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    return BRUSH_OK;
+}
+
+template <typename GT>
+void launch_loss(const float *pred, const GT *gt, uint32_t w, uint32_t h, uint32_t gt_channels, float ssim_weight,
+                 uint32_t ssim_window, float grad_scale, float *loss, float *v_pred, void *workspace, hipStream_t s) {
     const size_t plane = (size_t)(w + 2) * (h + 2);
     float *dmaps = static_cast<float *>(workspace);
     float *partials = reinterpret_cast<float *>(static_cast<char *>(workspace) + align_up(9 * plane * sizeof(float), 256));
@@ -336,11 +348,10 @@ extern "C" int brush_l1_ssim_loss(const float *pred, const float *gt, uint32_t w
     float4 *v4 = reinterpret_cast<float4 *>(v_pred);
     if (!(ssim_weight > 0.0f)) {
         const uint32_t npix = w * h, nblk = std::min(ceil_div(npix, 256u), kL1Blocks);
-        hipLaunchKernelGGL(k_l1_backward, dim3(nblk), dim3(256), 0, s, pred4, gt, gt_channels, npix, grad_scale * inv_l1,
-                           v4, partials);
+        hipLaunchKernelGGL((k_l1_backward<GT>), dim3(nblk), dim3(256), 0, s, pred4, gt, gt_channels, npix,
+                           grad_scale * inv_l1, v4, partials);
         hipLaunchKernelGGL(k_l1_finalize, dim3(1), dim3(64), 0, s, partials, nblk, inv_l1, loss);
-        BRUSH_HIP_CHECK(hipGetLastError());
-        return BRUSH_OK;
+        return;
     }
     const Window win = make_window((int)ssim_window);
     const float inv_ssim = 1.0f / (3.0f * (float)plane);
@@ -349,9 +360,9 @@ extern "C" int brush_l1_ssim_loss(const float *pred, const float *gt, uint32_t w
         using G = Geo<W>;                                                                                            \
         const dim3 gf(ceil_div(w + 2, (uint32_t)G::kOutCols), ceil_div(h + 2, (uint32_t)G::kSegRows));               \
         const dim3 gb(ceil_div(w, (uint32_t)G::kOutCols), ceil_div(h, (uint32_t)G::kSegRows));                       \
-        hipLaunchKernelGGL(k_ssim_forward<W>, gf, dim3(192), 0, s, pred, gt, gt_channels, w, h, win,                 \
+        hipLaunchKernelGGL((k_ssim_forward<W, GT>), gf, dim3(192), 0, s, pred, gt, gt_channels, w, h, win,           \
                            -ssim_weight * inv_ssim * grad_scale, dmaps, partials);                                   \
-        hipLaunchKernelGGL(k_ssim_backward<W>, gb, dim3(192), 0, s, pred, gt, gt_channels, w, h, win, dmaps,         \
+        hipLaunchKernelGGL((k_ssim_backward<W, GT>), gb, dim3(192), 0, s, pred, gt, gt_channels, w, h, win, dmaps,   \
                            (1.0f - ssim_weight) * inv_l1 * grad_scale, v_pred, partials, gf.x * gf.y * 3,            \
                            1.0f - ssim_weight, ssim_weight, inv_l1, inv_ssim, loss);                                 \
     } while (0)
@@ -365,6 +376,42 @@ extern "C" int brush_l1_ssim_loss(const float *pred, const float *gt, uint32_t w
         default: BRUSH_SSIM(15); break;
     }
 #undef BRUSH_SSIM
+}
+
+}  // namespace
+}  // namespace brush
+
+extern "C" int brush_l1_ssim_loss(const float *pred, const float *gt, uint32_t w, uint32_t h, uint32_t gt_channels,
+                                  float ssim_weight, uint32_t ssim_window, float grad_scale, float *loss,
+                                  float *v_pred, void *workspace, size_t workspace_bytes, brush_stream_t stream) {
+    const int st = loss_args_ok(pred, gt, w, h, gt_channels, ssim_weight, ssim_window, loss, v_pred, workspace);
+    if (st != BRUSH_OK) return st;
+    size_t need = 0;
+    brush_loss_workspace_size(w, h, &need);
+    if (workspace_bytes < need) return BRUSH_ERR_WORKSPACE_SMALL;
+    launch_loss(pred, gt, w, h, gt_channels, ssim_weight, ssim_window, grad_scale, loss, v_pred, workspace,
+                static_cast<hipStream_t>(stream));
+    BRUSH_HIP_CHECK(hipGetLastError());
+    return BRUSH_OK;
+}
+
+extern "C" int brush_l1_ssim_loss_gt(const float *pred, const void *gt, uint32_t gt_dtype, uint32_t w, uint32_t h,
+                                     uint32_t gt_channels, float ssim_weight, uint32_t ssim_window, float grad_scale,
+                                     float *loss, float *v_pred, void *workspace, size_t workspace_bytes,
+                                     brush_stream_t stream) {
+    const int st = loss_args_ok(pred, gt, w, h, gt_channels, ssim_weight, ssim_window, loss, v_pred, workspace);
+    if (st != BRUSH_OK) return st;
+    if (gt_dtype != BRUSH_EVAL_GT_U8 && gt_dtype != BRUSH_EVAL_GT_F32) return BRUSH_ERR_INVALID_ARG;
+    size_t need = 0;
+    brush_loss_workspace_size(w, h, &need);
+    if (workspace_bytes < need) return BRUSH_ERR_WORKSPACE_SMALL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (gt_dtype == BRUSH_EVAL_GT_U8)
+        launch_loss(pred, static_cast<const uint8_t *>(gt), w, h, gt_channels, ssim_weight, ssim_window, grad_scale,
+                    loss, v_pred, workspace, s);
+    else
+        launch_loss(pred, static_cast<const float *>(gt), w, h, gt_channels, ssim_weight, ssim_window, grad_scale,
+                    loss, v_pred, workspace, s);
     BRUSH_HIP_CHECK(hipGetLastError());
     return BRUSH_OK;
 }

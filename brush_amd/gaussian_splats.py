@@ -1,6 +1,7 @@
-"""Splats — the slice of crates/brush-render/src/gaussian_splats.rs the hot path needs:
-the parameter container, `render` (quaternion normalisation outside the op, :167-188) and
-`from_safetensors` (:208-223).  Initialisation / kd-tree code is out of scope.
+"""Splats — the slice of crates/brush-render/src/gaussian_splats.rs the trainer and the hot path need:
+the parameter container, `render` (quaternion normalisation outside the op, :167-188), `from_safetensors`
+(:208-223), and the initialisations `from_point_cloud` (:71-136, nearest-neighbour scales on the host through
+dataset.splat_init_from_point_cloud) and `from_random_config` (:41-69).
 """
 from __future__ import annotations
 
@@ -43,6 +44,41 @@ class Splats(torch.nn.Module):
             return torch.as_tensor(a, dtype=torch.float32, device=device)
 
         return cls(dev(t["means"]), dev(t["coeffs"]), dev(t["quats"]), dev(t["opacities"]), dev(t["scales"]))
+
+    @classmethod
+    def from_point_cloud(cls, positions, colors, sh_degree: int, device):
+        """gaussian_splats.rs:71-136: positions [n,3], colours [n,3] in 0..1 (array-likes) -> splats with the DC colour,
+        identity rotations, opacity 0.1 and isotropic scales from the 3 nearest neighbours
+        (dataset.splat_init_from_point_cloud, computed on the host)."""
+        import numpy as np
+
+        from .dataset import splat_init_from_point_cloud
+
+        d = splat_init_from_point_cloud(np.asarray(positions, dtype=np.float32).reshape(-1, 3),
+                                        np.asarray(colors, dtype=np.float32).reshape(-1, 3), int(sh_degree))
+        t = lambda a: torch.as_tensor(a, dtype=torch.float32, device=device)
+        return cls(t(d["means"]), t(d["sh"]), t(d["quats"]), t(d["raw_opac"]), t(d["log_scales"]))
+
+    @classmethod
+    def from_random_config(cls, init_count: int = 10000, sh_degree: int = 0, bounds=None, rng=None, device=None):
+        """gaussian_splats.rs:41-69 (RandomSplatsConfig): `init_count` positions uniform in the box `bounds` = (lo, hi)
+        (e.g. Scene.bounds(near, far)), then as many colours uniform in [0, 1), then from_point_cloud.  `rng`: a
+        numpy.random.Generator (a fresh unseeded one when None).  The draws keep the reference's order (all positions x,
+        y, z per point, then all colours) but not its bits: the reference samples with Rust's StdRng, whose stream
+        numpy cannot reproduce, so the same seed gives different splats here."""
+        import numpy as np
+
+        if bounds is None:
+            raise ValueError("from_random_config needs bounds = (lo, hi)")
+        lo = np.asarray(bounds[0], dtype=np.float32).reshape(3)
+        hi = np.asarray(bounds[1], dtype=np.float32).reshape(3)
+        rng = np.random.default_rng() if rng is None else rng
+        n = int(init_count)
+        positions = rng.uniform(lo, hi, size=(n, 3)).astype(np.float32)
+        # rng.uniform rounds into the f32 box; gen_range(min..max) is half-open: keep the points inside it
+        positions = np.minimum(np.maximum(positions, lo), np.nextafter(hi, lo, dtype=np.float32))
+        colors = rng.random((n, 3)).astype(np.float32)
+        return cls.from_point_cloud(positions, colors, sh_degree, device)
 
     @classmethod
     def from_ply(cls, path_or_bytes, device):

@@ -80,24 +80,39 @@ def quaternion_vec_multiply(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
 
 
 def l1_ssim_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_weight: float, window: int = 11,
-                 grad_scale: float = 1.0):
-    """(loss [1] device tensor, d loss / d pred [h,w,4]) through brush_l1_ssim_loss."""
+                 grad_scale: float = 1.0, out: Optional[torch.Tensor] = None):
+    """(loss [1] device tensor, d loss / d pred [h,w,4]) through brush_l1_ssim_loss.  A torch.uint8 `gt` (a view's
+    image as decoded, kept on the device) goes to brush_l1_ssim_loss_gt and is read as b / 255 in the kernels: the
+    result is bitwise that of the float32 target u8 / 255.  Other dtypes are converted with .float().
+    `out`: optional contiguous float32 [1] device tensor on pred's device to write the loss into (e.g. one element of a
+    preallocated per-step log); it is also the returned loss tensor."""
     assert pred.is_cuda and gt.is_cuda, "brush_amd has no CPU path: tensors must live on the GPU"
     h, w = int(pred.shape[0]), int(pred.shape[1])
     if tuple(pred.shape) != (h, w, 4) or tuple(gt.shape[:2]) != (h, w) or gt.shape[2] not in (3, 4):
         raise ValueError(f"pred must be [h,w,4] and gt [h,w,3|4], got {tuple(pred.shape)} / {tuple(gt.shape)}")
-    pred, gt = pred.contiguous().float(), gt.contiguous().float()
+    if out is not None and (tuple(out.shape) != (1,) or out.dtype != torch.float32 or not out.is_contiguous()
+                            or out.device != pred.device):
+        raise ValueError("out must be a contiguous float32 [1] tensor on pred's device")
+    u8 = gt.dtype == torch.uint8
+    pred, gt = pred.contiguous().float(), (gt.contiguous() if u8 else gt.contiguous().float())
     l = _lib.lib()
     nbytes = C.c_size_t()
     _lib.check(l.brush_loss_workspace_size(w, h, C.byref(nbytes)), "brush_loss_workspace_size")
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=pred.device)
-    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device) if out is None else out
     v_pred = torch.empty_like(pred)
     with torch.cuda.device(pred.device):
-        _lib.check(l.brush_l1_ssim_loss(pred.data_ptr(), gt.data_ptr(), w, h, int(gt.shape[2]), float(ssim_weight),
-                                        int(window), float(grad_scale), loss.data_ptr(), v_pred.data_ptr(),
-                                        ws.data_ptr(), nbytes.value, torch.cuda.current_stream().cuda_stream),
-                   "brush_l1_ssim_loss")
+        stream = torch.cuda.current_stream().cuda_stream
+        if u8:
+            _lib.check(l.brush_l1_ssim_loss_gt(pred.data_ptr(), gt.data_ptr(), _lib.EVAL_GT_U8, w, h, int(gt.shape[2]),
+                                               float(ssim_weight), int(window), float(grad_scale), loss.data_ptr(),
+                                               v_pred.data_ptr(), ws.data_ptr(), nbytes.value, stream),
+                       "brush_l1_ssim_loss_gt")
+        else:
+            _lib.check(l.brush_l1_ssim_loss(pred.data_ptr(), gt.data_ptr(), w, h, int(gt.shape[2]), float(ssim_weight),
+                                            int(window), float(grad_scale), loss.data_ptr(), v_pred.data_ptr(),
+                                            ws.data_ptr(), nbytes.value, stream),
+                       "brush_l1_ssim_loss")
     return loss, v_pred
 
 
@@ -255,9 +270,12 @@ class SplatTrainer:
         return c.lr_mean * gamma ** self.iter * scene_extent
 
     def step(self, splats: Splats, camera: Camera, gt_image: torch.Tensor, scene_extent: float = 1.0,
-             batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None):
+             batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None,
+             loss_out: Optional[torch.Tensor] = None):
         """One reference training iteration on one view (batch size is 1 in the reference,
-        train.rs:216-219).  With view-sharded data parallelism call it on each rank with
+        train.rs:216-219).  `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the
+        same bits as its float32 twin; brush_amd.scene_loader keeps the training images on the device in this form).
+        `loss_out`: optional float32 [1] device tensor the loss is written into (l1_ssim_loss's `out`).  With view-sharded data parallelism call it on each rank with
         `batch_views` = world size and either `exchange` = a brush_amd.dist.ViewExchange (per-view gradient
         records all-gathered, summed per splat in view order and fed straight into Adam: every rank applies
         the same bits) or `grad_sync(block, aux)` summing the dense gradient block over views
@@ -294,7 +312,7 @@ class SplatTrainer:
                                        lazy_sh=lazy)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
-        loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views)
+        loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views, out=loss_out)
         do_refine = self.iter < c.max_refine_step and self.iter >= c.warmup_steps and self.iter % c.refine_every == 1
         pre_step = None
         if do_refine:  # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)

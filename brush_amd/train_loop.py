@@ -1,0 +1,259 @@
+"""Training a scene end to end — mirror of crates/brush-viewer/src/train_loop.rs without the viewer's messages.
+
+    dataset -> initial splats -> (random training view, SplatTrainer.step) x steps -> eval on request -> splats
+
+Initial splats (train_loop.rs:57-90): a caller's splats (e.g. a .ply) win; else the COLMAP SfM points
+(colmap_initial_points + Splats.from_point_cloud); else `Splats.from_random_config` inside
+`train.bounds(0.25 |e|, |e|)`, |e| the length of `train.bounds(0, 0)`'s extent.  The training images are uploaded
+once, as u8, by scene_loader.SceneLoader, and the loss kernels read them as they are (brush_l1_ssim_loss_gt).  Each
+step's loss goes into a preallocated device log; between refinements a step neither uploads, reads back nor
+synchronises, and the log is read back at eval points and at the end.
+
+Command line (one line per eval and a last line; --json also writes the eval rows and the loss curve):
+
+    python -m brush_amd.train_loop DATASET [--steps 30000] [--format auto|nerf|colmap] [--max-resolution R]
+        [--eval-split-every K] [--eval-every N] [--eval-views V] [--init PLY] [--init-count 10000] [--sh-degree 3]
+        [--seed 42] [--export OUT.ply] [--json LOG]
+
+BRUSH_DETERMINISTIC=1 makes the renders (and so a run with a fixed seed) bitwise repeatable.
+"""
+from __future__ import annotations
+
+import dataclasses
+import time
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .dataset import Dataset
+from .gaussian_splats import Splats
+from .scene_loader import SceneLoader
+from .train import SplatTrainer, TrainConfig
+
+
+@dataclass
+class EvalRow:
+    step: int           # training steps done when the eval ran
+    psnr: float         # mean over the eval views
+    ssim: float
+    splats: int
+    seconds: float      # wall time since the loop started, evals included
+    loss: float         # loss of the last step (nan at step 0)
+    iters_per_s: float  # training steps per second since the previous eval row, evals excluded
+
+
+@dataclass
+class TrainLog:
+    steps: int
+    losses: np.ndarray                            # [steps] f32, the loss of every step
+    evals: List[EvalRow] = field(default_factory=list)
+    seconds: float = 0.0                          # wall time of the whole loop
+    train_seconds: float = 0.0                    # the same without the evals
+    image_bytes: int = 0                          # training images resident on the device
+    num_splats: int = 0
+
+    def to_json(self) -> dict:
+        return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
+                "image_bytes": self.image_bytes, "num_splats": self.num_splats,
+                "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
+
+
+def _colmap_points(root: str) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+    """The SfM points of a COLMAP dataset (colmap_initial_points), or None when it has no non-empty points3D file."""
+    from . import dataset as D
+
+    files = D.DatasetFiles(root)
+    _, _, ext = D._colmap_paths(files)
+    if files.find_base_path(f"sparse/0/points3D.{ext}") is None:
+        return None
+    pos, col = D.colmap_initial_points(root)
+    return (pos, col) if pos.shape[0] > 0 else None
+
+
+def load_dataset(root: str, fmt: str = "auto", max_resolution: Optional[int] = None,
+                 eval_split_every: Optional[int] = None):
+    """(Dataset, COLMAP SfM points or None) of a dataset directory or zip; host only (no device work)."""
+    import argparse
+
+    from .eval import _load_dataset, detect_format
+
+    fmt = detect_format(root) if fmt == "auto" else fmt
+    data = _load_dataset(argparse.Namespace(dataset=root, format=fmt, max_resolution=max_resolution,
+                                            eval_split_every=eval_split_every))
+    return data, (_colmap_points(root) if fmt == "colmap" else None)
+
+
+def random_init_bounds(scene) -> Tuple[np.ndarray, np.ndarray]:
+    """train_loop.rs:80-90: |e| = length of bounds(0, 0).extent (the half-size), box = bounds(0.25 |e|, |e|)."""
+    lo, hi = scene.bounds(0.0, 0.0)
+    e = float(np.linalg.norm((hi.astype(np.float32) - lo.astype(np.float32)) / np.float32(2.0)))
+    return scene.bounds(e * 0.25, e)
+
+
+class TrainLoop:
+    """The state of one run: splats, trainer, resident views and the device loss log.  `train_scene` drives it; tests
+    and tools may call step() / evaluate() themselves (from one thread, on the current stream)."""
+
+    def __init__(self, dataset: Dataset, config: Optional[TrainConfig] = None, *, steps: int, init=None,
+                 init_count: int = 10000, sh_degree: int = 3, seed: int = 42, device=None):
+        if steps < 0:
+            raise ValueError(f"steps must be >= 0, got {steps}")
+        self.dataset = dataset
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        # the mean learning rate decays over the run; the refinement RNG takes the run's seed (train_loop.rs:44-46)
+        self.config = dataclasses.replace(config or TrainConfig(), total_steps=max(int(steps), 1), seed=int(seed))
+        self.steps = int(steps)
+        self.rng = np.random.default_rng(seed)  # random init and eval view choice, as the reference's one StdRng
+        if isinstance(init, Splats):
+            self.splats = init
+        elif init is not None:
+            positions, colors = init
+            self.splats = Splats.from_point_cloud(positions, colors, sh_degree, self.device)
+        else:
+            self.splats = Splats.from_random_config(init_count, sh_degree, random_init_bounds(dataset.train), self.rng,
+                                                    self.device)
+        self.loader = SceneLoader(dataset.train, seed, self.device)
+        self.trainer = SplatTrainer(self.splats, self.config)
+        self.losses = torch.zeros(self.steps, dtype=torch.float32, device=self.device)
+        self.done = 0
+        self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes)
+        self._t0 = time.perf_counter()
+        self._eval_seconds = 0.0
+        self._last = (0, 0.0)  # (step, training seconds) of the previous eval row
+
+    def step(self):
+        """One training iteration on a random view; its loss lands in the device log."""
+        if self.done >= self.steps:
+            raise RuntimeError(f"the run has {self.steps} steps, all done")
+        view, gt = self.loader.next_batch()
+        self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
+                          loss_out=self.losses[self.done:self.done + 1])
+        self.done += 1
+
+    def evaluate(self, eval_views: Optional[int] = None) -> Tuple[EvalRow, object]:
+        """eval_stats on the dataset's eval views, between steps, on this thread and stream (its docstring's rule);
+        appends and returns the EvalRow (and the EvalStats)."""
+        from .eval import eval_stats
+
+        if self.dataset.eval is None or not self.dataset.eval.views:
+            raise ValueError("the dataset has no eval views")
+        torch.cuda.synchronize(self.device)  # the training time up to here is done
+        t = time.perf_counter()
+        train_s = t - self._t0 - self._eval_seconds
+        stats = eval_stats(self.splats, self.dataset.eval, eval_views, self.rng)
+        loss = float(self.losses[self.done - 1].item()) if self.done > 0 else float("nan")
+        dstep, dt = self.done - self._last[0], train_s - self._last[1]
+        row = EvalRow(self.done, stats.mean_psnr(), stats.mean_ssim(), self.splats.num_splats(),
+                      time.perf_counter() - self._t0, loss, dstep / dt if dstep > 0 and dt > 0 else float("nan"))
+        self._last = (self.done, train_s)
+        self._eval_seconds += time.perf_counter() - t
+        self.log.evals.append(row)
+        return row, stats
+
+    def finish(self) -> Tuple[Splats, TrainLog]:
+        """Applies the trainer's pending SH steps (the returned splats are current) and reads the loss log back."""
+        self.trainer.sync(self.splats)
+        self.log.losses = self.losses.cpu().numpy()  # synchronises
+        self.log.seconds = time.perf_counter() - self._t0
+        self.log.train_seconds = self.log.seconds - self._eval_seconds
+        self.log.num_splats = self.splats.num_splats()
+        return self.splats, self.log
+
+
+def train_scene(dataset: Dataset, config: Optional[TrainConfig] = None, *, steps: int, init=None,
+                init_count: int = 10000, sh_degree: int = 3, seed: int = 42, eval_every: int = 0,
+                eval_views: Optional[int] = None, on_eval: Optional[Callable] = None,
+                device=None) -> Tuple[Splats, TrainLog]:
+    """Trains `dataset.train` for `steps` iterations (train_loop.rs) and returns (current splats, TrainLog).
+
+    `config` is copied with total_steps = steps and seed = seed.  `init`: Splats to start from, or (positions,
+    colours) of a point cloud (e.g. load_dataset's COLMAP points), or None for from_random_config(init_count,
+    sh_degree) in random_init_bounds(dataset.train).  `eval_every` > 0: eval_stats at step 0, every `eval_every` steps
+    and after the last step, on `eval_views` views (all when None) chosen with the run's rng; `on_eval(row, stats)` is
+    called after each."""
+    if eval_every > 0 and (dataset.eval is None or not dataset.eval.views):
+        raise ValueError("eval_every > 0 needs a dataset with eval views")
+    loop = TrainLoop(dataset, config, steps=steps, init=init, init_count=init_count, sh_degree=sh_degree, seed=seed,
+                     device=device)
+
+    def ev():
+        row, stats = loop.evaluate(eval_views)
+        if on_eval is not None:
+            on_eval(row, stats)
+
+    if eval_every > 0:
+        ev()
+    for i in range(steps):
+        loop.step()
+        if eval_every > 0 and (loop.done % eval_every == 0 or loop.done == steps):
+            ev()
+    return loop.finish()
+
+
+# ---------------------------------------------------------------------------- command line
+def main(argv=None) -> int:
+    import argparse
+    import json
+    import os
+    import sys
+
+    p = argparse.ArgumentParser(prog="python -m brush_amd.train_loop",
+                                description="train splats on a dataset (NeRF-synthetic or COLMAP)")
+    p.add_argument("dataset", help="dataset directory or .zip")
+    p.add_argument("--steps", type=int, default=30000)
+    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
+    p.add_argument("--max-resolution", type=int, default=None)
+    p.add_argument("--eval-split-every", type=int, default=None)
+    p.add_argument("--eval-every", type=int, default=0, help="eval every N steps (0: never)")
+    p.add_argument("--eval-views", type=int, default=None, help="eval views per eval (default: all)")
+    p.add_argument("--init", default=None, help="start from this .ply instead of the dataset's points / random splats")
+    p.add_argument("--init-count", type=int, default=10000, help="random initial splats when there are no points")
+    p.add_argument("--sh-degree", type=int, default=3)
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--export", default=None, help="write the trained splats to this .ply")
+    p.add_argument("--json", default=None, help="write the eval rows and the loss curve to this file")
+    args = p.parse_args(argv)
+    if not os.path.exists(args.dataset):
+        p.error(f"dataset not found: {args.dataset}")
+    if args.steps < 0 or args.eval_every < 0:
+        p.error("--steps and --eval-every must be >= 0")
+    if args.init is not None and not os.path.isfile(args.init):
+        p.error(f"--init file not found: {args.init}")
+
+    data, points = load_dataset(args.dataset, args.format, args.max_resolution, args.eval_split_every)  # host only
+    if not data.train.views:
+        print(f"{args.dataset}: the dataset has no training views", file=sys.stderr)
+        return 2
+    if args.eval_every > 0 and (data.eval is None or not data.eval.views):
+        print(f"{args.dataset}: --eval-every needs eval views (try --eval-split-every K)", file=sys.stderr)
+        return 2
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    init = Splats.from_ply(args.init, dev) if args.init else points
+
+    def on_eval(row, stats):
+        print(f"step {row.step}\tpsnr {row.psnr:.4f}\tssim {row.ssim:.6f}\tsplats {row.splats}\t"
+              f"{row.iters_per_s:.1f} it/s", flush=True)
+
+    splats, log = train_scene(data, TrainConfig(), steps=args.steps, init=init, init_count=args.init_count,
+                              sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,
+                              eval_views=args.eval_views, on_eval=on_eval, device=dev)
+    final = float(log.losses[-1]) if log.steps else float("nan")
+    rate = log.steps / log.train_seconds if log.train_seconds > 0 else float("nan")
+    print(f"done: {log.steps} steps in {log.seconds:.1f} s ({rate:.1f} it/s), {log.num_splats} splats, "
+          f"final loss {final:.6f}, {log.image_bytes / 1e6:.1f} MB of images on the device")
+    if args.export:
+        with open(args.export, "wb") as f:
+            f.write(splats.to_ply())
+    if args.json:
+        res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree}
+        res.update(log.to_json())
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -295,6 +295,16 @@ int brush_eval_metrics(const float *pred, const void *gt, uint32_t gt_dtype, uin
                        uint32_t gt_channels, uint32_t ssim_window, float *out, void *workspace,
                        size_t workspace_bytes, brush_stream_t stream);
 
+/* brush_l1_ssim_loss with the ground truth's element type chosen per call: gt_dtype BRUSH_EVAL_GT_U8 (a training image
+ * kept on the device as uploaded, read as (float)b / 255.0f with an IEEE division, as image_to_tensor) or
+ * BRUSH_EVAL_GT_F32 (the same as brush_l1_ssim_loss).  A u8 target gives the bits of an f32 target holding u8 / 255:
+ * loss and v_pred are bitwise those of brush_l1_ssim_loss on that f32 image.  Same workspace
+ * (brush_loss_workspace_size), the same argument checks and status codes; any other gt_dtype returns
+ * BRUSH_ERR_INVALID_ARG. */
+int brush_l1_ssim_loss_gt(const float *pred, const void *gt, uint32_t gt_dtype, uint32_t w, uint32_t h,
+                          uint32_t gt_channels, float ssim_weight, uint32_t ssim_window, float grad_scale, float *loss,
+                          float *v_pred, void *workspace, size_t workspace_bytes, brush_stream_t stream);
+
 /* Hyper-parameters of one optimizer step: the five learning rates of train.rs:275-282, the lerp
  * factor 1/lr_coeffs_sh_scale for SH coefficients >= 1 (train.rs:336-351), Adam betas/epsilon
  * (AdamConfig::new().with_epsilon(1e-15), train.rs:184) and the 1-based step count. */

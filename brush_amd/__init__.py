@@ -4,6 +4,7 @@ Host-side mirror (Python, because no Rust toolchain exists in the build image) o
 crates/brush-render's public interface for the forward+backward rasterizer path:
 
   render_splats / RenderAux  <- Backend::render_splats, RenderAux (src/lib.rs:20-86)
+  render_splats_depth        <- render_splats plus the accumulated depth map (build extension, no reference)
   Camera                     <- camera.rs
   Splats                     <- gaussian_splats.rs (render, from_safetensors / from_ply, from_point_cloud,
                                 from_random_config)
@@ -18,8 +19,8 @@ gfx950).  There is no CPU fallback: importing the compute entry points without t
 library raises.
 """
 from .camera import Camera, fov_to_focal, focal_to_fov  # noqa: F401
-from .render import (RenderAux, render_rgba8, render_splats, rgba8_row_pitch, sh_coeffs_for_degree,  # noqa: F401
-                     sh_degree_from_coeffs)
+from .render import (RenderAux, render_rgba8, render_splats, render_splats_depth, rgba8_row_pitch,  # noqa: F401
+                     sh_coeffs_for_degree, sh_degree_from_coeffs)
 from .sort import radix_argsort  # noqa: F401
 from .prefix_sum import prefix_sum  # noqa: F401
 from .gaussian_splats import Splats  # noqa: F401

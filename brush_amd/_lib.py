@@ -111,6 +111,8 @@ _SYMBOLS = [
     ("brush_render_forward_rgba8", C.c_int,
      [C.POINTER(BrushUniforms), _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(BrushAux), _P,
       C.c_size_t, _P]),
+    ("brush_render_forward_depth", C.c_int,
+     [C.POINTER(BrushUniforms), _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(BrushAux), _P, C.c_size_t, _P]),
     ("brush_deterministic", C.c_int, []),
     ("brush_bwd_workspace_size_flags", C.c_int,
      [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
@@ -121,6 +123,9 @@ _SYMBOLS = [
     ("brush_render_backward", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P,
       _P, _P, _P, C.c_size_t, _P]),
+    ("brush_render_backward_depth", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+      _P, _P, C.c_size_t, _P]),
     ("brush_render_backward_records", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
       C.c_size_t, _P]),

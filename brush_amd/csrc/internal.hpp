@@ -44,7 +44,9 @@ hipError_t launch_rasterize(uint32_t w, uint32_t h, uint32_t tbx, uint32_t tby,
                             const float *projected, int raster_u32, uint32_t u32_pitch, void *out_img,
                             uint32_t *final_index, float *zero_rows /* nullable: [n][kCompactStride], the first
                             *num_visible rows are zeroed (BrushAux::bwd_accum) */,
-                            const uint32_t *num_visible, uint32_t n, hipStream_t s);
+                            const uint32_t *num_visible, uint32_t n, hipStream_t s,
+                            const float *compact_depth = nullptr /* brush_render_forward_depth: [n] z, compact order */,
+                            float *out_depth = nullptr /* [h][w]: accumulated depth (float image only) */);
 // Zero-fill the compositing backward carries beside its arithmetic: the dense gradient arrays of the same backward
 // (render.rs:539-547,573-575 zero-fills them with separate launches).  The kernel is bound by VALU issue and moves
 // little memory, so its waves store the zeros in passing, one KiB (64 lanes x 16 B) per wave instruction, paced over
@@ -66,7 +68,9 @@ hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint3
                                      const float *out_img, const float *v_out, float *v_compact,
                                      const uint32_t *unsorted_pos /* deterministic mode, else nullptr */,
                                      float *rows /* deterministic mode: [max_intersects][12], else nullptr */,
-                                     const ZeroFill &fill, hipStream_t s);
+                                     const ZeroFill &fill, hipStream_t s,
+                                     const float *compact_depth = nullptr /* brush_render_backward_depth: [n] z */,
+                                     const float *v_depth = nullptr /* [h][w]: gradient of the accumulated depth */);
 
 // project_bwd.hip
 // Optimizer state for the fused backward + Adam form (brush_render_backward_adam).
@@ -113,6 +117,14 @@ hipError_t launch_reduce_view_records(const float *records, uint32_t num_views, 
                                       const float *campos, const float *means, uint32_t n,
                                       uint32_t sh_degree, uint32_t *index, float *v_means, float *v_scales,
                                       float *v_quats, float *v_sh, float *v_opac, const AdamFuse *adam, hipStream_t s);
+// brush_render_backward_depth: v_means[g] += v_z viewmat row 2 for every visible splat, v_z = word 9 of its compact
+// row (default mode) or the fixed-order sum of word 10 of its intersection rows (deterministic mode).  Runs after
+// launch_sum_isect_rows / launch_project_backward.
+hipError_t launch_sum_isect_depth(const float *rows, const uint32_t *num_intersections, const uint32_t *cum_tiles_hit,
+                                  uint32_t cap, float *v_compact, float *partials, hipStream_t s);
+hipError_t launch_depth_means_grad(const ViewParams &vp, const uint32_t *num_visible, uint32_t n,
+                                   const uint32_t *global_from_compact, const float *v_compact, const DetSumsArgs &det,
+                                   float *v_means, hipStream_t s);
 hipError_t launch_zero_compact_grads(const uint32_t *num_visible, uint32_t n, float *v_compact, hipStream_t s);
 
 }  // namespace brush

@@ -242,6 +242,79 @@ __global__ __launch_bounds__(kThreads) void k_sum_isect_rows(const float4 *__res
     }
 }
 
+// ---- accumulated depth (brush_render_backward_depth) -------------------------------------------------------------------
+// v_z of a visible splat: word 9 of its compact row; in deterministic mode the compositing backward leaves it in word 10
+// of every intersection row (word 9 is the gid) and k_sum_isect_depth sums it exactly as k_sum_isect_rows sums words
+// 0..8: same segments, same tree, same chunk-order partials (word 9 of v_compact / partials, written after that kernel).
+constexpr uint32_t kDepthWord = 9, kDepthRowWord = 10;
+
+__device__ __forceinline__ float load_compact_depth(const float *__restrict__ v_compact, const DetSums &det, uint32_t c) {
+    const float *row = v_compact + (size_t)c * kCompactStride;
+    if (!det.partials) return row[kDepthWord];
+    const uint32_t I = min(*det.num_intersections, det.cap);
+    const uint32_t u0 = c ? min(det.cum_tiles_hit[c - 1], I) : 0u, u1 = min(det.cum_tiles_hit[c], I);
+    if (u1 <= u0) return 0.0f;
+    const uint32_t k0 = u0 / kWave, k1 = (u1 - 1u) / kWave;
+    if (k0 == k1) return row[kDepthWord];
+    float v = 0.0f;
+    for (uint32_t k = k0; k <= k1; k++)  // chunk order
+        v += det.partials[((size_t)k * 2 + (k == k0 ? 1 : 0)) * kCompactStride + kDepthWord];
+    return v;
+}
+
+__global__ __launch_bounds__(kThreads) void k_sum_isect_depth(const float *__restrict__ rows,
+                                                              const uint32_t *__restrict__ num_intersections,
+                                                              const uint32_t *__restrict__ cum_tiles_hit, uint32_t cap,
+                                                              float *__restrict__ v_compact,
+                                                              float *__restrict__ partials) {
+    const uint32_t I = min(*num_intersections, cap);
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t waves = gridDim.x * (kThreads / kWave);
+    for (uint32_t k = blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave; (uint64_t)k * kWave < I; k += waves) {
+        const uint32_t base = k * kWave, u = base + lane;
+        const bool valid = u < I;
+        float v = 0.0f;
+        uint32_t c = 0, first = lane, last = lane;
+        bool starts_here = true, ends_here = true;
+        if (valid) {
+            v = rows[(size_t)u * kCompactStride + kDepthRowWord];
+            c = __float_as_uint(rows[(size_t)u * kCompactStride + 9]);
+            const uint32_t u0 = c ? min(cum_tiles_hit[c - 1], I) : 0u, u1 = min(cum_tiles_hit[c], I);
+            starts_here = u0 >= base;
+            ends_here = u1 <= base + kWave;
+            first = max(u0, base) - base;
+            last = min(u1, base + kWave) - 1u - base;
+        }
+#pragma unroll
+        for (uint32_t dist = 1; dist < kWave; dist <<= 1) {
+            const float up = __shfl_up(v, dist, 64);
+            if (lane >= first + dist) v += up;
+        }
+        if (valid && lane == last) {
+            float *dst = (starts_here && ends_here) ? v_compact + (size_t)c * kCompactStride
+                                                    : partials + ((size_t)k * 2 + (starts_here ? 1 : 0)) * kCompactStride;
+            dst[kDepthWord] = v;
+        }
+    }
+}
+
+// v_means[g] += v_z * (d z / d mean) = v_z * viewmat row 2 (p_view = W mean + t, project_forward.wgsl:29-30), one lane
+// per visible splat, after the parameter VJP has written v_means.  A zero v_z leaves the row untouched (bitwise).
+__global__ __launch_bounds__(kThreads) void k_depth_means_grad(const ViewParams vp,
+                                                               const uint32_t *__restrict__ num_visible, uint32_t n,
+                                                               const uint32_t *__restrict__ global_from_compact,
+                                                               const float *__restrict__ v_compact, const DetSums det,
+                                                               float *__restrict__ v_means) {
+    const uint32_t V = min(*num_visible, n);
+    for (uint32_t c = blockIdx.x * kThreads + threadIdx.x; c < V; c += gridDim.x * kThreads) {
+        const float vz = load_compact_depth(v_compact, det, c);
+        if (vz == 0.0f) continue;
+        float *m = v_means + (size_t)global_from_compact[c] * 3;
+#pragma unroll
+        for (int j = 0; j < 3; j++) m[j] += vz * vp.vm[j * 4 + 2];
+    }
+}
+
 typedef float v4f __attribute__((ext_vector_type(4)));
 // Streaming 16-byte accesses: data that is touched once per step and is far larger than the caches.
 __device__ __forceinline__ float4 nt_load4(const float *p) {
@@ -1224,6 +1297,25 @@ hipError_t launch_sum_isect_rows(const float *rows, const uint32_t *num_intersec
     hipLaunchKernelGGL(k_sum_isect_rows, dim3(min(ceil_div(chunks, kThreads / kWave), 4096u)), dim3(kThreads), 0, s,
                        reinterpret_cast<const float4 *>(rows), num_intersections, cum_tiles_hit, cap,
                        reinterpret_cast<float4 *>(v_compact), reinterpret_cast<float4 *>(partials));
+    return hipGetLastError();
+}
+
+hipError_t launch_sum_isect_depth(const float *rows, const uint32_t *num_intersections, const uint32_t *cum_tiles_hit,
+                                  uint32_t cap, float *v_compact, float *partials, hipStream_t s) {
+    if (cap == 0) return hipSuccess;
+    const uint32_t chunks = ceil_div(cap, kWave);
+    hipLaunchKernelGGL(k_sum_isect_depth, dim3(min(ceil_div(chunks, kThreads / kWave), 4096u)), dim3(kThreads), 0, s,
+                       rows, num_intersections, cum_tiles_hit, cap, v_compact, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_means_grad(const ViewParams &vp, const uint32_t *num_visible, uint32_t n,
+                                   const uint32_t *global_from_compact, const float *v_compact,
+                                   const DetSumsArgs &dargs, float *v_means, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const DetSums det{dargs.cum_tiles_hit, dargs.num_intersections, dargs.partials, dargs.cap};
+    hipLaunchKernelGGL(k_depth_means_grad, dim3(min(ceil_div(n, kThreads), 2048u)), dim3(kThreads), 0, s, vp,
+                       num_visible, n, global_from_compact, v_compact, det, v_means);
     return hipGetLastError();
 }
 

@@ -112,12 +112,26 @@ struct QuadRec {
 // quadrants of one tile (they gather the same records, so three of the four gathers hit L1/L2).
 // A pixel that has saturated gets a NaN pixel centre: every later `power <= 0` test fails for it, so the
 // per-record path carries no separate "live" predicate.
-template <bool RASTER_U32>
+//
+// DEPTH (brush_render_forward_depth): the accumulated depth D = sum T alpha z of the same entries is carried beside the
+// colour; z (camera-space z of the splat's mean, the depth sort's key, compact order) rides in the record's spare lanes.
+// Everything else, the RGBA image included, is computed exactly as without it.
+// The depth instantiation takes one more argument, a DepthOut; without it the kernel's signature is the plain one.
+struct DepthOut {
+    const float *compact_depth;  // [N] z, compact order
+    float *out_depth;            // [h][w]
+};
+template <typename T>
+__device__ __forceinline__ const T &only(const T &x) { return x; }
+
+template <bool RASTER_U32, typename... Depth>
 __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
     uint32_t w, uint32_t h, uint32_t tbx, uint32_t num_tiles, const uint32_t *__restrict__ gid_from_isect,
     uint32_t *__restrict__ tile_bins, const uint32_t *__restrict__ bin_edges, const float *__restrict__ projected,
     void *__restrict__ out_img, uint32_t *__restrict__ final_index, uint32_t u32_pitch,
-    float4 *__restrict__ zero_rows, const uint32_t *__restrict__ num_visible, uint32_t n_splats) {
+    float4 *__restrict__ zero_rows, const uint32_t *__restrict__ num_visible, uint32_t n_splats, const Depth... depth) {
+    constexpr bool DEPTH = sizeof...(Depth) != 0;
+    static_assert(sizeof...(Depth) <= 1 && !(RASTER_U32 && DEPTH), "depth: one DepthOut, float image");
     __shared__ QuadRec lds_all[kTilesPerBlock][kBatch];
     BRUSH_KTRACE(kTrRasterize, 0);
     if (zero_rows) {
@@ -144,6 +158,7 @@ __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
     uint64_t live = inside_mask;
     uint32_t walked = 0;
     float T = 1.0f, cr = 0.0f, cg = 0.0f, cb_ = 0.0f;
+    float cd = 0.0f;  // DEPTH: accumulated depth
     uint32_t fin = 0;
     uint32_t r0, r1;
     if (bin_edges) {
@@ -164,10 +179,13 @@ __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
         const uint32_t remaining = min(kBatch, r1 - batch_start);
         bool hit = false;
         float rec[9];
+        float z = 0.0f;
         if (lane < remaining) {
-            const float *p = projected + (size_t)gid_from_isect[batch_start + lane] * BRUSH_PROJECTED_FLOATS;
+            const uint32_t cgid = gid_from_isect[batch_start + lane];
+            const float *p = projected + (size_t)cgid * BRUSH_PROJECTED_FLOATS;
 #pragma unroll
             for (int k = 0; k < 9; k++) rec[k] = p[k];
+            if constexpr (DEPTH) z = only(depth...).compact_depth[cgid];
             hit = quad_may_pass(rec[0], rec[1], rec[2], rec[3], rec[4], rec[8], bx, by);
         }
         uint64_t mask = ballot64(hit);
@@ -176,7 +194,7 @@ __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
         if (hit) {
             lds[lane].a = make_float4(rec[0], rec[1], rec[2], rec[3]);
             lds[lane].b = make_float4(rec[4], rec[5], rec[6], rec[7]);
-            lds[lane].c = make_float4(rec[8], 0.f, 0.f, 0.f);
+            lds[lane].c = make_float4(rec[8], z, 0.f, 0.f);
         }
         wave_sync();
         while (mask != 0ull) {
@@ -203,6 +221,7 @@ __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
                     cr = fmaf(b.y, fac, cr);
                     cg = fmaf(b.z, fac, cg);
                     cb_ = fmaf(b.w, fac, cb_);
+                    if constexpr (DEPTH) cd = fmaf(lds[t].c.y, fac, cd);
                     T = next_T;
                     fin = batch_start + t;
                 }
@@ -227,6 +246,7 @@ __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
             const size_t pix = (size_t)px + (size_t)py * w;
             static_cast<float4 *>(out_img)[pix] = make_float4(cr, cg, cb_, al);
             final_index[pix] = fin;
+            if constexpr (DEPTH) only(depth...).out_depth[pix] = cd;
         }
     }
 }
@@ -234,6 +254,8 @@ __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
 // ---- backward -----------------------------------------------------------------------------
 
 constexpr uint32_t kGradComps = 9;  // v_xy(2) v_conic(3) v_rgb(3) v_opac(1)
+constexpr uint32_t kGradCompsDepth = 10;  // ... + v_z (DEPTH), word 9 of the compact row
+constexpr uint32_t kDepthRowWord = 10;    // DET + DEPTH: v_z's word of an intersection row (word 9 is the gid)
 
 // Wave64 sum on the VALU with DPP (no LDS traffic, unlike __shfl_xor = ds_bpermute):
 // inclusive scan inside each row of 16 (row_shr 1/2/4/8), then row_bcast:15 and row_bcast:31
@@ -349,19 +371,36 @@ __device__ __forceinline__ void fill_step(const ZeroFill &zf, FillCursor &c, uin
 // intersection, [9 sums | compact gid | 0 ...], at the position the intersection had before the tile sort
 // (`unsorted_pos`, grouped by splat); intersections it does not walk get zero rows.  k_sum_isect_rows then adds a
 // splat's rows in that fixed order.
-template <uint32_t NQ, bool DET, uint32_t TPB>
+//
+// DEPTH (brush_render_backward_depth): the accumulated depth is a fourth colour channel whose per-splat value is z
+// (compact_depth, staged with the record) and whose pixel gradient is v_depth: z v_D joins the colour term cv of
+// v_alpha, KD keeps its start value (the depth behind a record comes in through cv record by record), and a tenth
+// component g[9] = sum fac v_D = dL/dz is reduced beside the nine others: word 9 of the compact row (default mode),
+// word 10 of the intersection row (DET: word 9 holds the gid).
+// The depth instantiation takes one more argument, a DepthGrad.
+struct DepthGrad {
+    const float *compact_depth;  // [N] z, compact order
+    const float *v_depth;        // [h][w]
+};
+template <uint32_t NQ, bool DET, uint32_t TPB, typename... Depth>
 __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
     uint32_t w, uint32_t h, uint32_t tbx, uint32_t num_tiles, const uint32_t *__restrict__ gid_from_isect,
     const uint32_t *__restrict__ tile_bins, const float *__restrict__ projected,
     const uint32_t *__restrict__ final_index, const float *__restrict__ out_img,
     const float *__restrict__ v_out, float *__restrict__ v_compact, const uint32_t *__restrict__ unsorted_pos,
-    float *__restrict__ rows, const ZeroFill zf) {
+    float *__restrict__ rows, const ZeroFill zf, const Depth... depth) {
     static_assert(!DET || NQ == 4, "deterministic mode: one wave per tile");
+    constexpr bool DEPTH = sizeof...(Depth) != 0;
+    static_assert(sizeof...(Depth) <= 1, "one DepthGrad");
+    constexpr uint32_t NC = DEPTH ? kGradCompsDepth : kGradComps;
+    constexpr uint32_t kRows = kStageRecs * NC;
+    static_assert(kRows <= 32, "one row per lane pair");
     __shared__ uint32_t lds_pos_all[DET ? TPB : 1][kBatch];
     __shared__ BwdRecs lds_all[TPB];
     __shared__ uint32_t lds_gid_all[TPB][kBatch];
-    __shared__ float acc_all[DET ? TPB : 1][kBatch][12];  // DET: 9 used; 48-byte rows keep b128 stores aligned
-    __shared__ float stage_all[DET ? 1 : TPB][kStageRows * kRowWords];
+    __shared__ float acc_all[DET ? TPB : 1][kBatch][12];  // DET: 9 used (10 with DEPTH); 48-byte rows keep b128 stores aligned
+    __shared__ float stage_all[DET ? 1 : TPB][kRows * kRowWords];
+    __shared__ float lds_z_all[DEPTH ? TPB : 1][kBatch];
     constexpr uint32_t kWavesPerTile = 4u / NQ;
     BRUSH_KTRACE(kTrRasterizeBwd, 0);
 
@@ -403,6 +442,7 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
     // Per-quadrant pixel state (see k_rasterize_backward for D and K); pixels outside the image get
     // fin = -1 and never contribute.
     float pcx[NQ], pcy[NQ], T[NQ], KD[NQ], vor[NQ], vog[NQ], vob[NQ];  // KD = K - D of k_rasterize_backward
+    float vod[NQ];  // DEPTH: v_depth
     int32_t fin[NQ];
     int32_t max_fin = -1;
 #pragma unroll
@@ -414,11 +454,13 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
         float T_final = 1.0f;
         float4 vo = make_float4(0.f, 0.f, 0.f, 0.f);
         fin[s] = -1;
+        if constexpr (DEPTH) vod[s] = 0.0f;
         if (px < w && py < h) {
             const size_t pix = (size_t)px + (size_t)py * w;
             T_final = 1.0f - out_img[pix * 4 + 3];  // rasterize_backwards.wgsl:163
             fin[s] = (int32_t)final_index[pix];
             vo = reinterpret_cast<const float4 *>(v_out)[pix];
+            if constexpr (DEPTH) vod[s] = only(depth...).v_depth[pix];
         }
         T[s] = T_final, KD[s] = T_final * vo.w;
         vor[s] = vo.x, vog[s] = vo.y, vob[s] = vo.z;
@@ -446,12 +488,14 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
 #pragma unroll
         for (uint32_t s = 0; s < NQ; s++) hitq[s] = false;
         float rec[9];
+        float zrec = 0.0f;
         uint32_t cg_id = 0;
         if (lane < remaining) {
             cg_id = gid_from_isect[batch_end - 1u - lane];
             const float *p = projected + (size_t)cg_id * BRUSH_PROJECTED_FLOATS;
 #pragma unroll
             for (int k = 0; k < 9; k++) rec[k] = p[k];
+            if constexpr (DEPTH) zrec = only(depth...).compact_depth[cg_id];
 #pragma unroll
             for (uint32_t s = 0; s < NQ; s++) {
                 const uint32_t qi = sub * NQ + s;
@@ -485,6 +529,7 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
             lds.a[lane] = make_float4(rec[0], rec[1], rec[2], rec[3]);
             lds.b[lane] = make_float4(rec[4], rec[5], rec[6], rec[7]);
             lds.opac[lane] = rec[8];
+            if constexpr (DEPTH) lds_z_all[wv][lane] = zrec;
         }
         if (DET) {
             float4 *row = reinterpret_cast<float4 *>(&acc[lane][0]);
@@ -502,7 +547,7 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
         auto reduce_stage = [&](const uint32_t cnt) {
             const uint32_t row = lane & 31u, half = lane >> 5;
             float sum = 0.0f;
-            if (row < cnt * kGradComps) {
+            if (row < cnt * NC) {
                 const float4 *src = reinterpret_cast<const float4 *>(stage + row * kRowWords + half * 32u);
                 float4 v[8];
 #pragma unroll
@@ -513,9 +558,9 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
                 sum = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
             }
             sum = fold_swap32(sum, sum);  // every lane: lower + upper half of its row
-            if (lane < cnt * kGradComps) {
-                const uint32_t slot = (row * 57u) >> 9;  // row / 9 for row < 32
-                const uint32_t k = row - slot * kGradComps;
+            if (lane < cnt * NC) {
+                const uint32_t slot = DEPTH ? row / NC : (row * 57u) >> 9;  // row / 9 for row < 32
+                const uint32_t k = row - slot * NC;
                 const uint32_t t = (uint32_t)(staged_t >> (6u * slot)) & 63u;
                 // rasterize_backwards.wgsl:256-263: v_xy = -opac (sum vva gx, sum vva gy), v_conic = -opac (S2 / 2, S3,
                 // S4 / 2), v_rgb, v_opac = S8
@@ -537,7 +582,7 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
             }
             // Zeros the compiler cannot see through: every quadrant then accumulates in place under its
             // exec mask, instead of each path materialising its own set of nine zero registers.
-            float g[kGradComps];
+            float g[NC];
             {
                 typedef float f2v __attribute__((ext_vector_type(2)));
                 f2v z01, z23, z45, z67;
@@ -548,6 +593,7 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
                 g[0] = z01.x, g[1] = z01.y, g[2] = z23.x, g[3] = z23.y;
                 g[4] = z45.x, g[5] = z45.y, g[6] = z67.x, g[7] = z67.y;
                 asm volatile("v_mov_b32 %0, 0" : "=v"(g[8]));
+                if constexpr (DEPTH) asm volatile("v_mov_b32 %0, 0" : "=v"(g[NC - 1]));
             }
             bool contributed = false;
 #pragma unroll
@@ -568,7 +614,8 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
                     const float ra = __builtin_amdgcn_rcpf(om);
                     const float Tn = T[s] * ra;
                     const float fac = alpha * Tn;
-                    const float cv = fmaf(b.w, vob[s], fmaf(b.z, vog[s], b.y * vor[s]));
+                    float cv = fmaf(b.w, vob[s], fmaf(b.z, vog[s], b.y * vor[s]));
+                    if constexpr (DEPTH) cv = fmaf(lds_z_all[wv][t], vod[s], cv);  // the fourth channel
                     // v_alpha = (c*T - buffer*ra) . v_rgb + T_final*ra*v_a = T (c . v_rgb) + ra (K - D)
                     const float v_alpha = fmaf(Tn, cv, ra * KD[s]);
                     T[s] = Tn;
@@ -593,16 +640,17 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
                     g[6] = fmaf(fac, vog[s], g[6]);
                     g[7] = fmaf(fac, vob[s], g[7]);
                     g[8] += vva;
+                    if constexpr (DEPTH) g[NC - 1] = fmaf(fac, vod[s], g[NC - 1]);
                     contributed = true;
                 }
             }
             if (ballot64(contributed) != 0ull) {  // wave-uniform: all 64 lanes take part in the reduction
                 if (dev_skip_reduce<DET>(g, v_compact, lane)) return;  // never in the product build
                 if constexpr (!DET) {
-                    // park the lane partials as 9 rows of the stage: plain LDS stores, no cross-lane VALU work
-                    float *dst = stage + staged * (kGradComps * kRowWords) + lane;
+                    // park the lane partials as 9 (10) rows of the stage: plain LDS stores, no cross-lane VALU work
+                    float *dst = stage + staged * (NC * kRowWords) + lane;
 #pragma unroll
-                    for (uint32_t k = 0; k < kGradComps; k++) dst[k * kRowWords] = g[k];
+                    for (uint32_t k = 0; k < NC; k++) dst[k * kRowWords] = g[k];
                     staged_t |= (uint64_t)t << (6u * staged);
                     if (++staged == kStageRecs) {
                         reduce_stage(kStageRecs);
@@ -615,12 +663,17 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
                 const float w0 = row_sum_lane15(fold_swap16(u0, u1));
                 const float w1 = row_sum_lane15(fold_swap16(u2, u3));
                 const float s8 = wave_sum_lane63(g[8]);
+                float s9 = 0.0f;
+                if constexpr (DEPTH) s9 = wave_sum_lane63(g[NC - 1]);
                 if ((lane & 15u) == 15u) {
                     const uint32_t r = lane >> 4;
                     const uint32_t i0 = ((r & 1u) << 1) | (r >> 1);
                     acc[t][i0] = w0;
                     acc[t][4 + i0] = w1;
-                    if (lane == 63) acc[t][8] = s8;
+                    if (lane == 63) {
+                        acc[t][8] = s8;
+                        if constexpr (DEPTH) acc[t][9] = s9;
+                    }
                 }
             }
         };
@@ -668,6 +721,8 @@ __global__ __launch_bounds__(TPB * kWave) void k_rasterize_backward_quad(
                 if ((flush_mask >> t) & 1ull) v = finish(t, k);
             } else if (k == kGradComps) {
                 v = __uint_as_float(lds_gid[t]);
+            } else if (DEPTH && k == kDepthRowWord) {
+                if ((flush_mask >> t) & 1ull) v = acc[t][9];
             }
             rows[(size_t)lds_pos[t] * kCompactStride + k] = v;
         }
@@ -708,12 +763,17 @@ hipError_t launch_rasterize(uint32_t w, uint32_t h, uint32_t tbx, uint32_t tby,
                             const uint32_t *compact_gid_from_isect, uint32_t *tile_bins, const uint32_t *bin_edges,
                             const float *projected, int raster_u32, uint32_t u32_pitch, void *out_img,
                             uint32_t *final_index, float *zero_rows, const uint32_t *num_visible, uint32_t n,
-                            hipStream_t s) {
+                            hipStream_t s, const float *compact_depth, float *out_depth) {
     const uint32_t tiles = tbx * tby;
     if (tiles == 0) return hipSuccess;
     // one workgroup (4 quadrant waves) per tile
     const dim3 grid(ceil_div(tiles, 8u) * 8u), block(kRasterThreads);
-    if (raster_u32)
+    if (out_depth) {
+        if (raster_u32 || !compact_depth) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_rasterize_quad<false, DepthOut>), grid, block, 0, s, w, h, tbx, tiles,
+                           compact_gid_from_isect, tile_bins, bin_edges, projected, out_img, final_index, u32_pitch,
+                           reinterpret_cast<float4 *>(zero_rows), num_visible, n, DepthOut{compact_depth, out_depth});
+    } else if (raster_u32)
         hipLaunchKernelGGL(k_rasterize_quad<true>, grid, block, 0, s, w, h, tbx, tiles, compact_gid_from_isect,
                            tile_bins, bin_edges, projected, out_img, final_index, u32_pitch,
                            reinterpret_cast<float4 *>(zero_rows), num_visible, n);
@@ -738,7 +798,8 @@ hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint3
                                      const uint32_t *compact_gid_from_isect, const uint32_t *tile_bins,
                                      const float *projected, const uint32_t *final_index,
                                      const float *out_img, const float *v_out, float *v_compact,
-                                     const uint32_t *unsorted_pos, float *rows, const ZeroFill &fill, hipStream_t s) {
+                                     const uint32_t *unsorted_pos, float *rows, const ZeroFill &fill, hipStream_t s,
+                                     const float *compact_depth, const float *v_depth) {
     const uint32_t tiles = tbx * tby;
     if (tiles == 0) return hipSuccess;
     // Waves per SIMD.  The kernel is bound by VALU issue once a SIMD holds 3+ waves, every wave lives for its whole
@@ -778,10 +839,34 @@ hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint3
                        dim3(ceil_div(ceil_div(units, kTilesPerBlock), 8u) * 8u), dim3(kRasterThreads), lds_pad, s, w, \
                        h, tbx, tiles, compact_gid_from_isect, tile_bins, projected, final_index, out_img, v_out,      \
                        v_compact, UNSORTED, ROWS, fill)
+#define BRUSH_RASTER_BWD_DEPTH(NQ, DET, UNSORTED, ROWS)                                                               \
+    hipLaunchKernelGGL((k_rasterize_backward_quad<NQ, DET, kTilesPerBlock, DepthGrad>),                               \
+                       dim3(ceil_div(ceil_div(units, kTilesPerBlock), 8u) * 8u), dim3(kRasterThreads), lds_pad, s, w, \
+                       h, tbx, tiles, compact_gid_from_isect, tile_bins, projected, final_index, out_img, v_out,      \
+                       v_compact, UNSORTED, ROWS, fill, DepthGrad{compact_depth, v_depth})
     // static LDS per workgroup as the compiler lays it out (unused arrays of the other mode are dropped); registers:
     // 110-122 VGPRs -> 4 waves per SIMD
     constexpr uint32_t kStaticLdsDet = kTilesPerBlock * (sizeof(BwdRecs) + kBatch * (4u + 4u + 48u));
     constexpr uint32_t kStaticLdsDefault = kTilesPerBlock * (sizeof(BwdRecs) + kBatch * 4u + kStageRows * kRowWords * 4u);
+    if (v_depth) {  // depth as a fourth channel: one more staged float per record, 10-component stage rows
+        if (!compact_depth) return hipErrorInvalidValue;
+        constexpr uint32_t kZ = kTilesPerBlock * kBatch * 4u;
+        if (rows) {
+            const uint32_t units = tiles;
+            const uint32_t lds_pad = lds_pad_for(units, kStaticLdsDet + kZ, 4u);
+            BRUSH_RASTER_BWD_DEPTH(4, true, unsorted_pos, rows);
+            return hipGetLastError();
+        }
+        constexpr uint32_t kStaticLdsDepth =
+            kTilesPerBlock * (sizeof(BwdRecs) + kBatch * 4u + kStageRecs * kGradCompsDepth * kRowWords * 4u) + kZ;
+        const uint32_t nq = backward_quadrants_per_wave(tiles);
+        const uint32_t units = tiles * (4u / nq);
+        const uint32_t lds_pad = lds_pad_for(units, kStaticLdsDepth, 4u);
+        if (nq == 4) BRUSH_RASTER_BWD_DEPTH(4, false, nullptr, nullptr);
+        else if (nq == 2) BRUSH_RASTER_BWD_DEPTH(2, false, nullptr, nullptr);
+        else BRUSH_RASTER_BWD_DEPTH(1, false, nullptr, nullptr);
+        return hipGetLastError();
+    }
     if (rows) {  // deterministic mode: one wave per tile, one stored row per intersection
         const uint32_t units = tiles;
         const uint32_t lds_pad = lds_pad_for(units, kStaticLdsDet, 4u);
@@ -795,6 +880,7 @@ hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint3
     else if (nq == 2) BRUSH_RASTER_BWD(2, false, nullptr, nullptr);
     else BRUSH_RASTER_BWD(1, false, nullptr, nullptr);
 #undef BRUSH_RASTER_BWD
+#undef BRUSH_RASTER_BWD_DEPTH
     return hipGetLastError();
 }
 

@@ -24,8 +24,8 @@ __device__ __forceinline__ void dev_flush(float *dst, float val) {
 #endif
 }
 
-template <bool DET>
-__device__ __forceinline__ bool dev_skip_reduce(const float (&g)[9], float *v_compact, uint32_t lane) {
+template <bool DET, uint32_t N>
+__device__ __forceinline__ bool dev_skip_reduce(const float (&g)[N], float *v_compact, uint32_t lane) {
 #ifdef BRUSH_ELIM_NO_REDUCE
     if (!DET) {
         if (g[0] + g[1] + g[2] + g[3] + g[4] + g[5] + g[6] + g[7] + g[8] == 12345.678f) v_compact[lane] = g[0];

@@ -206,9 +206,11 @@ extern "C" int brush_bwd_workspace_size(uint32_t n, uint32_t w, uint32_t h, uint
 static int render_forward_impl(const BrushUniforms *h_uniforms, const float *means, const float *log_scales,
                                const float *quats, const float *sh_coeffs, const float *raw_opacity, uint32_t n,
                                int raster_u32, uint32_t u32_pitch, void *out_img, const BrushAux *h_aux,
-                               void *workspace, size_t workspace_bytes, brush_stream_t stream) {
+                               void *workspace, size_t workspace_bytes, brush_stream_t stream,
+                               float *out_depth = nullptr, float *compact_depth = nullptr) {
     if (!uniforms_ok(h_uniforms) || !aux_ok(h_aux, !raster_u32) || !out_img || !workspace)
         return BRUSH_ERR_INVALID_ARG;
+    if ((out_depth != nullptr) != (compact_depth != nullptr) || (out_depth && raster_u32)) return BRUSH_ERR_INVALID_ARG;
     if (n > 0 && (!means || !log_scales || !quats || !sh_coeffs || !raw_opacity)) return BRUSH_ERR_INVALID_ARG;
     const BrushAux &aux = *h_aux;
     const uint32_t cap = aux.max_intersects;
@@ -236,9 +238,12 @@ static int render_forward_impl(const BrushUniforms *h_uniforms, const float *mea
                                         ws.bin_edges, ws.walk, lazy, s));
     mark_fwd(s, 1 + BRUSH_STAGE_PROJECT_CULL);
     if (stop_behind(BRUSH_STAGE_PROJECT_CULL)) return BRUSH_OK;
-    // DepthSort: keys = f32 depth bits, all 32 bits (render.rs:151-156)
-    BRUSH_HIP_CHECK(sort_launch(ws.pre_keys, ws.pre_gids, ws.sorted_keys, aux.global_from_compact_gid,
-                                aux.num_visible, n, 32, ws.sort_ws, s));
+    // DepthSort: keys = f32 depth bits, all 32 bits (render.rs:151-156).  With a depth output the sorted keys go to
+    // the caller's compact_depth: camera-space z of every visible splat in compact order, read by the compositing
+    // kernels of the forward and of the backward.
+    BRUSH_HIP_CHECK(sort_launch(ws.pre_keys, ws.pre_gids,
+                                compact_depth ? reinterpret_cast<uint32_t *>(compact_depth) : ws.sorted_keys,
+                                aux.global_from_compact_gid, aux.num_visible, n, 32, ws.sort_ws, s));
     mark_fwd(s, 1 + BRUSH_STAGE_DEPTH_SORT);
     if (stop_behind(BRUSH_STAGE_DEPTH_SORT)) return BRUSH_OK;
     // ProjectVisible (render.rs:161-184)
@@ -285,7 +290,7 @@ static int render_forward_impl(const BrushUniforms *h_uniforms, const float *mea
     BRUSH_HIP_CHECK(launch_rasterize(w, h, tbx, tby, aux.compact_gid_from_isect, aux.tile_bins,
                                      det ? nullptr : ws.bin_edges, aux.projected_splats, raster_u32,
                                      u32_pitch ? u32_pitch : w, out_img, aux.final_index,
-                                     det ? nullptr : aux.bwd_accum, aux.num_visible, n, s));
+                                     det ? nullptr : aux.bwd_accum, aux.num_visible, n, s, compact_depth, out_depth));
     mark_fwd(s, 1 + BRUSH_STAGE_RASTERIZE);
     return BRUSH_OK;
 }
@@ -296,6 +301,16 @@ extern "C" int brush_render_forward(const BrushUniforms *h_uniforms, const float
                                     void *workspace, size_t workspace_bytes, brush_stream_t stream) {
     return render_forward_impl(h_uniforms, means, log_scales, quats, sh_coeffs, raw_opacity, n, raster_u32, 0, out_img,
                                h_aux, workspace, workspace_bytes, stream);
+}
+
+extern "C" int brush_render_forward_depth(const BrushUniforms *h_uniforms, const float *means,
+                                          const float *log_scales, const float *quats, const float *sh_coeffs,
+                                          const float *raw_opacity, uint32_t n, float *out_img, float *out_depth,
+                                          float *compact_depth, const BrushAux *h_aux, void *workspace,
+                                          size_t workspace_bytes, brush_stream_t stream) {
+    if (!out_depth || !compact_depth) return BRUSH_ERR_INVALID_ARG;
+    return render_forward_impl(h_uniforms, means, log_scales, quats, sh_coeffs, raw_opacity, n, 0, 0, out_img, h_aux,
+                               workspace, workspace_bytes, stream, out_depth, compact_depth);
 }
 
 extern "C" int brush_render_forward_rgba8(const BrushUniforms *h_uniforms, const float *means,
@@ -316,16 +331,19 @@ extern "C" uint32_t brush_rgba8_row_pitch(uint32_t width) { return (width + 63u)
 // `fill` (may be inactive): zero-fill the compositing kernel carries in passing; *filled says whether it ran.
 static int composite_backward(const BrushUniforms &u, const BrushAux &aux, const float *out_img, const float *v_out,
                               uint32_t n, const BwdWs &ws, DetSumsArgs *det, const ZeroFill &fill, bool *filled,
-                              hipStream_t s) {
+                              hipStream_t s, const float *compact_depth = nullptr, const float *v_depth = nullptr) {
     const uint32_t w = u.img_size[0], h = u.img_size[1], tbx = u.tile_bounds[0], tby = u.tile_bounds[1];
     *filled = fill.active() && tbx * tby != 0u;  // (no tiles: no launch)
     if (ws.rows) {
         // no zero-fill stage in this mode: no launch, no event
         BRUSH_HIP_CHECK(launch_rasterize_backward(w, h, tbx, tby, aux.compact_gid_from_isect, aux.tile_bins,
                                                   aux.projected_splats, aux.final_index, out_img, v_out, ws.v_compact,
-                                                  aux.isect_unsorted_pos, ws.rows, fill, s));
+                                                  aux.isect_unsorted_pos, ws.rows, fill, s, compact_depth, v_depth));
         BRUSH_HIP_CHECK(launch_sum_isect_rows(ws.rows, aux.num_intersections, aux.cum_tiles_hit, aux.max_intersects,
                                               ws.v_compact, ws.partials, s));
+        if (v_depth)  // after the rows' sums: those write word 9 of their rows as 0
+            BRUSH_HIP_CHECK(launch_sum_isect_depth(ws.rows, aux.num_intersections, aux.cum_tiles_hit,
+                                                   aux.max_intersects, ws.v_compact, ws.partials, s));
         mark_bwd(s, 2);
         det->cum_tiles_hit = aux.cum_tiles_hit;
         det->num_intersections = aux.num_intersections;
@@ -342,7 +360,7 @@ static int composite_backward(const BrushUniforms &u, const BrushAux &aux, const
     if (stop_behind(BRUSH_STAGE_BWD_ZERO)) return BRUSH_OK;
     BRUSH_HIP_CHECK(launch_rasterize_backward(w, h, tbx, tby, aux.compact_gid_from_isect, aux.tile_bins,
                                               aux.projected_splats, aux.final_index, out_img, v_out, ws.v_compact,
-                                              nullptr, nullptr, fill, s));
+                                              nullptr, nullptr, fill, s, compact_depth, v_depth));
     mark_bwd(s, 2);
     return BRUSH_OK;
 }
@@ -351,9 +369,11 @@ static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux 
                                 const float *log_scales, const float *quats, const float *raw_opacity, uint32_t n,
                                 const float *out_img, const float *v_out, float *v_means, float *v_xy,
                                 float *v_scales, float *v_quats, float *v_sh, float *v_opac, const AdamFuse *adam,
-                                void *workspace, size_t workspace_bytes, brush_stream_t stream) {
+                                void *workspace, size_t workspace_bytes, brush_stream_t stream,
+                                const float *compact_depth = nullptr, const float *v_depth = nullptr) {
     if (!uniforms_ok(h_uniforms) || !aux_ok(h_aux, true) || !out_img || !v_out || !workspace)
         return BRUSH_ERR_INVALID_ARG;
+    if ((compact_depth != nullptr) != (v_depth != nullptr) || (v_depth && adam)) return BRUSH_ERR_INVALID_ARG;
     if (n > 0 && (!means || !log_scales || !quats || !raw_opacity || !v_xy)) return BRUSH_ERR_INVALID_ARG;
     if (n > 0 && !adam && (!v_means || !v_scales || !v_quats || !v_sh || !v_opac)) return BRUSH_ERR_INVALID_ARG;
     const BrushAux &aux = *h_aux;
@@ -382,12 +402,17 @@ static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux 
     mark_bwd(s, 0);
     DetSumsArgs det;
     bool filled = false;
-    if (const int rc = composite_backward(u, aux, out_img, v_out, n, ws, &det, fill, &filled, s)) return rc;
+    if (const int rc = composite_backward(u, aux, out_img, v_out, n, ws, &det, fill, &filled, s, compact_depth, v_depth))
+        return rc;
     if (stop_behind(BRUSH_STAGE_BWD_ZERO) || stop_behind(BRUSH_STAGE_RASTERIZE_BWD)) return BRUSH_OK;
     // GatherGrads + ProjectBackwards fused, dense outputs written once (render.rs:534-594)
     BRUSH_HIP_CHECK(launch_project_backward(vp, means, log_scales, quats, raw_opacity, aux.compact_from_global_gid,
                                             ws.v_compact, v_means, v_xy, v_scales, v_quats, v_sh, v_opac, adam, det,
                                             filled, s));
+    // depth: z = viewmat row 2 . [mean, 1] carries v_z into v_means
+    if (v_depth)
+        BRUSH_HIP_CHECK(launch_depth_means_grad(vp, aux.num_visible, n, aux.global_from_compact_gid, ws.v_compact, det,
+                                                v_means, s));
     mark_bwd(s, 3);
     return BRUSH_OK;
 }
@@ -445,6 +470,18 @@ extern "C" int brush_render_backward(const BrushUniforms *h_uniforms, const Brus
                                      void *workspace, size_t workspace_bytes, brush_stream_t stream) {
     return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
                                 v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int brush_render_backward_depth(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *means,
+                                           const float *log_scales, const float *quats, const float *raw_opacity,
+                                           uint32_t n, const float *out_img, const float *v_out,
+                                           const float *compact_depth, const float *v_depth, float *v_means,
+                                           float *v_xy, float *v_scales, float *v_quats, float *v_sh, float *v_opac,
+                                           void *workspace, size_t workspace_bytes, brush_stream_t stream) {
+    if (!compact_depth || !v_depth) return BRUSH_ERR_INVALID_ARG;
+    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
+                                v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream,
+                                compact_depth, v_depth);
 }
 
 extern "C" int brush_render_backward_adam(const BrushUniforms *h_uniforms, const BrushAux *h_aux,

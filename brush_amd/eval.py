@@ -128,6 +128,27 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
                       for k, (i, (r, a)) in enumerate(zip(idx, rendered))])
 
 
+def write_depth_maps(splats, views, out_dir: str):
+    """For each view: <stem>_depth.npy, the accumulated depth D = sum T alpha z (Splats.render_depth), and
+    <stem>_depth_norm.npy, D / max(alpha, 1e-6) with 0 where alpha is 0; both f32 [h,w].  Returns the written paths."""
+    import os
+
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    with torch.no_grad():
+        for v in views:
+            h, w = int(v.image.shape[0]), int(v.image.shape[1])
+            img, depth, _ = splats.render_depth(v.camera, (w, h))
+            alpha = img[..., 3]
+            norm = torch.where(alpha > 0, depth / torch.clamp(alpha, min=1e-6), torch.zeros_like(depth))
+            stem = os.path.splitext(os.path.basename(v.name))[0]
+            for suffix, t in (("_depth.npy", depth), ("_depth_norm.npy", norm)):
+                path = os.path.join(out_dir, stem + suffix)
+                np.save(path, t.cpu().numpy().astype(np.float32))
+                paths.append(path)
+    return paths
+
+
 # ---------------------------------------------------------------------------- command line
 def detect_format(dataset: str) -> str:
     """'nerf' when the directory / zip holds a transforms_*.json, else 'colmap'."""
@@ -169,6 +190,9 @@ def main(argv=None) -> int:
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--window", type=int, default=11)
     p.add_argument("--json", default=None, help="also write the results to this file")
+    p.add_argument("--depth-dir", default=None,
+                   help="also write every eval view's accumulated depth D (<view stem>_depth.npy, f32 [h,w]) and "
+                        "D / alpha (<view stem>_depth_norm.npy, 0 where alpha is 0) to this directory")
     args = p.parse_args(argv)
 
     data = _load_dataset(args)  # before any GPU work
@@ -187,6 +211,8 @@ def main(argv=None) -> int:
     for s in stats.samples:
         print(f"{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
     print(f"mean ({len(stats.samples)} views)\tpsnr {stats.mean_psnr():.4f}\tssim {stats.mean_ssim():.6f}")
+    if args.depth_dir:
+        write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir)
     if args.json:
         res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "window": args.window,
                "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in stats.samples],

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 
 from .camera import Camera
-from .render import render_splats
+from .render import render_splats, render_splats_depth
 
 
 class Splats(torch.nn.Module):
@@ -115,3 +115,11 @@ class Splats(torch.nn.Module):
         norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
         return render_splats(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
                              self.sh_coeffs, self.raw_opacity, render_u32_buffer, max_intersects)
+
+    def render_depth(self, camera: Camera, img_size, max_intersects=None):
+        """render() with the accumulated depth (render.render_splats_depth): (img [h,w,4], depth [h,w], aux)."""
+        self.sync()
+        rot = self.rotation
+        norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
+        return render_splats_depth(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
+                                   self.sh_coeffs, self.raw_opacity, max_intersects)

@@ -164,8 +164,10 @@ def _check_inputs(means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity):
 
 def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, render_u32: bool,
                   max_intersects: Optional[int], row_pitch: Optional[int] = None,
-                  deterministic: Optional[bool] = None, expect_backward: Optional[bool] = None, lazy_sh=None):
-    """expect_backward (default: a float image in default mode): allocate the backward's workspace now and let the
+                  deterministic: Optional[bool] = None, expect_backward: Optional[bool] = None, lazy_sh=None,
+                  depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """depth: (out_depth [h,w], compact_depth [N]) f32 buffers: render with brush_render_forward_depth (float image).
+    expect_backward (default: a float image in default mode): allocate the backward's workspace now and let the
     forward zero its accumulator rows, so that the backward of this render needs no zero-fill launch.
     lazy_sh: a _lib.BrushLazySh (SplatTrainer's deferred Adam of the SH block): colours come from the coefficients
     with their pending optimizer steps replayed; `sh_coeffs` is not written."""
@@ -220,7 +222,14 @@ def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, ra
     s = aux._as_struct()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        if row_pitch is not None:
+        if depth is not None:
+            assert not render_u32 and row_pitch is None
+            _lib.check(l.brush_render_forward_depth(C.byref(u), means.data_ptr(), log_scales.data_ptr(),
+                                                    quats.data_ptr(), sh_coeffs.data_ptr(), raw_opacity.data_ptr(), n,
+                                                    out.data_ptr(), depth[0].data_ptr(), depth[1].data_ptr(),
+                                                    C.byref(s), ws.data_ptr(), nbytes.value, stream),
+                       "brush_render_forward_depth")
+        elif row_pitch is not None:
             _lib.check(l.brush_render_forward_rgba8(C.byref(u), means.data_ptr(), log_scales.data_ptr(),
                                                     quats.data_ptr(), sh_coeffs.data_ptr(), raw_opacity.data_ptr(), n,
                                                     out.data_ptr(), int(row_pitch), C.byref(s), ws.data_ptr(),
@@ -249,7 +258,9 @@ def grad_block_layout(n: int, ncoef: int):
 
 
 def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, ncoef, out_img, v_out,
-                   block: Optional[torch.Tensor] = None):
+                   block: Optional[torch.Tensor] = None,
+                   depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """depth: (compact_depth [N], v_depth [h,w]) of a depth render: brush_render_backward_depth."""
     l = _lib.lib()
     n = means.shape[0]
     dev = means.device
@@ -274,12 +285,22 @@ def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, nco
     ws, s = aux.backward_workspace(nbytes.value, dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(l.brush_render_backward(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
-                                           quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
-                                           v_out.data_ptr(), g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
-                                           g["v_scales"].data_ptr(), g["v_quats"].data_ptr(), g["v_sh"].data_ptr(),
-                                           g["v_opac"].data_ptr(), ws.data_ptr(), nbytes.value, stream),
-                   "brush_render_backward")
+        if depth is not None:
+            compact_depth, v_depth = depth[0], depth[1].contiguous()
+            _lib.check(l.brush_render_backward_depth(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
+                                                     quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
+                                                     v_out.data_ptr(), compact_depth.data_ptr(), v_depth.data_ptr(),
+                                                     g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
+                                                     g["v_scales"].data_ptr(), g["v_quats"].data_ptr(),
+                                                     g["v_sh"].data_ptr(), g["v_opac"].data_ptr(), ws.data_ptr(),
+                                                     nbytes.value, stream), "brush_render_backward_depth")
+        else:
+            _lib.check(l.brush_render_backward(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
+                                               quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
+                                               v_out.data_ptr(), g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
+                                               g["v_scales"].data_ptr(), g["v_quats"].data_ptr(), g["v_sh"].data_ptr(),
+                                               g["v_opac"].data_ptr(), ws.data_ptr(), nbytes.value, stream),
+                       "brush_render_backward")
     return g, block
 
 
@@ -332,6 +353,62 @@ def render_splats(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Opt
     holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic}
     out = _RenderSplatsFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder)
     return out, holder["aux"]
+
+
+def _depth_buffers(n: int, img_size, device):
+    w, h = int(img_size[0]), int(img_size[1])
+    return _empty((h, w), torch.float32, device), _empty((max(n, 1),), torch.float32, device)
+
+
+class _RenderSplatsDepthFn(torch.autograd.Function):
+    """render_splats with the accumulated depth as a second output; same six parents."""
+
+    @staticmethod
+    def forward(ctx, means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder):
+        depth = _depth_buffers(means.shape[0], holder["img_size"], means.device)
+        out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
+                                    raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
+                                    depth=depth)
+        holder["aux"] = aux
+        ctx.u, ctx.aux, ctx.ncoef = u, aux, sh_coeffs.shape[1]
+        ctx.save_for_backward(means, log_scales, quats, raw_opacity, out, depth[1])
+        return out, depth[0]
+
+    @staticmethod
+    def backward(ctx, v_output, v_depth):
+        means, log_scales, quats, raw_opacity, out, compact_depth = ctx.saved_tensors
+        # a zero (or absent) gradient on one output is passed as zeros
+        v_output = torch.zeros_like(out) if v_output is None else v_output.to(torch.float32)
+        v_depth = torch.zeros(out.shape[:2], dtype=torch.float32, device=out.device) if v_depth is None \
+            else v_depth.to(torch.float32)
+        g, _ = _backward_impl(ctx.u, ctx.aux, means, log_scales, quats, raw_opacity, ctx.ncoef, out, v_output,
+                              depth=(compact_depth, v_depth))
+        return g["v_means"], g["v_xy"], g["v_scales"], g["v_quats"], g["v_sh"], g["v_opac"], None
+
+
+def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Optional[torch.Tensor],
+                        log_scales: torch.Tensor, quats: torch.Tensor, sh_coeffs: torch.Tensor,
+                        raw_opacity: torch.Tensor, max_intersects: Optional[int] = None,
+                        deterministic: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor, RenderAux]:
+    """render_splats (float image) plus the accumulated depth D(p) = sum_i T_i alpha_i z_i over exactly the entries
+    the colour composites (z_i: camera-space z of splat i's mean).  Returns (img [h,w,4], depth [h,w], aux); the image
+    and aux are bitwise those of render_splats.  D is not normalised: D / img[..., 3] is the expected depth of the
+    covered part.  Differentiable for gradients on img, on depth or both, into the same six parents."""
+    _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
+    tracked = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity))
+    if not tracked:
+        with torch.no_grad():
+            depth = _depth_buffers(means.shape[0], img_size, means.device)
+            out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, False,
+                                        max_intersects, deterministic=deterministic, expect_backward=False,
+                                        depth=depth)
+        return out, depth[0], aux
+    if xy_grad_dummy is None:
+        xy_grad_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
+    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic}
+    out, depth = _RenderSplatsDepthFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder)
+    return out, depth, holder["aux"]
 
 
 def rgba8_row_pitch(width: int) -> int:

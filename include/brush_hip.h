@@ -194,6 +194,21 @@ int brush_render_forward_rgba8(const BrushUniforms *uniforms, const float *means
                                uint32_t n, uint32_t *out_img, uint32_t row_pitch_pixels, const BrushAux *aux,
                                void *workspace, size_t workspace_bytes, brush_stream_t stream);
 
+/* Accumulated depth beside the colour image (build extension; the reference has no depth output).  For a pixel p
+ *     D(p) = sum_i T_i alpha_i z_i
+ * over exactly the entries the colour forward composites into p: the same alpha (0.999 clamp), the same
+ * alpha >= 1/255 test and T <= 1e-4 stop, in the same order.  z_i is the camera-space z of splat i's mean
+ * (p_view.z, project_forward.wgsl:67), the key of the depth sort.  D is NOT normalised: the alpha-normalised
+ * expected depth is D / alpha with alpha = out_img[..., 3].
+ * out_img, final_index, tile_bins, the counts and every other aux array come out bitwise identical to
+ * brush_render_forward(raster_u32 = 0) with the same aux flags; the workspace is brush_fwd_workspace_size's.
+ * out_depth: [h,w] f32.  compact_depth: [N] f32, written with z of the visible splats in compact (depth) order;
+ * keep it for brush_render_backward_depth. */
+int brush_render_forward_depth(const BrushUniforms *h_uniforms, const float *means, const float *log_scales,
+                               const float *quats, const float *sh_coeffs, const float *raw_opacity, uint32_t n,
+                               float *out_img, float *out_depth, float *compact_depth, const BrushAux *h_aux,
+                               void *workspace, size_t workspace_bytes, brush_stream_t stream);
+
 /* ---- render backward ------------------------------------------------------------------ */
 /* A host-side DEFAULT for BrushAux::flags, nothing more: 1 when the environment holds BRUSH_DETERMINISTIC=1 (read
  * on every call, never cached, never consulted by the render entry points themselves).  A host that wants the
@@ -221,6 +236,18 @@ int brush_render_backward(const BrushUniforms *h_uniforms, const BrushAux *h_aux
                           const float *v_out, float *v_means, float *v_xy, float *v_scales,
                           float *v_quats, float *v_sh, float *v_opac, void *workspace,
                           size_t workspace_bytes, brush_stream_t stream);
+
+/* brush_render_backward for a brush_render_forward_depth render, with v_depth [h,w] the gradient of out_depth.  The
+ * depth is a fourth colour channel whose per-splat value is z (compact_depth of that forward) under the backward's
+ * rules (0.99 clamp, rasterize_backwards.wgsl:239), and dL/dz_i = sum_p T alpha v_depth(p) flows into v_means through
+ * z = row 2 of viewmat . [mean, 1].  Same workspace (brush_bwd_workspace_size_flags), same aliasing rules and same
+ * outputs as brush_render_backward; with v_depth = 0 the deterministic mode gives its gradients bit for bit. */
+int brush_render_backward_depth(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *means,
+                                const float *log_scales, const float *quats, const float *raw_opacity, uint32_t n,
+                                const float *out_img, const float *v_out, const float *compact_depth,
+                                const float *v_depth, float *v_means, float *v_xy, float *v_scales, float *v_quats,
+                                float *v_sh, float *v_opac, void *workspace, size_t workspace_bytes,
+                                brush_stream_t stream);
 
 /* ---- view-sharded data parallelism (build extension; the reference is single-device, batch 1:
  *      crates/brush-train/src/train.rs:216-219) ------------------------------------------------ */

@@ -140,9 +140,10 @@ def test_training_trajectory_is_bitwise_reproducible(dev, det_default):
         gt = torch.rand((h, w, 3), device=dev, generator=torch.Generator(device=dev).manual_seed(3))
         for _ in range(3):
             tr.step(splats, cam, gt, 1.0)
+        tr.sync(splats)  # deferred SH Adam (the default): the pending steps belong to the trajectory
         torch.cuda.synchronize()
         return [q.detach().clone() for q in (splats.means, splats.sh_coeffs, splats.rotation, splats.raw_opacity,
-                                             splats.log_scales)]
+                                             splats.log_scales, tr.moment1, tr.moment2)]
 
     t1, t2 = train_once(), train_once()
     assert all(torch.equal(a, b) for a, b in zip(t1, t2)), "training trajectory must be bitwise reproducible"

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("BRUSH_HIP_LIB") or os.path.join(_HERE, "lib", "libbru
 BRUSH_OK = 0
 AUX_DETERMINISTIC = 1  # BrushAux.flags: BRUSH_AUX_DETERMINISTIC
 AUX_ACCUM_ZEROED = 2   # BrushAux.flags: BRUSH_AUX_ACCUM_ZEROED (backward only)
+AUX_ANTIALIASED = 4    # BrushAux.flags: BRUSH_AUX_ANTIALIASED (opacity compensation for the 2D blur)
 EVAL_GT_U8 = 0         # brush_eval_metrics / brush_l1_ssim_loss_gt gt_dtype: BRUSH_EVAL_GT_U8
 EVAL_GT_F32 = 1        # BRUSH_EVAL_GT_F32
 UNIFORM_WORDS = 28

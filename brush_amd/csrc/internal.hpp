@@ -97,6 +97,9 @@ struct DetSumsArgs {
 };
 hipError_t launch_sum_isect_rows(const float *rows, const uint32_t *num_intersections, const uint32_t *cum_tiles_hit,
                                  uint32_t cap, float *v_compact, float *partials, hipStream_t s);
+// Antialiased mode (BRUSH_AUX_ANTIALIASED) in the kernels' template arguments: the per-splat kernels that differ in that
+// mode take DM = SH degree | kAaMode where they took the degree, so the instantiations without it are unchanged.
+constexpr int kDegMask = 7, kAaMode = 8;
 hipError_t launch_project_backward(const ViewParams &vp, const float *means, const float *log_scales,
                                    const float *quats, const float *raw_opac,
                                    const uint32_t *compact_from_global, const float *v_compact,
@@ -105,7 +108,7 @@ hipError_t launch_project_backward(const ViewParams &vp, const float *means, con
                                    const AdamFuse *adam, const DetSumsArgs &det,
                                    bool prezeroed /* dense form only: the arrays are already zero (ZeroFill), the
                                    visible splats' rows alone are written */,
-                                   hipStream_t s);
+                                   hipStream_t s, bool antialiased = false /* BRUSH_AUX_ANTIALIASED */);
 // View-sharded data parallelism (project_bwd.hip): per-view 64-byte gradient records, their index by global id and
 // the deterministic per-splat sum over views (dense arrays, or straight into the Adam update when adam != nullptr).
 hipError_t launch_project_backward_records(const ViewParams &vp, const float *means, const float *log_scales,

@@ -302,7 +302,17 @@ __device__ __forceinline__ void sh_colour(const ViewParams &vp, const float mean
 // from its stored coefficients with the pending zero-gradient steps replayed in registers; nothing is written back.
 // (four waves per SIMD: the launch is 4 waves per SIMD at 1 M splats, one round; the LAZY degree-3 form would otherwise
 // take 130 registers and a second round)
-template <int DEG, bool LAZY = false>
+// Word 8 of the record: sigmoid(raw), times cov_compensation in the antialiased mode.
+template <bool AA>
+__device__ __forceinline__ float record_opacity(float raw_opac, const float raw[3], const float cov2d[3]) {
+    if constexpr (AA) return det_sigmoid(raw_opac) * cov_compensation(raw, cov2d);
+    return det_sigmoid(raw_opac);
+}
+
+// DM = SH degree | kAaMode (internal.hpp): with kAaMode (BRUSH_AUX_ANTIALIASED) the record's opacity is
+// sigmoid(raw) * cov_compensation (splat_math.hpp), everything else is as without it.  The mode rides in the degree
+// argument so that the instantiations without it keep their names and their code.
+template <int DM, bool LAZY = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_project_cull(ViewParams vp, BrushUniforms u,
                                                            const float *__restrict__ means,
                                                            const float *__restrict__ log_scales,
@@ -319,6 +329,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
                                                            uint32_t *__restrict__ tile_bins, uint32_t num_bin_words,
                                                            uint32_t *__restrict__ bin_edges,
                                                            uint32_t *__restrict__ walk_counter, LazySh lazy) {
+    constexpr int DEG = DM & kDegMask;
+    constexpr bool AA = (DM & kAaMode) != 0;
     __shared__ uint32_t wave_cnt[kThreads / kWave];
     __shared__ uint32_t vis_list[kThreads / kWave][kCullPerThread * kWave];  // per wave: global ids that passed
     BRUSH_KTRACE(kTrCull, 0);
@@ -406,9 +418,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             const float quat[4] = {q4.x, q4.y, q4.z, q4.w};
             const float ro = raw_opac[g];
             const float *sh = sh_coeffs + (size_t)g * ((DEG + 1) * (DEG + 1)) * 3;
-            float p_view[3], cov2d[3];
+            float p_view[3], cov2d[3], raw[3];
             to_view(vp, mean, p_view);
-            calc_cov2d(vp, p_view, scale, quat, cov2d);
+            calc_cov2d(vp, p_view, scale, quat, cov2d, AA ? raw : nullptr);
             const float det = cov2d[0] * cov2d[2] - cov2d[1] * cov2d[1];
             if (!(det == 0.0f)) {  // :43
                 float conic[3], xy[2];
@@ -419,6 +431,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
                 get_tile_bbox(xy, radius, vp.tile_bounds, bb);
                 if ((bb[2] - bb[0]) != 0u && (bb[3] - bb[1]) != 0u) {  // :60
                     visible = true;
+                    // the antialiased opacity before the colour: the covariance terms die here instead of living
+                    // through the SH evaluation (the LAZY degree-3 form is at the register cap)
+                    float opac_aa = 0.0f;
+                    if constexpr (AA) opac_aa = record_opacity<true>(ro, raw, cov2d);
                     float rgb[3];
                     if constexpr (LAZY) {
                         constexpr uint32_t kRow = (DEG + 1) * (DEG + 1) * 3;
@@ -430,7 +446,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
                     }
                     float4 *row = proj_global + (size_t)g * 3;
                     row[0] = make_float4(xy[0], xy[1], conic[0], conic[1]);
-                    row[1] = make_float4(conic[2], det_sigmoid(ro), 0.0f, 0.0f);
+                    row[1] = make_float4(conic[2], AA ? opac_aa : record_opacity<false>(ro, raw, cov2d), 0.0f, 0.0f);
                     row[2] = make_float4(rgb[0], rgb[1], rgb[2], 0.0f);
                 }
             }
@@ -965,11 +981,17 @@ hipError_t launch_project_cull(const ViewParams &vp, const BrushUniforms &u, con
     uint32_t *compact_from_global = aux.compact_from_global_gid;
     uint32_t *num_visible = aux.num_visible;
     uint32_t *uniforms_buffer = aux.uniforms_buffer;
-#define BRUSH_LAUNCH_CULL(D, L)                                                                                  \
-    hipLaunchKernelGGL((k_project_cull<D, L>), dim3(blocks), dim3(kThreads), 0, s, vp, u, means, log_scales, quats, \
+    const bool aa = (aux.flags & BRUSH_AUX_ANTIALIASED) != 0;
+#define BRUSH_LAUNCH_CULL_DM(DM, L)                                                                               \
+    hipLaunchKernelGGL((k_project_cull<DM, L>), dim3(blocks), dim3(kThreads), 0, s, vp, u, means, log_scales, quats, \
                        sh, raw_opac, reinterpret_cast<float4 *>(proj_global), key_all, compact_from_global,      \
                        block_counts, uniforms_buffer, aux.num_intersections, aux.overflow, aux.tile_bins,        \
                        num_tiles * 2, bin_edges, walk.counter, lazy)
+#define BRUSH_LAUNCH_CULL(D, L)                                                                                  \
+    do {                                                                                                         \
+        if (aa) BRUSH_LAUNCH_CULL_DM((D) | kAaMode, L);                                                          \
+        else BRUSH_LAUNCH_CULL_DM(D, L);                                                                         \
+    } while (0)
     if (lazy.on()) {  // rows of whole 16-byte chunks only (make_lazy_sh)
         if (vp.sh_degree == 1) BRUSH_LAUNCH_CULL(1, true);
         else BRUSH_LAUNCH_CULL(3, true);
@@ -983,6 +1005,7 @@ hipError_t launch_project_cull(const ViewParams &vp, const BrushUniforms &u, con
         }
     }
 #undef BRUSH_LAUNCH_CULL
+#undef BRUSH_LAUNCH_CULL_DM
     if (blocks <= kSelfScanBlocks) {
         hipLaunchKernelGGL(k_compact<true>, dim3(blocks), dim3(kThreads), 0, s, n, key_all, block_counts, keys, gids,
                            num_visible, uniforms_buffer);

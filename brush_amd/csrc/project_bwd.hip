@@ -75,9 +75,14 @@ __global__ __launch_bounds__(kThreads) void k_zero_compact_grads(const uint32_t 
 
 // ProjectBackwards for one splat (project_backwards.wgsl:83-226): (v_xy, v_conic) -> v_mean, v_scale (log
 // space), v_quat.  Shared by the dense kernel, the per-view record kernel and nothing else.
+// AA (BRUSH_AUX_ANTIALIASED): v_comp, the gradient of the opacity factor comp, also enters v_cov2d
+// (project_backwards.wgsl:112-128, disabled in the reference), and *comp_out receives comp, recomputed by the
+// forward's own function from the same calc_cov2d outputs.
+template <bool AA = false>
 __device__ __forceinline__ void splat_projection_vjp(const ViewParams &vp, const float mean[3], const float scale[3],
                                                      const float quat[4], const float vxy[2], const float vconic[3],
-                                                     float o_mean[3], float o_scale[3], float o_quat[4]) {
+                                                     float o_mean[3], float o_scale[3], float o_quat[4],
+                                                     float v_comp = 0.0f, float *comp_out = nullptr) {
     const Mat3 W = view_rot(vp);
     float p_view[3];
     to_view(vp, mean, p_view);
@@ -93,10 +98,24 @@ __device__ __forceinline__ void splat_projection_vjp(const ViewParams &vp, const
 #pragma unroll
     for (int i = 0; i < 3; i++) vm[i] = W.m[0][i] * vpj[0] + W.m[1][i] * vpj[1] + W.m[2][i] * vpj[2];
 
-    float cov2d[3], conic[3], v_cov2d[3];
-    calc_cov2d(vp, p_view, scale, quat, cov2d);
+    float cov2d[3], conic[3], v_cov2d[3], raw[3];
+    calc_cov2d(vp, p_view, scale, quat, cov2d, AA ? raw : nullptr);
     cov_to_conic(cov2d, conic);
     cov2d_to_conic_vjp(conic, vconic, v_cov2d);
+    if constexpr (AA) {
+        // comp^2 = det(S) / det(S + 0.3 I): d comp^2 / d(S + 0.3 I) = (1 - comp^2) conic - 0.3 det(conic) I, the
+        // off-diagonal counted twice (cov2d_to_conic_vjp's convention for c01)
+        const float comp = cov_compensation(raw, cov2d);
+        *comp_out = comp;
+        if (comp > 0.0f) {
+            const float inv_det = conic[0] * conic[2] - conic[1] * conic[1];
+            const float one_minus_sqr_comp = 1.0f - comp * comp;
+            const float v_sqr_comp = v_comp * 0.5f / (comp + 1e-6f);
+            v_cov2d[0] = v_cov2d[0] + v_sqr_comp * (one_minus_sqr_comp * conic[0] - kCovBlur * inv_det);
+            v_cov2d[1] = v_cov2d[1] + 2.0f * v_sqr_comp * (one_minus_sqr_comp * conic[1]);
+            v_cov2d[2] = v_cov2d[2] + v_sqr_comp * (one_minus_sqr_comp * conic[2] - kCovBlur * inv_det);
+        }
+    }
 
     const float rz = 1.0f / p_view[2];
     const float rz2 = rz * rz;
@@ -602,7 +621,9 @@ __device__ __forceinline__ void zero_invisible_rows(uint32_t n, uint32_t g0, uin
 
 // GatherGrads + ProjectBackwards of one visible splat `g` from its compact-order sums (r0, r1, r2): the parameter
 // gradients and the factors of its v_sh row (Y[k] * vcol).  Shared by the dense kernels; same expression trees in both.
-template <int DEG>
+// AA: the compositing gradient v_alpha is with respect to the record's opacity sigmoid(raw) * comp (brush_hip.h:
+// BRUSH_AUX_ANTIALIASED).
+template <int DEG, bool AA = false>
 __device__ __forceinline__ void visible_splat_vjp(const ViewParams &vp, const float *means, const float *log_scales,
                                                   const float *__restrict__ quats, const float *raw_opac, uint32_t g,
                                                   const float4 r0, const float4 r1, const float4 r2, float o_mean[3],
@@ -627,6 +648,15 @@ __device__ __forceinline__ void visible_splat_vjp(const ViewParams &vp, const fl
     view_dir(vp, mean, dir);
     sh_basis<ncoef>(DEG, dir, Y);
     const float sg = det_sigmoid(raw_opac[g]);
+    if constexpr (AA) {
+        // v_raw = v_alpha comp sigmoid (1 - sigmoid); v_comp = v_alpha sigmoid goes into the projection VJP
+        o_xy[0] = vxy[0];
+        o_xy[1] = vxy[1];
+        float comp;
+        splat_projection_vjp<true>(vp, mean, scale, quat, vxy, vconic, o_mean, o_scale, o_quat, v_alpha_sum * sg, &comp);
+        o_opac = (v_alpha_sum * comp) * (sg * (1.0f - sg));
+        return;
+    }
     o_opac = v_alpha_sum * (sg * (1.0f - sg));
     o_xy[0] = vxy[0];
     o_xy[1] = vxy[1];
@@ -677,13 +707,16 @@ __device__ __forceinline__ void store_visible_rows(uint32_t g, const float o_mea
 // GLOBAL id: a launch over the visible splats in depth order writes the same rows slower at every size measured — 27.5
 // vs 25.9 us at 1 M splats, 0.80 vs 0.57 ms at 21 M — because the partial lines of neighbouring splats no longer meet
 // in the L2; profiles/r04_zero_fill_in_passing.json.)
-template <int DEG, bool ADAM, bool PREZEROED = false>
+// DM = SH degree | kAaMode (internal.hpp): with kAaMode (BRUSH_AUX_ANTIALIASED) the VJP is visible_splat_vjp<DEG, true>.
+template <int DM, bool ADAM, bool PREZEROED = false>
 __global__ __launch_bounds__(kThreads) void k_project_backward(
     ViewParams vp, const float *means, const float *log_scales, const float *__restrict__ quats,
     const float *raw_opac, const uint32_t *__restrict__ compact_from_global,
     const float *__restrict__ v_compact, float *__restrict__ v_means, float *__restrict__ v_xy,
     float *__restrict__ v_scales, float *__restrict__ v_quats, float *__restrict__ v_sh,
     float *__restrict__ v_opac, AdamFuse af, DetSums det) {
+    constexpr int DEG = DM & kDegMask;
+    constexpr bool AA = (DM & kAaMode) != 0;
     constexpr uint32_t ncoef = (DEG + 1) * (DEG + 1);
     constexpr uint32_t kRow = ncoef * 3;                 // floats per v_sh row
     constexpr uint32_t kRowPad = kRow | 1u;              // odd LDS row stride: conflict-free column access
@@ -735,8 +768,8 @@ __global__ __launch_bounds__(kThreads) void k_project_backward(
     if (c != kInvalid) {
         float4 r0, r1, r2;
         load_compact_sums(v_compact, det, c, r0, r1, r2);
-        visible_splat_vjp<DEG>(vp, means, log_scales, quats, raw_opac, g, r0, r1, r2, o_mean, o_scale, o_quat, o_opac, o_xy,
-                               vcol, Y);
+        visible_splat_vjp<DEG, AA>(vp, means, log_scales, quats, raw_opac, g, r0, r1, r2, o_mean, o_scale, o_quat, o_opac,
+                                   o_xy, vcol, Y);
         // dense gradients: the computing lane writes the visible splat's rows itself (ordinary stores)
         if (!ADAM) store_visible_rows<DEG>(g, o_mean, o_scale, o_quat, o_opac, o_xy, vcol, Y, v_means, v_xy, v_scales, v_quats, v_sh, v_opac);
         if (ADAM) {
@@ -793,11 +826,14 @@ __global__ __launch_bounds__(kThreads) void k_project_backward(
 // kernel (53 us) and a plain small-group stream (60 us at 4.7 TB/s) — could not.  Same expressions as
 // store_gradients_or_step<ADAM>: the same bits as the all-in-one kernel.  Requires n % 4 == 0 and 16-byte aligned
 // arrays (AdamFuse::vec_ok).
-template <int DEG>
+// DM = SH degree | kAaMode, as k_project_backward.
+template <int DM>
 __global__ __launch_bounds__(kThreads) void k_project_backward_lazy(
     ViewParams vp, const float *means, const float *log_scales, const float *__restrict__ quats, const float *raw_opac,
     const uint32_t *__restrict__ compact_from_global, const float *__restrict__ v_compact, float *__restrict__ v_xy,
     AdamFuse af, DetSums det) {
+    constexpr int DEG = DM & kDegMask;
+    constexpr bool AA = (DM & kAaMode) != 0;
     constexpr uint32_t ncoef = (DEG + 1) * (DEG + 1), kRow = ncoef * 3, kChunks = kRow / 4;
     static_assert(kRow % 4 == 0, "rows of whole 16-byte chunks");
     constexpr uint32_t kFac = (5 + ncoef) | 1u;
@@ -832,8 +868,8 @@ __global__ __launch_bounds__(kThreads) void k_project_backward_lazy(
         float4 r0, r1, r2;
         load_compact_sums(v_compact, det, c, r0, r1, r2);
         float o_mean[3], o_scale[3], o_quat[4], o_xy[2], o_opac, vcol[3], Y[ncoef];
-        visible_splat_vjp<DEG>(vp, means, log_scales, quats, raw_opac, g, r0, r1, r2, o_mean, o_scale, o_quat, o_opac, o_xy,
-                               vcol, Y);
+        visible_splat_vjp<DEG, AA>(vp, means, log_scales, quats, raw_opac, g, r0, r1, r2, o_mean, o_scale, o_quat, o_opac,
+                                   o_xy, vcol, Y);
         const float vx = o_xy[0] * af.half_w, vy = o_xy[1] * af.half_h;  // train.rs:300-302
         reinterpret_cast<float2 *>(v_xy)[g] = make_float2(o_xy[0], o_xy[1]);
         float *sg = small_g[li];
@@ -1205,7 +1241,8 @@ hipError_t launch_project_backward(const ViewParams &vp, const float *means, con
                                    const float *quats, const float *raw_opac,
                                    const uint32_t *compact_from_global, const float *v_compact, float *v_means,
                                    float *v_xy, float *v_scales, float *v_quats, float *v_sh, float *v_opac,
-                                   const AdamFuse *adam, const DetSumsArgs &dargs, bool prezeroed, hipStream_t s) {
+                                   const AdamFuse *adam, const DetSumsArgs &dargs, bool prezeroed, hipStream_t s,
+                                   bool antialiased) {
     const uint32_t n = vp.total_splats;
     if (n == 0) return hipSuccess;
     const dim3 grid(ceil_div(n, kThreads)), block(kThreads);
@@ -1213,15 +1250,28 @@ hipError_t launch_project_backward(const ViewParams &vp, const float *means, con
     if (adam) af = *adam;
     const DetSums det{dargs.cum_tiles_hit, dargs.num_intersections, dargs.partials, dargs.cap};
     if (adam && af.lazy.on()) {  // SH block under deferred Adam
-        if (vp.sh_degree == 1)
-            hipLaunchKernelGGL(k_project_backward_lazy<1>, grid, block, 0, s, vp, means, log_scales, quats, raw_opac,
-                               compact_from_global, v_compact, v_xy, af, det);
-        else
-            hipLaunchKernelGGL(k_project_backward_lazy<3>, grid, block, 0, s, vp, means, log_scales, quats, raw_opac,
-                               compact_from_global, v_compact, v_xy, af, det);
+#define BRUSH_LAUNCH_PBL(DM)                                                                                    \
+    hipLaunchKernelGGL(k_project_backward_lazy<DM>, grid, block, 0, s, vp, means, log_scales, quats, raw_opac,  \
+                       compact_from_global, v_compact, v_xy, af, det)
+        if (vp.sh_degree == 1) {
+            if (antialiased) BRUSH_LAUNCH_PBL(1 | kAaMode);
+            else BRUSH_LAUNCH_PBL(1);
+        } else {
+            if (antialiased) BRUSH_LAUNCH_PBL(3 | kAaMode);
+            else BRUSH_LAUNCH_PBL(3);
+        }
+#undef BRUSH_LAUNCH_PBL
         return hipGetLastError();
     }
-#define BRUSH_LAUNCH_PB(D)                                                                                      \
+#define BRUSH_LAUNCH_PB(D0)                                                                                     \
+    if (antialiased) {                                                                                          \
+        constexpr int D = (D0) | kAaMode;                                                                       \
+        BRUSH_LAUNCH_PB_DM(D);                                                                                  \
+    } else {                                                                                                    \
+        constexpr int D = (D0);                                                                                 \
+        BRUSH_LAUNCH_PB_DM(D);                                                                                  \
+    }
+#define BRUSH_LAUNCH_PB_DM(D)                                                                                   \
     if (adam)                                                                                                   \
         hipLaunchKernelGGL((k_project_backward<D, true>), grid, block, 0, s, vp, means, log_scales, quats,      \
                            raw_opac, compact_from_global, v_compact, v_means, v_xy, v_scales, v_quats, v_sh,    \
@@ -1242,6 +1292,7 @@ hipError_t launch_project_backward(const ViewParams &vp, const float *means, con
         default: BRUSH_LAUNCH_PB(4); break;
     }
 #undef BRUSH_LAUNCH_PB
+#undef BRUSH_LAUNCH_PB_DM
     return hipGetLastError();
 }
 

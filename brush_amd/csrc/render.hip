@@ -127,7 +127,8 @@ BwdWs carve_bwd(void *ws, uint32_t n, uint32_t cap, bool det) {
 inline bool aux_det(const BrushAux &a) { return (a.flags & BRUSH_AUX_DETERMINISTIC) != 0; }
 
 bool aux_ok(const BrushAux *a, bool need_final_index) {
-    if (a && (a->flags & ~(BRUSH_AUX_DETERMINISTIC | BRUSH_AUX_ACCUM_ZEROED)) != 0) return false;  // unknown flag bits
+    if (a && (a->flags & ~(BRUSH_AUX_DETERMINISTIC | BRUSH_AUX_ACCUM_ZEROED | BRUSH_AUX_ANTIALIASED)) != 0)
+        return false;  // unknown flag bits
     if (a && aux_det(*a) && !a->isect_unsorted_pos) return false;
     return a && a->projected_splats && a->uniforms_buffer && a->num_intersections && a->num_visible &&
            (a->final_index || !need_final_index) && a->cum_tiles_hit && a->tile_bins &&
@@ -189,6 +190,8 @@ extern "C" int brush_bwd_workspace_size_flags(uint32_t n, uint32_t w, uint32_t h
                                               uint32_t max_intersects, uint32_t flags, size_t *bytes) {
     (void)w;
     (void)h;
+    // Only the bits that size the workspace are taken (brush_hip.h); BRUSH_AUX_ANTIALIASED sizes nothing and is refused
+    // like any other bit, as before it existed.
     if (!bytes || sh_degree > 4 || (flags & ~BRUSH_AUX_DETERMINISTIC) != 0) return BRUSH_ERR_INVALID_ARG;
     *bytes = carve_bwd(nullptr, n, max_intersects, (flags & BRUSH_AUX_DETERMINISTIC) != 0).bytes;
     return BRUSH_OK;
@@ -408,7 +411,7 @@ static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux 
     // GatherGrads + ProjectBackwards fused, dense outputs written once (render.rs:534-594)
     BRUSH_HIP_CHECK(launch_project_backward(vp, means, log_scales, quats, raw_opacity, aux.compact_from_global_gid,
                                             ws.v_compact, v_means, v_xy, v_scales, v_quats, v_sh, v_opac, adam, det,
-                                            filled, s));
+                                            filled, s, (aux.flags & BRUSH_AUX_ANTIALIASED) != 0));
     // depth: z = viewmat row 2 . [mean, 1] carries v_z into v_means
     if (v_depth)
         BRUSH_HIP_CHECK(launch_depth_means_grad(vp, aux.num_visible, n, aux.global_from_compact_gid, ws.v_compact, det,
@@ -515,6 +518,7 @@ extern "C" int brush_render_backward_records(const BrushUniforms *h_uniforms, co
     if (n > 0 && (!means || !log_scales || !quats || !raw_opacity || (max_rows > 0 && !records)))
         return BRUSH_ERR_INVALID_ARG;
     if ((reinterpret_cast<uintptr_t>(records) & 15) != 0) return BRUSH_ERR_INVALID_ARG;
+    if (h_aux->flags & BRUSH_AUX_ANTIALIASED) return BRUSH_ERR_INVALID_ARG;  // out of scope (brush_hip.h)
     const BrushAux &aux = *h_aux;
     const BwdWs ws = carve_bwd(workspace, n, aux.max_intersects, aux_det(aux));
     if (workspace_bytes < ws.bytes) return BRUSH_ERR_WORKSPACE_SMALL;

@@ -131,10 +131,10 @@ __device__ __forceinline__ float clampf(float x, float lo, float hi) {
     return fminf(fmaxf(x, lo), hi);
 }
 
-// helpers.wgsl:124-158 -> (c00, c01, c11)
+// helpers.wgsl:124-158 -> (c00, c01, c11); `raw` (may be null): the same three terms before the blur is added
 __device__ __forceinline__ void calc_cov2d(const ViewParams &vp, const float p_view[3],
                                            const float scale[3], const float quat[4],
-                                           float cov2d[3]) {
+                                           float cov2d[3], float *raw = nullptr) {
     const float img[2] = {(float)vp.img_size[0], (float)vp.img_size[1]};
     float t[2];
     const float rz = 1.0f / p_view[2];
@@ -173,6 +173,18 @@ __device__ __forceinline__ void calc_cov2d(const ViewParams &vp, const float p_v
     cov2d[0] = cov00 + kCovBlur;
     cov2d[1] = cov10;  // WGSL cov[0][1] = column 0, row 1
     cov2d[2] = cov11 + kCovBlur;
+    if (raw) raw[0] = cov00, raw[1] = cov10, raw[2] = cov11;
+}
+
+// Antialiased mode (BRUSH_AUX_ANTIALIASED): the opacity factor that keeps a splat's integrated weight under the blur,
+//   comp = sqrt(max(0, det(S) / det(S + 0.3 I)))
+// (helpers.wgsl:168-173, unused by the reference).  det(S) comes from the unblurred terms `raw` of calc_cov2d:
+// (c00 - 0.3)(c11 - 0.3) - c01^2 would cancel for exactly the sub-pixel splats the mode is for.  0 where det(S) <= 0.
+// The forward and the backward call this one function on the same calc_cov2d outputs: the same bits in both.
+__device__ __forceinline__ float cov_compensation(const float raw[3], const float cov2d[3]) {
+    const float det_orig = raw[0] * raw[2] - raw[1] * raw[1];
+    const float det = cov2d[0] * cov2d[2] - cov2d[1] * cov2d[1];
+    return det_orig > 0.0f ? sqrtf(fmaxf(0.0f, det_orig / det)) : 0.0f;
 }
 
 // helpers.wgsl:160-164

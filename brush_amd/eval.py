@@ -96,10 +96,11 @@ def select_views(num_views: int, num_frames: Optional[int] = None,
 
 
 def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np.random.Generator] = None,
-               window: int = 11, keep_aux: bool = False) -> EvalStats:
+               window: int = 11, keep_aux: bool = False, antialiased: bool = False) -> EvalStats:
     """eval.rs:27-77: render each selected view of `scene` (a dataset.Scene, e.g. Dataset.eval) at its image's size
     through Splats.render under no_grad and score it against the image's RGB, uploaded as uint8, with eval_metrics.
     The metrics of all views go into one [V,3] device tensor that is read back once, after the last view.
+    `antialiased`: render in the antialiased mode (render.render_splats), e.g. splats trained in it.
 
     One deviation from the reference: `aux` is kept only with keep_aux=True, because a RenderAux holds the
     intersection lists of its view (hundreds of MB for a large scene).
@@ -120,7 +121,7 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
                 raise ValueError(f"{v.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
             h, w = int(img.shape[0]), int(img.shape[1])
             gt = torch.from_numpy(img).to(dev)  # u8, as the reference uploads to_rgb8() (the kernel divides by 255)
-            pred, aux = splats.render(v.camera, (w, h), False)
+            pred, aux = splats.render(v.camera, (w, h), False, antialiased=antialiased)
             eval_metrics(pred, gt, window, out=metrics[row])
             rendered.append((pred[..., :3], aux if keep_aux else None))
     host = metrics.cpu().numpy()  # the one readback
@@ -173,11 +174,8 @@ def _load_dataset(args):
     return reader(args.dataset, max_resolution=args.max_resolution, eval_split_every=args.eval_split_every)
 
 
-def main(argv=None) -> int:
+def parser():
     import argparse
-    import json
-    import os
-    import sys
 
     p = argparse.ArgumentParser(prog="python -m brush_amd.eval",
                                 description="PSNR / SSIM of a splat file on a dataset's eval views")
@@ -193,7 +191,18 @@ def main(argv=None) -> int:
     p.add_argument("--depth-dir", default=None,
                    help="also write every eval view's accumulated depth D (<view stem>_depth.npy, f32 [h,w]) and "
                         "D / alpha (<view stem>_depth_norm.npy, 0 where alpha is 0) to this directory")
-    args = p.parse_args(argv)
+    p.add_argument("--antialiased", action="store_true",
+                   help="render in the antialiased mode (opacity compensation of the 2D blur), e.g. for splats "
+                        "trained with it")
+    return p
+
+
+def main(argv=None) -> int:
+    import json
+    import os
+    import sys
+
+    args = parser().parse_args(argv)
 
     data = _load_dataset(args)  # before any GPU work
     if data.eval is None or not data.eval.views:
@@ -207,7 +216,7 @@ def main(argv=None) -> int:
     else:
         splats = Splats.from_ply(args.splats, dev)
     rng = np.random.default_rng(args.seed)
-    stats = eval_stats(splats, data.eval, args.num_frames, rng, args.window)
+    stats = eval_stats(splats, data.eval, args.num_frames, rng, args.window, antialiased=args.antialiased)
     for s in stats.samples:
         print(f"{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
     print(f"mean ({len(stats.samples)} views)\tpsnr {stats.mean_psnr():.4f}\tssim {stats.mean_ssim():.6f}")
@@ -215,6 +224,7 @@ def main(argv=None) -> int:
         write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir)
     if args.json:
         res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "window": args.window,
+               "antialiased": bool(args.antialiased),
                "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in stats.samples],
                "mean_psnr": stats.mean_psnr(), "mean_ssim": stats.mean_ssim()}
         with open(args.json, "w") as f:

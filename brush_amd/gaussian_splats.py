@@ -108,18 +108,20 @@ class Splats(torch.nn.Module):
     def num_splats(self) -> int:
         return self.means.shape[0]
 
-    def render(self, camera: Camera, img_size, render_u32_buffer: bool = False, max_intersects=None):
-        """gaussian_splats.rs:167-188"""
+    def render(self, camera: Camera, img_size, render_u32_buffer: bool = False, max_intersects=None,
+               antialiased: bool = False):
+        """gaussian_splats.rs:167-188; `antialiased`: render.render_splats."""
         self.sync()
         rot = self.rotation
         norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
         return render_splats(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
-                             self.sh_coeffs, self.raw_opacity, render_u32_buffer, max_intersects)
+                             self.sh_coeffs, self.raw_opacity, render_u32_buffer, max_intersects,
+                             antialiased=antialiased)
 
-    def render_depth(self, camera: Camera, img_size, max_intersects=None):
+    def render_depth(self, camera: Camera, img_size, max_intersects=None, antialiased: bool = False):
         """render() with the accumulated depth (render.render_splats_depth): (img [h,w,4], depth [h,w], aux)."""
         self.sync()
         rot = self.rotation
         norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
         return render_splats_depth(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
-                                   self.sh_coeffs, self.raw_opacity, max_intersects)
+                                   self.sh_coeffs, self.raw_opacity, max_intersects, antialiased=antialiased)

@@ -86,6 +86,16 @@ class RenderAux:
     def deterministic(self) -> bool:
         return bool(self.flags & _lib.AUX_DETERMINISTIC)
 
+    @property
+    def antialiased(self) -> bool:
+        """Rendered with the opacity compensation of the 2D blur (BRUSH_AUX_ANTIALIASED)."""
+        return bool(self.flags & _lib.AUX_ANTIALIASED)
+
+    @property
+    def workspace_flags(self) -> int:
+        """The bits of `flags` that size the backward's workspace (brush_bwd_workspace_size_flags takes only those)."""
+        return int(self.flags) & _lib.AUX_DETERMINISTIC
+
     def backward_workspace(self, nbytes: int, device):
         """(workspace tensor, BrushAux struct) for ONE backward call of this render: the buffer the forward pre-zeroed
         (with BRUSH_AUX_ACCUM_ZEROED set, first backward only) or a fresh one."""
@@ -165,8 +175,10 @@ def _check_inputs(means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity):
 def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, render_u32: bool,
                   max_intersects: Optional[int], row_pitch: Optional[int] = None,
                   deterministic: Optional[bool] = None, expect_backward: Optional[bool] = None, lazy_sh=None,
-                  depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                  depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, antialiased: bool = False):
     """depth: (out_depth [h,w], compact_depth [N]) f32 buffers: render with brush_render_forward_depth (float image).
+    antialiased: scale each splat's opacity by sqrt(det(S) / det(S + 0.3 I)) (BRUSH_AUX_ANTIALIASED); the backward of
+    this render follows aux.flags.
     expect_backward (default: a float image in default mode): allocate the backward's workspace now and let the
     forward zero its accumulator rows, so that the backward of this render needs no zero-fill launch.
     lazy_sh: a _lib.BrushLazySh (SplatTrainer's deferred Adam of the SH block): colours come from the coefficients
@@ -197,7 +209,7 @@ def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, ra
         overflow=_empty((1,), i32, dev),
         max_intersects=cap,
         isect_unsorted_pos=_empty((cap,), i32, dev) if det else None,
-        flags=_lib.AUX_DETERMINISTIC if det else 0,
+        flags=(_lib.AUX_DETERMINISTIC if det else 0) | (_lib.AUX_ANTIALIASED if antialiased else 0),
         lazy_sh=lazy_sh,
     )
     if row_pitch is not None:
@@ -210,7 +222,7 @@ def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, ra
         expect_backward = not render_u32
     if expect_backward and not det and not render_u32:
         bbytes = C.c_size_t()
-        _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, sh_degree, cap, int(aux.flags), C.byref(bbytes)),
+        _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, sh_degree, cap, aux.workspace_flags, C.byref(bbytes)),
                    "brush_bwd_workspace_size_flags")
         aux.bwd_ws = _empty((max(bbytes.value, 1),), torch.uint8, dev)
         aux.bwd_ws_zeroed = True
@@ -279,8 +291,8 @@ def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, nco
         "v_opac": seg("v_opac", (n,)), "v_sh": seg("v_sh", (n, ncoef, 3)), "v_xy": seg("v_xy", (n, 2)),
     }
     nbytes = C.c_size_t()
-    _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, int(u.sh_degree), int(aux.max_intersects), int(aux.flags),
-                                                C.byref(nbytes)), "brush_bwd_workspace_size_flags")
+    _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, int(u.sh_degree), int(aux.max_intersects),
+                                                aux.workspace_flags, C.byref(nbytes)), "brush_bwd_workspace_size_flags")
     v_out = v_out.contiguous()
     ws, s = aux.backward_workspace(nbytes.value, dev)
     with torch.cuda.device(dev):
@@ -310,7 +322,8 @@ class _RenderSplatsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder):
         out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
-                                    raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"])
+                                    raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
+                                    antialiased=holder["antialiased"])
         holder["aux"] = aux
         ctx.u, ctx.aux, ctx.ncoef = u, aux, sh_coeffs.shape[1]
         ctx.save_for_backward(means, log_scales, quats, raw_opacity, out)
@@ -329,7 +342,7 @@ def render_splats(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Opt
                   log_scales: torch.Tensor, quats: torch.Tensor, sh_coeffs: torch.Tensor,
                   raw_opacity: torch.Tensor, render_u32_buffer: bool = False,
                   max_intersects: Optional[int] = None,
-                  deterministic: Optional[bool] = None) -> Tuple[torch.Tensor, RenderAux]:
+                  deterministic: Optional[bool] = None, antialiased: bool = False) -> Tuple[torch.Tensor, RenderAux]:
     """Backend::render_splats (lib.rs:75-85).
 
     Returns (img, aux): img is float32 [h,w,4] (rgb, 1-T; no background blend) or, with
@@ -337,6 +350,8 @@ def render_splats(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Opt
     screen-space xy gradient (global order, pixel units).  `max_intersects` defaults to the
     reference's min(N*tiles, 128*65535); aux.overflow reports truncation.  `deterministic` (build extension)
     selects bitwise reproducible gradients for this call (default: render.DETERMINISTIC, then BRUSH_DETERMINISTIC).
+    `antialiased` (build extension, BRUSH_AUX_ANTIALIASED): each splat's opacity is scaled by
+    sqrt(det(S) / det(S + 0.3 I)), so that the 0.3 px^2 blur keeps its integrated weight (Mip-Splatting's 2D filter).
     """
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
     tracked = torch.is_grad_enabled() and not render_u32_buffer and any(
@@ -346,11 +361,12 @@ def render_splats(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Opt
         with torch.no_grad():
             out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity,
                                         render_u32_buffer, max_intersects, deterministic=deterministic,
-                                        expect_backward=False)
+                                        expect_backward=False, antialiased=antialiased)
         return out, aux
     if xy_grad_dummy is None:
         xy_grad_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
-    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic}
+    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic,
+              "antialiased": bool(antialiased)}
     out = _RenderSplatsFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder)
     return out, holder["aux"]
 
@@ -368,7 +384,7 @@ class _RenderSplatsDepthFn(torch.autograd.Function):
         depth = _depth_buffers(means.shape[0], holder["img_size"], means.device)
         out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
                                     raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
-                                    depth=depth)
+                                    depth=depth, antialiased=holder["antialiased"])
         holder["aux"] = aux
         ctx.u, ctx.aux, ctx.ncoef = u, aux, sh_coeffs.shape[1]
         ctx.save_for_backward(means, log_scales, quats, raw_opacity, out, depth[1])
@@ -389,11 +405,13 @@ class _RenderSplatsDepthFn(torch.autograd.Function):
 def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Optional[torch.Tensor],
                         log_scales: torch.Tensor, quats: torch.Tensor, sh_coeffs: torch.Tensor,
                         raw_opacity: torch.Tensor, max_intersects: Optional[int] = None,
-                        deterministic: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor, RenderAux]:
+                        deterministic: Optional[bool] = None,
+                        antialiased: bool = False) -> Tuple[torch.Tensor, torch.Tensor, RenderAux]:
     """render_splats (float image) plus the accumulated depth D(p) = sum_i T_i alpha_i z_i over exactly the entries
     the colour composites (z_i: camera-space z of splat i's mean).  Returns (img [h,w,4], depth [h,w], aux); the image
     and aux are bitwise those of render_splats.  D is not normalised: D / img[..., 3] is the expected depth of the
-    covered part.  Differentiable for gradients on img, on depth or both, into the same six parents."""
+    covered part.  Differentiable for gradients on img, on depth or both, into the same six parents.
+    `antialiased`: as render_splats."""
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
     tracked = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity))
@@ -402,11 +420,12 @@ def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dumm
             depth = _depth_buffers(means.shape[0], img_size, means.device)
             out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, False,
                                         max_intersects, deterministic=deterministic, expect_backward=False,
-                                        depth=depth)
+                                        depth=depth, antialiased=antialiased)
         return out, depth[0], aux
     if xy_grad_dummy is None:
         xy_grad_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
-    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic}
+    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic,
+              "antialiased": bool(antialiased)}
     out, depth = _RenderSplatsDepthFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder)
     return out, depth, holder["aux"]
 
@@ -417,15 +436,16 @@ def rgba8_row_pitch(width: int) -> int:
 
 
 def render_rgba8(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, raw_opacity,
-                 row_pitch: Optional[int] = None, max_intersects: Optional[int] = None):
+                 row_pitch: Optional[int] = None, max_intersects: Optional[int] = None, antialiased: bool = False):
     """Forward-only display path: packed RGBA8 with rows `row_pitch` pixels apart (default
     rgba8_row_pitch(width)), i.e. the padded tensor burn_texture.rs:17-26 builds with a zero-fill
-    and a slice_assign, written by the rasterizer directly.  Returns (int32 [h, row_pitch, 1], aux)."""
+    and a slice_assign, written by the rasterizer directly.  Returns (int32 [h, row_pitch, 1], aux).
+    `antialiased`: as render_splats."""
     _check_inputs(means, None, log_scales, quats, sh_coeffs, raw_opacity)
     pitch = rgba8_row_pitch(img_size[0]) if row_pitch is None else int(row_pitch)
     with torch.no_grad():
         out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, True,
-                                    max_intersects, row_pitch=pitch)
+                                    max_intersects, row_pitch=pitch, antialiased=antialiased)
     return out, aux
 
 

@@ -54,6 +54,10 @@ class TrainConfig:
     # parameter values as the eager optimizer, bit for bit; SplatTrainer.sync() brings `splats.sh_coeffs` up to date
     # for readers that do not go through the trainer (Splats.render / to_ply call it themselves).
     deferred_sh_adam: bool = True
+    # Build extension: render and backpropagate in the antialiased mode (BRUSH_AUX_ANTIALIASED: opacity compensation of
+    # the 2D blur).  Single-view training only: a step given an `exchange` raises.  Refinement still prunes on
+    # sigmoid(raw_opacity), as gsplat does.
+    antialiased: bool = False
 
 
 @dataclass
@@ -281,6 +285,8 @@ class SplatTrainer:
         the same bits) or `grad_sync(block, aux)` summing the dense gradient block over views
         (brush_amd.dist.allreduce_param_grads)."""
         c = self.config
+        if c.antialiased and exchange is not None:
+            raise ValueError("antialiased training has no data-parallel record path (brush_render_backward_records)")
         h, w = int(gt_image.shape[0]), int(gt_image.shape[1])
         n, ncoef = splats.num_splats(), int(splats.sh_coeffs.shape[1])
         if self.moment1.numel() != n * (11 + 3 * ncoef):
@@ -309,7 +315,7 @@ class SplatTrainer:
             self.sync(splats)  # this step reads / steps every SH block: nothing may stay pending
             self._lazy = None
         pred, aux, u = R._forward_impl(camera, (w, h), means, log_scales, norm_rot, sh, raw_opac, False, None,
-                                       lazy_sh=lazy)
+                                       lazy_sh=lazy, antialiased=c.antialiased)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
         loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views, out=loss_out)
@@ -342,7 +348,7 @@ class SplatTrainer:
                 # single view: gradients go straight through the optimizer inside the backward kernel
                 nbytes = C.c_size_t()
                 _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, int(u.sh_degree), int(aux.max_intersects),
-                                                            int(aux.flags), C.byref(nbytes)),
+                                                            aux.workspace_flags, C.byref(nbytes)),
                            "brush_bwd_workspace_size_flags")
                 ws, s_aux = aux.backward_workspace(nbytes.value, means.device)
                 v_xy = torch.empty((max(n, 1), 2), dtype=torch.float32, device=means.device)

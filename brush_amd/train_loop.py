@@ -13,7 +13,7 @@ Command line (one line per eval and a last line; --json also writes the eval row
 
     python -m brush_amd.train_loop DATASET [--steps 30000] [--format auto|nerf|colmap] [--max-resolution R]
         [--eval-split-every K] [--eval-every N] [--eval-views V] [--init PLY] [--init-count 10000] [--sh-degree 3]
-        [--seed 42] [--export OUT.ply] [--json LOG]
+        [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased]
 
 BRUSH_DETERMINISTIC=1 makes the renders (and so a run with a fixed seed) bitwise repeatable.
 """
@@ -142,7 +142,8 @@ class TrainLoop:
         torch.cuda.synchronize(self.device)  # the training time up to here is done
         t = time.perf_counter()
         train_s = t - self._t0 - self._eval_seconds
-        stats = eval_stats(self.splats, self.dataset.eval, eval_views, self.rng)
+        # evaluated in the mode the splats are trained in
+        stats = eval_stats(self.splats, self.dataset.eval, eval_views, self.rng, antialiased=self.config.antialiased)
         loss = float(self.losses[self.done - 1].item()) if self.done > 0 else float("nan")
         dstep, dt = self.done - self._last[0], train_s - self._last[1]
         row = EvalRow(self.done, stats.mean_psnr(), stats.mean_ssim(), self.splats.num_splats(),
@@ -193,11 +194,8 @@ def train_scene(dataset: Dataset, config: Optional[TrainConfig] = None, *, steps
 
 
 # ---------------------------------------------------------------------------- command line
-def main(argv=None) -> int:
+def parser():
     import argparse
-    import json
-    import os
-    import sys
 
     p = argparse.ArgumentParser(prog="python -m brush_amd.train_loop",
                                 description="train splats on a dataset (NeRF-synthetic or COLMAP)")
@@ -214,6 +212,17 @@ def main(argv=None) -> int:
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--export", default=None, help="write the trained splats to this .ply")
     p.add_argument("--json", default=None, help="write the eval rows and the loss curve to this file")
+    p.add_argument("--antialiased", action="store_true",
+                   help="train (and evaluate) in the antialiased mode: opacity compensation of the 2D blur")
+    return p
+
+
+def main(argv=None) -> int:
+    import json
+    import os
+    import sys
+
+    p = parser()
     args = p.parse_args(argv)
     if not os.path.exists(args.dataset):
         p.error(f"dataset not found: {args.dataset}")
@@ -237,7 +246,7 @@ def main(argv=None) -> int:
         print(f"step {row.step}\tpsnr {row.psnr:.4f}\tssim {row.ssim:.6f}\tsplats {row.splats}\t"
               f"{row.iters_per_s:.1f} it/s", flush=True)
 
-    splats, log = train_scene(data, TrainConfig(), steps=args.steps, init=init, init_count=args.init_count,
+    splats, log = train_scene(data, TrainConfig(antialiased=args.antialiased), steps=args.steps, init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,
                               eval_views=args.eval_views, on_eval=on_eval, device=dev)
     final = float(log.losses[-1]) if log.steps else float("nan")
@@ -248,7 +257,8 @@ def main(argv=None) -> int:
         with open(args.export, "wb") as f:
             f.write(splats.to_ply())
     if args.json:
-        res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree}
+        res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree,
+               "antialiased": bool(args.antialiased)}
         res.update(log.to_json())
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)

@@ -116,7 +116,8 @@ typedef struct BrushAux {
                                           the backward to sum a splat's per-tile gradient rows in a fixed order.
                                           Must be non-NULL in that mode, ignored otherwise. */
     uint32_t flags;                    /* BRUSH_AUX_* bits, chosen PER CALL; the forward and the backward of one
-                                          render must be given the same BRUSH_AUX_DETERMINISTIC bit */
+                                          render must be given the same BRUSH_AUX_DETERMINISTIC and
+                                          BRUSH_AUX_ANTIALIASED bits */
     float *bwd_accum;                  /* NULL, or the buffer the caller will pass as `workspace` to the backward of
                                           this render (brush_bwd_workspace_size* bytes).  Default mode only: the
                                           forward's last kernel then also zeroes the backward's per-splat accumulator
@@ -142,6 +143,30 @@ typedef struct BrushAux {
                                       render, nothing has written to it since, and no backward has consumed it yet
                                       (the FIRST backward after that forward): the accumulators are already zero.  A
                                       second backward of the same forward must clear the bit (it zero-fills itself). */
+#define BRUSH_AUX_ANTIALIASED 4u   /* antialiased mode (build extension; Mip-Splatting's 2D filter, gsplat's
+                                      rasterize_mode="antialiased"): every projected covariance S still gets the 0.3 px^2
+                                      blur (helpers.wgsl:153-157), and the opacity a splat is drawn with is scaled so
+                                      that its integrated weight stays what it was before the blur:
+                                          o = sigmoid(raw) * comp,  comp = sqrt(max(0, det(S) / det(S + 0.3 I)))
+                                      with det(S) from the unblurred covariance (0 where det(S) <= 0).  Word 8 of a
+                                      projected_splats row holds o; xy, conic, colour and the visible set are those of the
+                                      plain mode (intersections can only drop: the tile test sees the smaller o).
+                                      Gradient: with v_o the compositing gradient with respect to o,
+                                          v_raw = v_o comp sigmoid(1 - sigmoid)
+                                      and v_comp = v_o sigmoid enters the gradient of S + 0.3 I = (c00, c01, c11) as
+                                          v_sqr = v_comp 0.5 / (comp + 1e-6),
+                                          v_c00 += v_sqr ((1 - comp^2) conic.x - 0.3 det(conic)),
+                                          v_c01 += 2 v_sqr (1 - comp^2) conic.y,
+                                          v_c11 += v_sqr ((1 - comp^2) conic.z - 0.3 det(conic))
+                                      (the reference's disabled VJP, project_backwards.wgsl:112-128; nothing where
+                                      comp = 0), then the plain chain to means, scales and quats.  The forward and the
+                                      backward of one render must be given the same bit.  Accepted by the forward entry
+                                      points, brush_render_backward(_depth) and brush_render_backward_adam, in both
+                                      modes.  The mode needs no extra workspace: size the backward with the render's
+                                      flags & BRUSH_AUX_DETERMINISTIC (brush_bwd_workspace_size_flags takes only the bits
+                                      that size the workspace and refuses this one, as it did before the bit existed).
+                                      brush_render_backward_records (data-parallel training) returns
+                                      BRUSH_ERR_INVALID_ARG with it (out of scope). */
 
 /* ---- introspection ------------------------------------------------------------------ */
 const char *brush_version(void);
@@ -215,7 +240,8 @@ int brush_render_forward_depth(const BrushUniforms *h_uniforms, const float *mea
  * mode per call (a viewer thread beside a trainer task) sets or clears BRUSH_AUX_DETERMINISTIC itself. */
 int brush_deterministic(void);
 /* Backward workspace for a call with these BrushAux::flags and this intersection capacity (the deterministic mode
- * keeps 64 bytes per intersection). */
+ * keeps 64 bytes per intersection).  `flags` holds the bits that size the workspace, i.e. BRUSH_AUX_DETERMINISTIC or
+ * nothing; any other bit returns BRUSH_ERR_INVALID_ARG (an antialiased render passes flags & BRUSH_AUX_DETERMINISTIC). */
 int brush_bwd_workspace_size_flags(uint32_t n, uint32_t w, uint32_t h, uint32_t sh_degree, uint32_t max_intersects,
                                    uint32_t flags, size_t *bytes);
 /* Shorthands: flags = 0 (the default mode); brush_bwd_workspace_size also assumes

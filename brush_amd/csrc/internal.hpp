@@ -1,5 +1,7 @@
 // internal.hpp — host-side launch functions, one group per translation unit.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "lazy_sh.hpp"
 
@@ -72,7 +74,7 @@ hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint3
                                      const float *compact_depth = nullptr /* brush_render_backward_depth: [n] z */,
                                      const float *v_depth = nullptr /* [h][w]: gradient of the accumulated depth */);
 
-// project_bwd.hip
+// project_bwd.hip, view_records.hip
 // Optimizer state for the fused backward + Adam form (brush_render_backward_adam).
 struct AdamFuse {
     float *means, *log_scales, *rotation, *raw_opac, *sh;  // parameters, updated in place
@@ -87,7 +89,7 @@ struct AdamFuse {
     LazySh lazy;                                           // BrushAdamConfig::lazy_sh (off: every SH block is stepped)
 };
 hipError_t launch_lazy_sh_flush(const LazySh &lazy, float *sh, uint32_t n, uint32_t row_floats, hipStream_t s);
-// Deterministic mode: where a splat's compact-order sums come from (see project_bwd.hip); partials == nullptr
+// Deterministic mode: where a splat's compact-order sums come from (see det_sums.hpp); partials == nullptr
 // selects the default atomic accumulators in v_compact.
 struct DetSumsArgs {
     const uint32_t *cum_tiles_hit = nullptr;
@@ -100,6 +102,30 @@ hipError_t launch_sum_isect_rows(const float *rows, const uint32_t *num_intersec
 // Antialiased mode (BRUSH_AUX_ANTIALIASED) in the kernels' template arguments: the per-splat kernels that differ in that
 // mode take DM = SH degree | kAaMode where they took the degree, so the instantiations without it are unchanged.
 constexpr int kDegMask = 7, kAaMode = 8;
+// Runtime (sh_degree, antialiased) -> compile-time template argument of a kernel launch: f receives an IntC<...>, whose
+// `dm()` is the argument.  dispatch_degree: degrees 0-4 (anything above: 4); dispatch_dm adds the kAaMode bit;
+// dispatch_dm_lazy, for the deferred-SH forms (rows of whole 16-byte chunks): degrees 1 and 3 only (anything else: 3).
+template <int D> using IntC = std::integral_constant<int, D>;
+template <int D, typename F>
+void dispatch_aa(bool antialiased, F &&f) { antialiased ? f(IntC<D | kAaMode>{}) : f(IntC<D>{}); }
+template <typename F>
+void dispatch_degree(uint32_t sh_degree, F &&f) {
+    switch (sh_degree) {
+        case 0: return f(IntC<0>{});
+        case 1: return f(IntC<1>{});
+        case 2: return f(IntC<2>{});
+        case 3: return f(IntC<3>{});
+        default: return f(IntC<4>{});
+    }
+}
+template <typename F>
+void dispatch_dm(uint32_t sh_degree, bool antialiased, F &&f) {
+    dispatch_degree(sh_degree, [&](auto deg) { dispatch_aa<deg()>(antialiased, f); });
+}
+template <typename F>
+void dispatch_dm_lazy(uint32_t sh_degree, bool antialiased, F &&f) {
+    sh_degree == 1 ? dispatch_aa<1>(antialiased, f) : dispatch_aa<3>(antialiased, f);
+}
 hipError_t launch_project_backward(const ViewParams &vp, const float *means, const float *log_scales,
                                    const float *quats, const float *raw_opac,
                                    const uint32_t *compact_from_global, const float *v_compact,
@@ -109,7 +135,7 @@ hipError_t launch_project_backward(const ViewParams &vp, const float *means, con
                                    bool prezeroed /* dense form only: the arrays are already zero (ZeroFill), the
                                    visible splats' rows alone are written */,
                                    hipStream_t s, bool antialiased = false /* BRUSH_AUX_ANTIALIASED */);
-// View-sharded data parallelism (project_bwd.hip): per-view 64-byte gradient records, their index by global id and
+// View-sharded data parallelism (view_records.hip): per-view 64-byte gradient records, their index by global id and
 // the deterministic per-splat sum over views (dense arrays, or straight into the Adam update when adam != nullptr).
 hipError_t launch_project_backward_records(const ViewParams &vp, const float *means, const float *log_scales,
                                            const float *quats, const float *raw_opac, const uint32_t *num_visible,

@@ -6,7 +6,7 @@
 // 24 bytes per parameter the optimizer moves, although ~90 % of the splats are outside the view, have a zero gradient,
 // and their coefficients are read by nothing until the splat is visible again.  A zero-gradient Adam step is a pure
 // function of (m, v, x) and the step's constants, so it can be applied LATER, bit for bit: lazy_step_elem() below is
-// adam_elem4() / copy_out() of project_bwd.hip with g = 0, and every translation unit that includes this file is built
+// adam_elem4() / step_rows() of grad_out.hpp with g = 0, and every translation unit that includes this file is built
 // with -ffp-contract=off, so a replayed step rounds exactly as the eager one would have.
 #pragma once
 #include <math.h>
@@ -63,7 +63,7 @@ __device__ __forceinline__ float adam_stepped(float m, float v, float x, float r
 
 // One zero-gradient step on one element, with the constants `c` = (1 / bc1, 1 / bc2, lr, lerp) of its optimizer time;
 // `rest`: an SH coefficient >= 1, which takes the lerp of train.rs:336-351.  Expression for expression adam_elem4()
-// and the lerp of copy_out() (project_bwd.hip) with g = 0.
+// and the lerp of step_rows() (grad_out.hpp) with g = 0.
 __device__ __forceinline__ void lazy_step_elem(const LazySh &z, const float4 c, bool rest, float &m, float &v, float &x) {
 #pragma clang fp contract(off)
     const float g = 0.0f;

@@ -982,30 +982,14 @@ hipError_t launch_project_cull(const ViewParams &vp, const BrushUniforms &u, con
     uint32_t *num_visible = aux.num_visible;
     uint32_t *uniforms_buffer = aux.uniforms_buffer;
     const bool aa = (aux.flags & BRUSH_AUX_ANTIALIASED) != 0;
-#define BRUSH_LAUNCH_CULL_DM(DM, L)                                                                               \
-    hipLaunchKernelGGL((k_project_cull<DM, L>), dim3(blocks), dim3(kThreads), 0, s, vp, u, means, log_scales, quats, \
-                       sh, raw_opac, reinterpret_cast<float4 *>(proj_global), key_all, compact_from_global,      \
-                       block_counts, uniforms_buffer, aux.num_intersections, aux.overflow, aux.tile_bins,        \
-                       num_tiles * 2, bin_edges, walk.counter, lazy)
-#define BRUSH_LAUNCH_CULL(D, L)                                                                                  \
-    do {                                                                                                         \
-        if (aa) BRUSH_LAUNCH_CULL_DM((D) | kAaMode, L);                                                          \
-        else BRUSH_LAUNCH_CULL_DM(D, L);                                                                         \
-    } while (0)
-    if (lazy.on()) {  // rows of whole 16-byte chunks only (make_lazy_sh)
-        if (vp.sh_degree == 1) BRUSH_LAUNCH_CULL(1, true);
-        else BRUSH_LAUNCH_CULL(3, true);
-    } else {
-        switch (vp.sh_degree) {
-            case 0: BRUSH_LAUNCH_CULL(0, false); break;
-            case 1: BRUSH_LAUNCH_CULL(1, false); break;
-            case 2: BRUSH_LAUNCH_CULL(2, false); break;
-            case 3: BRUSH_LAUNCH_CULL(3, false); break;
-            default: BRUSH_LAUNCH_CULL(4, false); break;
-        }
-    }
-#undef BRUSH_LAUNCH_CULL
-#undef BRUSH_LAUNCH_CULL_DM
+    auto launch = [&](auto dm, auto deferred) {
+        hipLaunchKernelGGL((k_project_cull<dm(), deferred()>), dim3(blocks), dim3(kThreads), 0, s, vp, u, means, log_scales,
+                           quats, sh, raw_opac, reinterpret_cast<float4 *>(proj_global), key_all, compact_from_global,
+                           block_counts, uniforms_buffer, aux.num_intersections, aux.overflow, aux.tile_bins,
+                           num_tiles * 2, bin_edges, walk.counter, lazy);
+    };
+    if (lazy.on()) dispatch_dm_lazy(vp.sh_degree, aa, [&](auto dm) { launch(dm, std::true_type{}); });
+    else dispatch_dm(vp.sh_degree, aa, [&](auto dm) { launch(dm, std::false_type{}); });
     if (blocks <= kSelfScanBlocks) {
         hipLaunchKernelGGL(k_compact<true>, dim3(blocks), dim3(kThreads), 0, s, n, key_all, block_counts, keys, gids,
                            num_visible, uniforms_buffer);

@@ -2,7 +2,7 @@
 
 * cov2d64: calc_cov2d (splat_math.hpp, helpers.wgsl:124-158) with its frustum clamp, before and after the 0.3 px^2 blur;
 * comp64: sqrt(max(0, det(S) / det(S + 0.3 I))), 0 where det(S) <= 0;
-* comp_vjp64: the VJP from v_comp to (means, log_scales, normalised quats) exactly as project_bwd.hip computes it:
+* comp_vjp64: the VJP from v_comp to (means, log_scales, normalised quats) exactly as splat_vjp.hpp computes it:
   v_sqr = v_comp 0.5 / (comp + 1e-6), d comp^2 / d(S + 0.3 I) = (1 - comp^2) conic - 0.3 det(conic) I, then the
   projection chain of splat_projection_vjp with the Jacobian at the UNCLAMPED p_view (SURVEY 2b quirk 3);
 * word8_bound: a forward-error bound of the kernel's f32 opacity word sigmoid(raw) * comp, derived from the

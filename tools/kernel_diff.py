@@ -2,14 +2,19 @@
 
     python tools/kernel_diff.py OLD.so NEW.so
     python tools/kernel_diff.py --resources LIB.so REGEX   # registers / spills / scratch / LDS of matching kernels
+    python tools/kernel_diff.py --opcodes OLD.so NEW.so    # also: per-opcode count differences of every CHANGED kernel
 
 For each .so: the device code objects (one per translation unit) are taken out of the .hip_fatbin section and
 unbundled with clang-offload-bundler; then, for every kernel symbol of OLD, the llvm-objdump disassembly of the kernel (addresses
 and trailing comments stripped: they move when other kernels are added) and the 64 bytes of its kernel descriptor
 (<name>.kd) must be identical in NEW.  Kernels only NEW has are listed as new.  Exit status 1 on any difference.
+A kernel whose descriptor differs (registers, spills, scratch, LDS) is reported as "CHANGED descriptor", whatever its code.
+--opcodes tells a reordering (every count equal), added register moves (only v_mov / s_mov / nop counts differ) and a
+different instruction selection (anything else, e.g. one global_load_dwordx3 against three global_load_dword) apart.
 """
 from __future__ import annotations
 
+import collections
 import os
 import re
 import struct
@@ -101,6 +106,9 @@ def kernels(co: str):
         if cur is None or not line.strip():
             continue
         bodies[cur].append(line.split("//")[0].strip())
+    for body in bodies.values():  # "...": the zero padding up to the next symbol's alignment, not part of the kernel
+        while body and body[-1] == "...":
+            body.pop()
     return {k: (bodies.get(k, []), kd) for k, kd in kds.items()}
 
 
@@ -122,11 +130,21 @@ def resources(lib: str, pattern: str):
     return out
 
 
+def opcode_diff(old_lines, new_lines):
+    """'opcode old->new' for every opcode (first token of a disassembly line) whose count differs."""
+    a = collections.Counter(l.split()[0] for l in old_lines if not l.endswith(":"))
+    b = collections.Counter(l.split()[0] for l in new_lines if not l.endswith(":"))
+    return " ".join(f"{op} {a[op]}->{b[op]}" for op in sorted(set(a) | set(b)) if a[op] != b[op])
+
+
 def main(argv):
     if len(argv) == 4 and argv[1] == "--resources":
         for k, v in sorted(resources(argv[2], argv[3]).items()):
             print(k, " ".join(f"{a}={b}" for a, b in v.items()))
         return 0
+    opcodes = len(argv) == 4 and argv[1] == "--opcodes"
+    if opcodes:
+        argv = argv[:1] + argv[2:]
     if len(argv) != 3:
         print(__doc__)
         return 2
@@ -139,8 +157,10 @@ def main(argv):
             print("MISSING", k)
             bad += 1
         elif old[k] != new[k]:
-            what = "disassembly" if old[k][0] != new[k][0] else "descriptor"
+            what = "descriptor" if old[k][1] != new[k][1] else "disassembly"
             print("CHANGED", what, k)
+            if opcodes:
+                print("   ", opcode_diff(old[k][0], new[k][0]) or "(every opcode count equal)")
             bad += 1
     added = sorted(set(new) - set(old))
     for k in added:

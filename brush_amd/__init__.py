@@ -5,6 +5,9 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
 
   render_splats / RenderAux  <- Backend::render_splats, RenderAux (src/lib.rs:20-86)
   render_splats_depth        <- render_splats plus the accumulated depth map (build extension, no reference)
+  render_splats_pose         <- render_splats seen through an explicit world-to-camera matrix, differentiable with
+                                respect to it (build extension; gsplat's v_viewmats is the model)
+  se3_exp / apply_delta / PoseTable  <- camera-frame twists and the per-view pose optimiser (brush_amd/pose.py)
   Camera                     <- camera.rs
   Splats                     <- gaussian_splats.rs (render, from_safetensors / from_ply, from_point_cloud,
                                 from_random_config)
@@ -19,8 +22,8 @@ gfx950).  There is no CPU fallback: importing the compute entry points without t
 library raises.
 """
 from .camera import Camera, fov_to_focal, focal_to_fov  # noqa: F401
-from .render import (RenderAux, render_rgba8, render_splats, render_splats_depth, rgba8_row_pitch,  # noqa: F401
-                     sh_coeffs_for_degree, sh_degree_from_coeffs)
+from .render import (RenderAux, render_rgba8, render_splats, render_splats_depth, render_splats_pose,  # noqa: F401
+                     rgba8_row_pitch, sh_coeffs_for_degree, sh_degree_from_coeffs)
 from .sort import radix_argsort  # noqa: F401
 from .prefix_sum import prefix_sum  # noqa: F401
 from .gaussian_splats import Splats  # noqa: F401
@@ -32,6 +35,8 @@ from . import dataset  # noqa: F401
 # twice).
 _EVAL_NAMES = ("eval_metrics", "eval_stats", "EvalStats", "EvalView")
 _TRAIN_LOOP_NAMES = ("train_scene", "TrainLog", "TrainLoop")
+# brush_amd.pose is imported on first use too: a run without pose refinement never loads it.
+_POSE_NAMES = ("se3_exp", "apply_delta", "PoseTable")
 
 
 def __getattr__(name):
@@ -41,6 +46,9 @@ def __getattr__(name):
     if name in _TRAIN_LOOP_NAMES:
         from . import train_loop as _train_loop
         return getattr(_train_loop, name)
+    if name in _POSE_NAMES:
+        from . import pose as _pose
+        return getattr(_pose, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

@@ -127,6 +127,10 @@ _SYMBOLS = [
     ("brush_render_backward_depth", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
       _P, _P, C.c_size_t, _P]),
+    ("brush_pose_grad_workspace_size", C.c_int, [C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("brush_render_backward_pose", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+      _P, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     ("brush_render_backward_records", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
       C.c_size_t, _P]),
@@ -147,6 +151,9 @@ _SYMBOLS = [
     ("brush_render_backward_adam", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), C.POINTER(BrushAdamConfig), _P, _P, _P, _P, _P, _P, C.c_uint32,
       _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_render_backward_adam_pose", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), C.POINTER(BrushAdamConfig), _P, _P, _P, _P, _P, _P, C.c_uint32,
+      _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     ("brush_reduce_view_records_adam", C.c_int,
      [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.POINTER(BrushAdamConfig), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
       C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),

@@ -156,4 +156,15 @@ hipError_t launch_depth_means_grad(const ViewParams &vp, const uint32_t *num_vis
                                    float *v_means, hipStream_t s);
 hipError_t launch_zero_compact_grads(const uint32_t *num_visible, uint32_t n, float *v_compact, hipStream_t s);
 
+// pose_grad.hip
+// v_viewmat[12] (row-major 3x4, [d L / d W row r | d L / d t[r]]) from the compact-order sums of the visible splats, in
+// float64 partial sums with a fixed order; every word is written.  Runs after the compositing backward and BEFORE
+// launch_project_backward: the fused Adam forms overwrite `means` in place.  pose_ws: pose_grad_workspace_bytes(n).
+size_t pose_grad_workspace_bytes(uint32_t n);
+hipError_t launch_view_grad(const ViewParams &vp, const float *means, const float *log_scales, const float *quats,
+                            const float *raw_opac, const uint32_t *num_visible, uint32_t n,
+                            const uint32_t *global_from_compact, const float *v_compact, const DetSumsArgs &det,
+                            bool has_depth /* v_z of brush_render_backward_depth is present */, bool antialiased,
+                            void *pose_ws, float *v_viewmat, hipStream_t s);
+
 }  // namespace brush

@@ -373,10 +373,12 @@ static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux 
                                 const float *out_img, const float *v_out, float *v_means, float *v_xy,
                                 float *v_scales, float *v_quats, float *v_sh, float *v_opac, const AdamFuse *adam,
                                 void *workspace, size_t workspace_bytes, brush_stream_t stream,
-                                const float *compact_depth = nullptr, const float *v_depth = nullptr) {
+                                const float *compact_depth = nullptr, const float *v_depth = nullptr,
+                                float *v_viewmat = nullptr, void *pose_ws = nullptr) {
     if (!uniforms_ok(h_uniforms) || !aux_ok(h_aux, true) || !out_img || !v_out || !workspace)
         return BRUSH_ERR_INVALID_ARG;
     if ((compact_depth != nullptr) != (v_depth != nullptr) || (v_depth && adam)) return BRUSH_ERR_INVALID_ARG;
+    if ((v_viewmat != nullptr) != (pose_ws != nullptr)) return BRUSH_ERR_INVALID_ARG;
     if (n > 0 && (!means || !log_scales || !quats || !raw_opacity || !v_xy)) return BRUSH_ERR_INVALID_ARG;
     if (n > 0 && !adam && (!v_means || !v_scales || !v_quats || !v_sh || !v_opac)) return BRUSH_ERR_INVALID_ARG;
     const BrushAux &aux = *h_aux;
@@ -408,6 +410,11 @@ static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux 
     if (const int rc = composite_backward(u, aux, out_img, v_out, n, ws, &det, fill, &filled, s, compact_depth, v_depth))
         return rc;
     if (stop_behind(BRUSH_STAGE_BWD_ZERO) || stop_behind(BRUSH_STAGE_RASTERIZE_BWD)) return BRUSH_OK;
+    // camera-pose gradient: ahead of the parameter VJP, whose fused Adam forms overwrite `means` in place
+    if (v_viewmat)
+        BRUSH_HIP_CHECK(launch_view_grad(vp, means, log_scales, quats, raw_opacity, aux.num_visible, n,
+                                         aux.global_from_compact_gid, ws.v_compact, det, v_depth != nullptr,
+                                         (aux.flags & BRUSH_AUX_ANTIALIASED) != 0, pose_ws, v_viewmat, s));
     // GatherGrads + ProjectBackwards fused, dense outputs written once (render.rs:534-594)
     BRUSH_HIP_CHECK(launch_project_backward(vp, means, log_scales, quats, raw_opacity, aux.compact_from_global_gid,
                                             ws.v_compact, v_means, v_xy, v_scales, v_quats, v_sh, v_opac, adam, det,
@@ -487,13 +494,34 @@ extern "C" int brush_render_backward_depth(const BrushUniforms *h_uniforms, cons
                                 compact_depth, v_depth);
 }
 
-extern "C" int brush_render_backward_adam(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
-                                          const BrushAdamConfig *cfg, float *means, float *log_scales,
-                                          const float *quats_fed, float *rotation, float *raw_opacity, float *sh,
-                                          uint32_t n, const float *out_img, const float *v_out, float *v_xy,
-                                          float *moment1, float *moment2, float *next_quats_fed,
-                                          float *grad_2d_accum, float *xy_grad_counts, void *workspace,
-                                          size_t workspace_bytes, brush_stream_t stream) {
+extern "C" int brush_pose_grad_workspace_size(uint32_t n, size_t *bytes) {
+    if (!bytes) return BRUSH_ERR_INVALID_ARG;
+    *bytes = pose_grad_workspace_bytes(n);
+    return BRUSH_OK;
+}
+
+extern "C" int brush_render_backward_pose(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *means,
+                                          const float *log_scales, const float *quats, const float *raw_opacity,
+                                          uint32_t n, const float *out_img, const float *v_out,
+                                          const float *compact_depth, const float *v_depth, float *v_means,
+                                          float *v_xy, float *v_scales, float *v_quats, float *v_sh, float *v_opac,
+                                          void *workspace, size_t workspace_bytes, float *v_viewmat,
+                                          void *pose_workspace, size_t pose_workspace_bytes, brush_stream_t stream) {
+    if (!v_viewmat || !pose_workspace) return BRUSH_ERR_INVALID_ARG;
+    if (pose_workspace_bytes < pose_grad_workspace_bytes(n)) return BRUSH_ERR_WORKSPACE_SMALL;
+    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
+                                v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream,
+                                compact_depth, v_depth, v_viewmat, pose_workspace);
+}
+
+static int render_backward_adam_impl(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                                     const BrushAdamConfig *cfg, float *means, float *log_scales,
+                                     const float *quats_fed, float *rotation, float *raw_opacity, float *sh,
+                                     uint32_t n, const float *out_img, const float *v_out, float *v_xy,
+                                     float *moment1, float *moment2, float *next_quats_fed,
+                                     float *grad_2d_accum, float *xy_grad_counts, void *workspace,
+                                     size_t workspace_bytes, brush_stream_t stream, float *v_viewmat,
+                                     void *pose_ws) {
     if (!cfg || cfg->time == 0 || !h_uniforms || h_uniforms->sh_degree > 4) return BRUSH_ERR_INVALID_ARG;
     if ((reinterpret_cast<uintptr_t>(quats_fed) & 15) != 0) return BRUSH_ERR_INVALID_ARG;
     AdamFuse af{};
@@ -503,7 +531,34 @@ extern "C" int brush_render_backward_adam(const BrushUniforms *h_uniforms, const
         return BRUSH_ERR_INVALID_ARG;
     return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats_fed, raw_opacity, n, out_img, v_out,
                                 nullptr, v_xy, nullptr, nullptr, nullptr, nullptr, &af, workspace, workspace_bytes,
-                                stream);
+                                stream, nullptr, nullptr, v_viewmat, pose_ws);
+}
+
+extern "C" int brush_render_backward_adam(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                                          const BrushAdamConfig *cfg, float *means, float *log_scales,
+                                          const float *quats_fed, float *rotation, float *raw_opacity, float *sh,
+                                          uint32_t n, const float *out_img, const float *v_out, float *v_xy,
+                                          float *moment1, float *moment2, float *next_quats_fed,
+                                          float *grad_2d_accum, float *xy_grad_counts, void *workspace,
+                                          size_t workspace_bytes, brush_stream_t stream) {
+    return render_backward_adam_impl(h_uniforms, h_aux, cfg, means, log_scales, quats_fed, rotation, raw_opacity, sh, n,
+                                     out_img, v_out, v_xy, moment1, moment2, next_quats_fed, grad_2d_accum,
+                                     xy_grad_counts, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+extern "C" int brush_render_backward_adam_pose(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                                               const BrushAdamConfig *cfg, float *means, float *log_scales,
+                                               const float *quats_fed, float *rotation, float *raw_opacity, float *sh,
+                                               uint32_t n, const float *out_img, const float *v_out, float *v_xy,
+                                               float *moment1, float *moment2, float *next_quats_fed,
+                                               float *grad_2d_accum, float *xy_grad_counts, void *workspace,
+                                               size_t workspace_bytes, float *v_viewmat, void *pose_workspace,
+                                               size_t pose_workspace_bytes, brush_stream_t stream) {
+    if (!v_viewmat || !pose_workspace) return BRUSH_ERR_INVALID_ARG;
+    if (pose_workspace_bytes < pose_grad_workspace_bytes(n)) return BRUSH_ERR_WORKSPACE_SMALL;
+    return render_backward_adam_impl(h_uniforms, h_aux, cfg, means, log_scales, quats_fed, rotation, raw_opacity, sh, n,
+                                     out_img, v_out, v_xy, moment1, moment2, next_quats_fed, grad_2d_accum,
+                                     xy_grad_counts, workspace, workspace_bytes, stream, v_viewmat, pose_workspace);
 }
 
 // ---- view-sharded data parallelism (build extension) ------------------------------------------

@@ -28,6 +28,14 @@ __device__ __forceinline__ void quat_to_rotmat_vjp(const float q[4], const Mat3 
 #undef G
 }
 
+// What splat_projection_vjp hands to the camera-pose gradient: with p = W mean + t and T = J W,
+//   v_p   the gradient at p: through the pixel position and through J (a depth gradient v_z is the caller's to add);
+//   J     rows 0..1 of the UNCLAMPED Jacobian (row 2 is zero);
+//   v_T   rows 0..1 of the gradient at T (row 2 meets the zero row of J: it contributes nothing to J^T v_T).
+struct PoseTerms {
+    float v_p[3], J[2][3], v_T[2][3];
+};
+
 // project_backwards.wgsl:59-72
 __device__ __forceinline__ void cov2d_to_conic_vjp(const float conic[3], const float v_conic[3], float o[3]) {
     const float X[2][2] = {{conic[0], conic[1]}, {conic[1], conic[2]}};
@@ -51,11 +59,13 @@ __device__ __forceinline__ void cov2d_to_conic_vjp(const float conic[3], const f
 // AA (BRUSH_AUX_ANTIALIASED): v_comp, the gradient of the opacity factor comp, also enters v_cov2d
 // (project_backwards.wgsl:112-128, disabled in the reference), and *comp_out receives comp, recomputed by the
 // forward's own function from the same calc_cov2d outputs.
-template <bool AA = false>
+// PoseOut (void for the parameter backward: nothing is kept): the camera-pose gradient (pose_grad.hip) asks for the
+// links of the same chain that end at the view matrix, see PoseTerms.
+template <bool AA = false, typename PoseOut = void>
 __device__ __forceinline__ void splat_projection_vjp(
     const ViewParams &vp, const float mean[3], const float scale[3], const float quat[4], const float vxy[2],
     const float vconic[3], float o_mean[3], float o_scale[3], float o_quat[4], float v_comp = 0.0f,
-    float *comp_out = nullptr) {
+    float *comp_out = nullptr, PoseOut *pose = nullptr) {
     const Mat3 W = view_rot(vp);
     float p_view[3];
     to_view(vp, mean, p_view);
@@ -134,6 +144,14 @@ __device__ __forceinline__ void splat_projection_vjp(
 #pragma unroll
     for (int i = 0; i < 3; i++)
         o_mean[i] = vm[i] + ((v_t[0] * W.m[0][i] + v_t[1] * W.m[1][i]) + v_t[2] * W.m[2][i]);
+    if constexpr (!std::is_void<PoseOut>::value) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            pose->v_p[i] = vpj[i] + v_t[i];
+            pose->J[0][i] = J.m[0][i], pose->J[1][i] = J.m[1][i];
+            pose->v_T[0][i] = v_T.m[0][i], pose->v_T[1][i] = v_T.m[1][i];
+        }
+    }
 
     Mat3 two_vVs;
     two_vVs.m[0][0] = 2.0f * c0; two_vVs.m[0][1] = 2.0f * (0.5f * c1); two_vVs.m[0][2] = 2.0f * (0.5f * c2);

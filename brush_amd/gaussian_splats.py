@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 
 from .camera import Camera
-from .render import render_splats, render_splats_depth
+from .render import render_splats, render_splats_depth, render_splats_pose
 
 
 class Splats(torch.nn.Module):
@@ -125,3 +125,14 @@ class Splats(torch.nn.Module):
         norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
         return render_splats_depth(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
                                    self.sh_coeffs, self.raw_opacity, max_intersects, antialiased=antialiased)
+
+    def render_pose(self, camera: Camera, img_size, viewmat, max_intersects=None, antialiased: bool = False,
+                    depth: bool = False):
+        """render() / render_depth() through the explicit world-to-camera matrix `viewmat` (float32 [4,4] CPU tensor),
+        differentiable with respect to it (render.render_splats_pose): (img, aux) or (img, depth, aux)."""
+        self.sync()
+        rot = self.rotation
+        norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
+        return render_splats_pose(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
+                                  self.sh_coeffs, self.raw_opacity, viewmat, max_intersects=max_intersects,
+                                  antialiased=antialiased, depth=depth)

@@ -137,11 +137,16 @@ class RenderAux:
         return s
 
 
-def pack_uniforms(cam: Camera, img_size, sh_degree: int, total_splats: int) -> _lib.BrushUniforms:
-    """render.rs:82-116: tile bounds, viewmat (column-major), focal, centre."""
+def pack_uniforms(cam: Camera, img_size, sh_degree: int, total_splats: int, viewmat=None) -> _lib.BrushUniforms:
+    """render.rs:82-116: tile bounds, viewmat (column-major), focal, centre.  `viewmat`: an explicit row-major 4x4
+    float32 world-to-camera matrix (array-like) used in place of cam.world_to_local(); focal and centre still come
+    from `cam`."""
     w, h = int(img_size[0]), int(img_size[1])
     u = _lib.BrushUniforms()
-    w2l = cam.world_to_local()  # row-major [r][c]
+    if viewmat is None:
+        w2l = cam.world_to_local()  # row-major [r][c]
+    else:
+        w2l = np.asarray(viewmat, dtype=np.float32).reshape(4, 4)
     u.viewmat[:] = [float(w2l[r][c]) for c in range(4) for r in range(4)]
     f = cam.focal((w, h))
     c = cam.center((w, h))
@@ -175,8 +180,9 @@ def _check_inputs(means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity):
 def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, render_u32: bool,
                   max_intersects: Optional[int], row_pitch: Optional[int] = None,
                   deterministic: Optional[bool] = None, expect_backward: Optional[bool] = None, lazy_sh=None,
-                  depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, antialiased: bool = False):
-    """depth: (out_depth [h,w], compact_depth [N]) f32 buffers: render with brush_render_forward_depth (float image).
+                  depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, antialiased: bool = False, viewmat=None):
+    """viewmat: pack_uniforms' explicit world-to-camera matrix (None: the camera's own).
+    depth: (out_depth [h,w], compact_depth [N]) f32 buffers: render with brush_render_forward_depth (float image).
     antialiased: scale each splat's opacity by sqrt(det(S) / det(S + 0.3 I)) (BRUSH_AUX_ANTIALIASED); the backward of
     this render follows aux.flags.
     expect_backward (default: a float image in default mode): allocate the backward's workspace now and let the
@@ -189,7 +195,7 @@ def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, ra
     w, h = int(img_size[0]), int(img_size[1])
     dev = means.device
     sh_degree = sh_degree_from_coeffs(sh_coeffs.shape[1])
-    u = pack_uniforms(cam, (w, h), sh_degree, n)
+    u = pack_uniforms(cam, (w, h), sh_degree, n, viewmat)
     tbx, tby = int(u.tile_bounds[0]), int(u.tile_bounds[1])
     cap = int(max_intersects) if max_intersects is not None else int(l.brush_default_max_intersects(n, w, h))
     cap = max(cap, 1)
@@ -271,8 +277,11 @@ def grad_block_layout(n: int, ncoef: int):
 
 def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, ncoef, out_img, v_out,
                    block: Optional[torch.Tensor] = None,
-                   depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
-    """depth: (compact_depth [N], v_depth [h,w]) of a depth render: brush_render_backward_depth."""
+                   depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                   pose: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """depth: (compact_depth [N], v_depth [h,w]) of a depth render: brush_render_backward_depth.
+    pose: (v_viewmat [12] f32, workspace) device buffers (pose_buffers): brush_render_backward_pose, with or without
+    `depth`; v_viewmat stays on the device, nothing here synchronises."""
     l = _lib.lib()
     n = means.shape[0]
     dev = means.device
@@ -297,7 +306,19 @@ def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, nco
     ws, s = aux.backward_workspace(nbytes.value, dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        if depth is not None:
+        if pose is not None:
+            compact_depth, v_depth = (None, None) if depth is None else (depth[0], depth[1].contiguous())
+            _lib.check(l.brush_render_backward_pose(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
+                                                    quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
+                                                    v_out.data_ptr(),
+                                                    None if depth is None else compact_depth.data_ptr(),
+                                                    None if depth is None else v_depth.data_ptr(),
+                                                    g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
+                                                    g["v_scales"].data_ptr(), g["v_quats"].data_ptr(),
+                                                    g["v_sh"].data_ptr(), g["v_opac"].data_ptr(), ws.data_ptr(),
+                                                    nbytes.value, pose[0].data_ptr(), pose[1].data_ptr(),
+                                                    pose[1].numel(), stream), "brush_render_backward_pose")
+        elif depth is not None:
             compact_depth, v_depth = depth[0], depth[1].contiguous()
             _lib.check(l.brush_render_backward_depth(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
                                                      quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
@@ -428,6 +449,99 @@ def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dumm
               "antialiased": bool(antialiased)}
     out, depth = _RenderSplatsDepthFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder)
     return out, depth, holder["aux"]
+
+
+def pose_buffers(n: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(v_viewmat [12] f32, scratch of brush_pose_grad_workspace_size(n) bytes) for one pose backward."""
+    nbytes = C.c_size_t()
+    _lib.check(_lib.lib().brush_pose_grad_workspace_size(int(n), C.byref(nbytes)), "brush_pose_grad_workspace_size")
+    return (_empty((12,), torch.float32, device),
+            _empty((max(nbytes.value, 8) // 8,), torch.float64, device).view(torch.uint8))
+
+
+def _check_viewmat(viewmat) -> torch.Tensor:
+    if not isinstance(viewmat, torch.Tensor):
+        raise TypeError("viewmat must be a float32 [4,4] CPU tensor")
+    if viewmat.is_cuda:
+        raise ValueError("viewmat must be a CPU tensor: the uniforms are built on the host (the gradient comes back "
+                         "as a CPU tensor too)")
+    if viewmat.shape != (4, 4) or viewmat.dtype != torch.float32:
+        raise ValueError(f"viewmat must be float32 [4,4], got {viewmat.dtype} {tuple(viewmat.shape)}")
+    return viewmat
+
+
+class _RenderSplatsPoseFn(torch.autograd.Function):
+    """render_splats / render_splats_depth with the world-to-camera matrix as a seventh parent (a CPU tensor)."""
+
+    @staticmethod
+    def forward(ctx, means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat, holder):
+        depth = _depth_buffers(means.shape[0], holder["img_size"], means.device) if holder["depth"] else None
+        out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
+                                    raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
+                                    depth=depth, antialiased=holder["antialiased"],
+                                    viewmat=viewmat.detach().numpy())
+        holder["aux"] = aux
+        ctx.u, ctx.aux, ctx.ncoef, ctx.has_depth = u, aux, sh_coeffs.shape[1], depth is not None
+        if depth is not None:
+            ctx.save_for_backward(means, log_scales, quats, raw_opacity, out, depth[1])
+            return out, depth[0]
+        ctx.save_for_backward(means, log_scales, quats, raw_opacity, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, v_output, v_depth=None):
+        if ctx.has_depth:
+            means, log_scales, quats, raw_opacity, out, compact_depth = ctx.saved_tensors
+            v_output = torch.zeros_like(out) if v_output is None else v_output.to(torch.float32)
+            v_depth = torch.zeros(out.shape[:2], dtype=torch.float32, device=out.device) if v_depth is None \
+                else v_depth.to(torch.float32)
+            depth = (compact_depth, v_depth)
+        else:
+            means, log_scales, quats, raw_opacity, out = ctx.saved_tensors
+            v_output, depth = v_output.to(torch.float32), None
+        pose = pose_buffers(means.shape[0], means.device)
+        g, _ = _backward_impl(ctx.u, ctx.aux, means, log_scales, quats, raw_opacity, ctx.ncoef, out, v_output,
+                              depth=depth, pose=pose)
+        v_viewmat = torch.zeros((4, 4), dtype=torch.float32)
+        v_viewmat[:3] = pose[0].cpu().view(3, 4)  # 48 bytes: the op's one synchronisation
+        return g["v_means"], g["v_xy"], g["v_scales"], g["v_quats"], g["v_sh"], g["v_opac"], v_viewmat, None
+
+
+def render_splats_pose(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Optional[torch.Tensor],
+                       log_scales: torch.Tensor, quats: torch.Tensor, sh_coeffs: torch.Tensor,
+                       raw_opacity: torch.Tensor, viewmat: torch.Tensor, *, max_intersects: Optional[int] = None,
+                       deterministic: Optional[bool] = None, antialiased: bool = False, depth: bool = False):
+    """render_splats (or, with `depth`, render_splats_depth) seen through an explicit world-to-camera matrix, and
+    differentiable with respect to it.
+
+    `viewmat` is a float32 [4,4] CPU tensor, row-major, replacing cam.world_to_local(); focal and centre still come
+    from `cam`.  The uniforms are built on the host, so a device tensor is refused.  Returns (img, aux) or
+    (img, depth, aux).  The backward returns the six parent gradients exactly as render_splats does, plus a [4,4] CPU
+    gradient for `viewmat`: rows 0..2 from brush_render_backward_pose, row 3 zero.  It reads those 48 bytes back once
+    per backward: that readback is the op's single synchronisation (SplatTrainer uses a form that leaves them on
+    the device).  Conventions of the gradient (include/brush_hip.h): the Jacobian at the unclamped p_view, no gradient
+    through the SH view direction (above SH degree 0: the gradient with the colours held fixed), piecewise-constant
+    culling and tiling, none for focal / centre."""
+    _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
+    viewmat = _check_viewmat(viewmat)
+    tracked = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad
+        for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat))
+    if not tracked:
+        with torch.no_grad():
+            bufs = _depth_buffers(means.shape[0], img_size, means.device) if depth else None
+            out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, False,
+                                        max_intersects, deterministic=deterministic, expect_backward=False,
+                                        depth=bufs, antialiased=antialiased, viewmat=viewmat.numpy())
+        return (out, bufs[0], aux) if depth else (out, aux)
+    if xy_grad_dummy is None:
+        xy_grad_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
+    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic,
+              "antialiased": bool(antialiased), "depth": bool(depth)}
+    res = _RenderSplatsPoseFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat, holder)
+    if depth:
+        return res[0], res[1], holder["aux"]
+    return res, holder["aux"]
 
 
 def rgba8_row_pitch(width: int) -> int:

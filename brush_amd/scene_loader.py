@@ -53,5 +53,10 @@ class SceneLoader:
 
     def next_batch(self) -> Tuple[object, torch.Tensor]:
         """(SceneView, its image as a uint8 [h,w,3|4] device tensor)."""
+        _, view, image = self.next_indexed()
+        return view, image
+
+    def next_indexed(self) -> Tuple[int, object, torch.Tensor]:
+        """next_batch with the drawn view's index in scene.views in front (the same draw from the same rng)."""
         i = self.next_index()
-        return self.scene.views[i], self.images[i]
+        return i, self.scene.views[i], self.images[i]

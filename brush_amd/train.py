@@ -58,6 +58,15 @@ class TrainConfig:
     # the 2D blur).  Single-view training only: a step given an `exchange` raises.  Refinement still prunes on
     # sigmoid(raw_opacity), as gsplat does.
     antialiased: bool = False
+    # Build extension: per-view camera-pose refinement (brush_amd/pose.py; gsplat's pose_opt is the model).  Each
+    # training view carries a camera-frame twist, stepped by Adam from the view-matrix gradient of the render backward.
+    # Learning rates in radians / world units per step; pose_reg pulls the twists back to the dataset's poses (and
+    # pins the gauge the scene shares with its cameras).  Single-view training only.  DESIGN §8 row 9 has the runs
+    # these defaults come from.
+    pose_opt: bool = False
+    lr_pose_rot: float = 1e-3
+    lr_pose_trans: float = 5e-4
+    pose_reg: float = 1e-6
 
 
 @dataclass
@@ -275,7 +284,7 @@ class SplatTrainer:
 
     def step(self, splats: Splats, camera: Camera, gt_image: torch.Tensor, scene_extent: float = 1.0,
              batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None,
-             loss_out: Optional[torch.Tensor] = None):
+             loss_out: Optional[torch.Tensor] = None, view_index: Optional[int] = None, poses=None):
         """One reference training iteration on one view (batch size is 1 in the reference,
         train.rs:216-219).  `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the
         same bits as its float32 twin; brush_amd.scene_loader keeps the training images on the device in this form).
@@ -283,8 +292,16 @@ class SplatTrainer:
         `batch_views` = world size and either `exchange` = a brush_amd.dist.ViewExchange (per-view gradient
         records all-gathered, summed per splat in view order and fed straight into Adam: every rank applies
         the same bits) or `grad_sync(block, aux)` summing the dense gradient block over views
-        (brush_amd.dist.allreduce_param_grads)."""
+        (brush_amd.dist.allreduce_param_grads).
+        `poses` (a brush_amd.pose.PoseTable) with `view_index`: the view's pending pose update is applied, the view is
+        rendered through its current matrix, the backward also returns the view-matrix gradient (the `_pose` entry
+        points) and hands it to the table without waiting for it.  Not with `exchange` / `grad_sync`."""
         c = self.config
+        if poses is not None:
+            if exchange is not None or grad_sync is not None:
+                raise ValueError("pose refinement is single-view: it cannot be combined with exchange / grad_sync")
+            if view_index is None:
+                raise ValueError("poses needs view_index")
         if c.antialiased and exchange is not None:
             raise ValueError("antialiased training has no data-parallel record path (brush_render_backward_records)")
         h, w = int(gt_image.shape[0]), int(gt_image.shape[1])
@@ -314,8 +331,13 @@ class SplatTrainer:
         if lazy is None:
             self.sync(splats)  # this step reads / steps every SH block: nothing may stay pending
             self._lazy = None
+        viewmat, pose = None, None
+        if poses is not None:
+            poses.apply(view_index)  # the update this view's previous draw left
+            viewmat = poses.viewmat(view_index, camera).numpy()
+            pose = R.pose_buffers(n, means.device)
         pred, aux, u = R._forward_impl(camera, (w, h), means, log_scales, norm_rot, sh, raw_opac, False, None,
-                                       lazy_sh=lazy, antialiased=c.antialiased)
+                                       lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
         loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views, out=loss_out)
@@ -353,19 +375,22 @@ class SplatTrainer:
                 ws, s_aux = aux.backward_workspace(nbytes.value, means.device)
                 v_xy = torch.empty((max(n, 1), 2), dtype=torch.float32, device=means.device)
                 next_rot = torch.empty_like(quats)
-                _lib.check(l.brush_render_backward_adam(C.byref(u), C.byref(s_aux), C.byref(cfg), means.data_ptr(),
-                                                        log_scales.data_ptr(), norm_rot.data_ptr(), quats.data_ptr(),
-                                                        raw_opac.data_ptr(), sh.data_ptr(), n, pred.data_ptr(),
-                                                        v_pred.data_ptr(), v_xy.data_ptr(), self.moment1.data_ptr(),
-                                                        self.moment2.data_ptr(), next_rot.data_ptr(),
-                                                        self.grad_2d_accum.data_ptr() if want_stats else None,
-                                                        self.xy_grad_counts.data_ptr() if want_stats else None,
-                                                        ws.data_ptr(), nbytes.value, stream),
-                           "brush_render_backward_adam")
+                args = (C.byref(u), C.byref(s_aux), C.byref(cfg), means.data_ptr(), log_scales.data_ptr(),
+                        norm_rot.data_ptr(), quats.data_ptr(), raw_opac.data_ptr(), sh.data_ptr(), n, pred.data_ptr(),
+                        v_pred.data_ptr(), v_xy.data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
+                        next_rot.data_ptr(), self.grad_2d_accum.data_ptr() if want_stats else None,
+                        self.xy_grad_counts.data_ptr() if want_stats else None, ws.data_ptr(), nbytes.value)
+                if pose is None:
+                    _lib.check(l.brush_render_backward_adam(*args, stream), "brush_render_backward_adam")
+                else:
+                    _lib.check(l.brush_render_backward_adam_pose(*args, pose[0].data_ptr(), pose[1].data_ptr(),
+                                                                 pose[1].numel(), stream),
+                               "brush_render_backward_adam_pose")
                 self._norm_rot, self._norm_rot_key = next_rot, (quats.data_ptr(), n, splats.rotation._version)
                 self._norm_rot_owner = splats.rotation
             else:
-                grads, block = R._backward_impl(u, aux, means, log_scales, norm_rot, raw_opac, ncoef, pred, v_pred)
+                grads, block = R._backward_impl(u, aux, means, log_scales, norm_rot, raw_opac, ncoef, pred, v_pred,
+                                                pose=pose)
                 if grad_sync is not None:  # view-sharded data parallelism: sum the per-view gradients
                     grad_sync(block, aux)
                 if want_stats:
@@ -388,6 +413,8 @@ class SplatTrainer:
                                              grads["v_sh"].data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
                                              stream),
                            "brush_adam_step")
+        if pose is not None:
+            poses.push(view_index, pose[0])
         self.opt_time += 1
         if lazy is not None:
             self._lazy_pending = True

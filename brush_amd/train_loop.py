@@ -13,7 +13,11 @@ Command line (one line per eval and a last line; --json also writes the eval row
 
     python -m brush_amd.train_loop DATASET [--steps 30000] [--format auto|nerf|colmap] [--max-resolution R]
         [--eval-split-every K] [--eval-every N] [--eval-views V] [--init PLY] [--init-count 10000] [--sh-degree 3]
-        [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased]
+        [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased] [--pose-opt] [--export-cameras CAMS.json]
+
+--pose-opt refines every training view's camera pose beside the splats (TrainConfig.pose_opt, brush_amd/pose.py);
+--export-cameras writes the training views' names and 4x4 world-to-camera matrices as the run leaves them.  Eval views
+carry no correction and are rendered as given.
 
 BRUSH_DETERMINISTIC=1 makes the renders (and so a run with a fixed seed) bitwise repeatable.
 """
@@ -53,10 +57,13 @@ class TrainLog:
     train_seconds: float = 0.0                    # the same without the evals
     image_bytes: int = 0                          # training images resident on the device
     num_splats: int = 0
+    pose_opt: bool = False
+    pose_deltas: Optional[List[List[float]]] = None  # pose_opt: the twist (omega, tau) of every training view
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
-                "image_bytes": self.image_bytes, "num_splats": self.num_splats,
+                "image_bytes": self.image_bytes, "num_splats": self.num_splats, "pose_opt": self.pose_opt,
+                "pose_deltas": self.pose_deltas,
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -116,6 +123,12 @@ class TrainLoop:
                                                     self.device)
         self.loader = SceneLoader(dataset.train, seed, self.device)
         self.trainer = SplatTrainer(self.splats, self.config)
+        self.poses = None
+        if self.config.pose_opt:
+            from .pose import PoseTable
+
+            self.poses = PoseTable(len(self.loader), self.config.lr_pose_rot, self.config.lr_pose_trans,
+                                   self.config.pose_reg)
         self.losses = torch.zeros(self.steps, dtype=torch.float32, device=self.device)
         self.done = 0
         self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes)
@@ -127,10 +140,25 @@ class TrainLoop:
         """One training iteration on a random view; its loss lands in the device log."""
         if self.done >= self.steps:
             raise RuntimeError(f"the run has {self.steps} steps, all done")
-        view, gt = self.loader.next_batch()
-        self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
-                          loss_out=self.losses[self.done:self.done + 1])
+        if self.poses is None:
+            view, gt = self.loader.next_batch()
+            self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
+                              loss_out=self.losses[self.done:self.done + 1])
+        else:
+            i, view, gt = self.loader.next_indexed()
+            self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
+                              loss_out=self.losses[self.done:self.done + 1], view_index=i, poses=self.poses)
         self.done += 1
+
+    def train_viewmats(self) -> List[Tuple[str, np.ndarray]]:
+        """(name, row-major 4x4 float32 world-to-camera matrix) of every training view as the run holds it now: the
+        dataset's matrix, under its refined twist with pose_opt (updates still pending are not in)."""
+        out = []
+        for i, v in enumerate(self.dataset.train.views):
+            m = np.asarray(v.camera.world_to_local(), dtype=np.float32) if self.poses is None \
+                else self.poses.viewmat(i, v.camera).numpy()
+            out.append((v.name, m))
+        return out
 
     def evaluate(self, eval_views: Optional[int] = None) -> Tuple[EvalRow, object]:
         """eval_stats on the dataset's eval views, between steps, on this thread and stream (its docstring's rule);
@@ -154,8 +182,13 @@ class TrainLoop:
         return row, stats
 
     def finish(self) -> Tuple[Splats, TrainLog]:
-        """Applies the trainer's pending SH steps (the returned splats are current) and reads the loss log back."""
+        """Applies the trainer's pending SH steps (the returned splats are current) and the pending pose updates, and
+        reads the loss log back."""
         self.trainer.sync(self.splats)
+        self.log.pose_opt = self.poses is not None
+        if self.poses is not None:
+            self.poses.apply_all()
+            self.log.pose_deltas = self.poses.deltas()
         self.log.losses = self.losses.cpu().numpy()  # synchronises
         self.log.seconds = time.perf_counter() - self._t0
         self.log.train_seconds = self.log.seconds - self._eval_seconds
@@ -166,14 +199,14 @@ class TrainLoop:
 def train_scene(dataset: Dataset, config: Optional[TrainConfig] = None, *, steps: int, init=None,
                 init_count: int = 10000, sh_degree: int = 3, seed: int = 42, eval_every: int = 0,
                 eval_views: Optional[int] = None, on_eval: Optional[Callable] = None,
-                device=None) -> Tuple[Splats, TrainLog]:
+                device=None, on_finish: Optional[Callable] = None) -> Tuple[Splats, TrainLog]:
     """Trains `dataset.train` for `steps` iterations (train_loop.rs) and returns (current splats, TrainLog).
 
     `config` is copied with total_steps = steps and seed = seed.  `init`: Splats to start from, or (positions,
     colours) of a point cloud (e.g. load_dataset's COLMAP points), or None for from_random_config(init_count,
     sh_degree) in random_init_bounds(dataset.train).  `eval_every` > 0: eval_stats at step 0, every `eval_every` steps
     and after the last step, on `eval_views` views (all when None) chosen with the run's rng; `on_eval(row, stats)` is
-    called after each."""
+    called after each; `on_finish(loop)` after the run's finish(), with the TrainLoop (its poses, its views)."""
     if eval_every > 0 and (dataset.eval is None or not dataset.eval.views):
         raise ValueError("eval_every > 0 needs a dataset with eval views")
     loop = TrainLoop(dataset, config, steps=steps, init=init, init_count=init_count, sh_degree=sh_degree, seed=seed,
@@ -190,7 +223,10 @@ def train_scene(dataset: Dataset, config: Optional[TrainConfig] = None, *, steps
         loop.step()
         if eval_every > 0 and (loop.done % eval_every == 0 or loop.done == steps):
             ev()
-    return loop.finish()
+    res = loop.finish()
+    if on_finish is not None:
+        on_finish(loop)
+    return res
 
 
 # ---------------------------------------------------------------------------- command line
@@ -214,6 +250,10 @@ def parser():
     p.add_argument("--json", default=None, help="write the eval rows and the loss curve to this file")
     p.add_argument("--antialiased", action="store_true",
                    help="train (and evaluate) in the antialiased mode: opacity compensation of the 2D blur")
+    p.add_argument("--pose-opt", action="store_true",
+                   help="refine the training views' camera poses beside the splats (eval views are rendered as given)")
+    p.add_argument("--export-cameras", default=None, metavar="FILE.json",
+                   help="write name and 4x4 world-to-camera matrix of every training view after the run")
     return p
 
 
@@ -246,9 +286,16 @@ def main(argv=None) -> int:
         print(f"step {row.step}\tpsnr {row.psnr:.4f}\tssim {row.ssim:.6f}\tsplats {row.splats}\t"
               f"{row.iters_per_s:.1f} it/s", flush=True)
 
-    splats, log = train_scene(data, TrainConfig(antialiased=args.antialiased), steps=args.steps, init=init, init_count=args.init_count,
+    cameras = []
+
+    def on_finish(loop):
+        cameras.extend({"name": name, "world_to_camera": [[float(x) for x in row] for row in m]}
+                       for name, m in loop.train_viewmats())
+
+    splats, log = train_scene(data, TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt), steps=args.steps,
+                              init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,
-                              eval_views=args.eval_views, on_eval=on_eval, device=dev)
+                              eval_views=args.eval_views, on_eval=on_eval, device=dev, on_finish=on_finish)
     final = float(log.losses[-1]) if log.steps else float("nan")
     rate = log.steps / log.train_seconds if log.train_seconds > 0 else float("nan")
     print(f"done: {log.steps} steps in {log.seconds:.1f} s ({rate:.1f} it/s), {log.num_splats} splats, "
@@ -256,6 +303,9 @@ def main(argv=None) -> int:
     if args.export:
         with open(args.export, "wb") as f:
             f.write(splats.to_ply())
+    if args.export_cameras:
+        with open(args.export_cameras, "w") as f:
+            json.dump({"pose_opt": bool(args.pose_opt), "cameras": cameras}, f, indent=1)
     if args.json:
         res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree,
                "antialiased": bool(args.antialiased)}

@@ -275,6 +275,29 @@ int brush_render_backward_depth(const BrushUniforms *h_uniforms, const BrushAux 
                                 float *v_sh, float *v_opac, void *workspace, size_t workspace_bytes,
                                 brush_stream_t stream);
 
+/* ---- camera-pose gradient (build extension) ---------------------------------------------------------------- */
+/* brush_render_backward_depth that also returns the gradient with respect to the camera: v_viewmat[12] (device, f32),
+ * row-major 3x4 = [d L / d W row r | d L / d t[r]] of the world-to-camera transform p = W mean + t that
+ * BrushUniforms::viewmat holds column-major (W[r][c] = viewmat[4 c + r], t[r] = viewmat[12 + r]).  All twelve words
+ * are written on every call, zeros included (no visible splat, n = 0).  compact_depth / v_depth may both be NULL: the
+ * call is then brush_render_backward plus v_viewmat.  The six dense gradients are exactly those of
+ * brush_render_backward / _depth (bit for bit in deterministic mode).
+ * Per visible splat the chain of the parameter backward is followed to its last link (v_p, the gradient at p, and v_T,
+ * the gradient at T = J W): v_t = sum v_p, v_W = sum (v_p mean^T + J^T v_T), summed in float64 in a fixed order with no
+ * atomics: the same inputs give the same words (bit for bit when the compact sums are, i.e. in deterministic mode).
+ * Conventions inherited from that backward: J is taken at the unclamped p_view; no gradient flows through the SH view
+ * direction (mean - viewmat[12..14]), so above SH degree 0 this is the gradient with the colours held fixed; culling and
+ * tile decisions are piecewise constant.  Intrinsics (focal, centre) get no gradient.
+ * pose_workspace: brush_pose_grad_workspace_size(n) bytes (8-byte aligned), scratch, no state between calls.  No
+ * allocation, no synchronisation: the call can be captured into a graph. */
+int brush_pose_grad_workspace_size(uint32_t n, size_t *bytes);
+int brush_render_backward_pose(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *means,
+                               const float *log_scales, const float *quats, const float *raw_opacity, uint32_t n,
+                               const float *out_img, const float *v_out, const float *compact_depth,
+                               const float *v_depth, float *v_means, float *v_xy, float *v_scales, float *v_quats,
+                               float *v_sh, float *v_opac, void *workspace, size_t workspace_bytes, float *v_viewmat,
+                               void *pose_workspace, size_t pose_workspace_bytes, brush_stream_t stream);
+
 /* ---- view-sharded data parallelism (build extension; the reference is single-device, batch 1:
  *      crates/brush-train/src/train.rs:216-219) ------------------------------------------------ */
 /* One process per GPU renders one view of the replicated splats; the step needs the SUM over views of the
@@ -408,6 +431,16 @@ int brush_render_backward_adam(const BrushUniforms *uniforms, const BrushAux *au
                                const float *v_out, float *v_xy, float *moment1, float *moment2,
                                float *next_quats_fed, float *grad_2d_accum, float *xy_grad_counts,
                                void *workspace, size_t workspace_bytes, brush_stream_t stream);
+/* brush_render_backward_adam (eager or cfg->lazy_sh) that also writes the camera-pose gradient v_viewmat[12] of
+ * brush_render_backward_pose, from the means as they were BEFORE this call's update (the pose kernels run ahead of the
+ * kernel that steps them).  Parameters, moments and v_xy come out bit for bit as from brush_render_backward_adam. */
+int brush_render_backward_adam_pose(const BrushUniforms *uniforms, const BrushAux *aux, const BrushAdamConfig *cfg,
+                                    float *means, float *log_scales, const float *quats_fed, float *rotation,
+                                    float *raw_opacity, float *sh, uint32_t n, const float *out_img,
+                                    const float *v_out, float *v_xy, float *moment1, float *moment2,
+                                    float *next_quats_fed, float *grad_2d_accum, float *xy_grad_counts,
+                                    void *workspace, size_t workspace_bytes, float *v_viewmat, void *pose_workspace,
+                                    size_t pose_workspace_bytes, brush_stream_t stream);
 /* brush_reduce_view_records and brush_adam_step in one pass (data-parallel counterpart of
  * brush_render_backward_adam): the summed gradients go straight through the optimizer update, every rank applies
  * the same bits.  means / log_scales / rotation / raw_opacity / sh are updated in place (means is also the source

@@ -38,7 +38,7 @@ hipError_t launch_tile_bin_edges(const uint32_t *sorted_tile_ids, const uint32_t
                                  uint32_t cap, uint32_t *tile_bins, const uint32_t *perm,
                                  const uint32_t *gid_unsorted, uint32_t *gid_sorted, hipStream_t s);
 
-// rasterize.hip
+// rasterize.hip (forward), rasterize_bwd.hip (backward, zero-fill); raster_common.hpp, raster_zero_fill.hpp
 // bin_edges != nullptr: the tile sort's last pass left (~start, end) per tile there (sort_launch: edges) instead of a
 // GetTileBinEdges launch; the kernel decodes them and writes tile_bins (every tile) for the aux / the backward.
 hipError_t launch_rasterize(uint32_t w, uint32_t h, uint32_t tbx, uint32_t tby,

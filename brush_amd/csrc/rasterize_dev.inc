@@ -1,5 +1,5 @@
-// rasterize_dev.inc — every development / test-only hook of the compositing backward, so that rasterize.hip reads as
-// the product kernel.  Included twice by rasterize.hip (BRUSH_DEV_SECTION 1: device helpers inside namespace brush::{};
+// rasterize_dev.inc — every development / test-only hook of the compositing backward, so that rasterize_bwd.hip reads as
+// the product kernel.  Included twice by rasterize_bwd.hip (BRUSH_DEV_SECTION 1: device helpers inside namespace brush::{};
 // 2: the host-side reader at file scope).  In the product build every hook below is the identity:
 //   dev_vva()          vis * v_alpha                 BRUSH_INJECT_VVA_ULPS=<n> (build/libbrush_hip_inject.so, tests/
 //                                                    test_gpu_gate.py): a one-signed error of n eps32 per gradient term

@@ -124,6 +124,39 @@ def test_no_cpu_fallback():
         brush_amd.prefix_sum(torch.zeros(4, dtype=torch.int32))
 
 
+def test_compositing_kernels_static_lds_and_no_spills(lib):
+    """The launcher pads the compositing backward's occupancy with dynamic LDS beside the kernel's static LDS, which
+    rasterize_bwd.hip derives from the kernel's own array types (bwd_static_lds, pinned there by static_asserts to the
+    same literals): the descriptors of the built library must report exactly those bytes, for every instantiation, and
+    neither compositing kernel may spill or use scratch."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("kernel_diff", os.path.join(ROOT, "tools", "kernel_diff.py"))
+    kd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kd)
+    from brush_amd import _lib
+
+    assert lib is not None
+    res = kd.resources(_lib.LIB_PATH, r"k_rasterize_(backward_)?quad")
+    # (deterministic, depth) -> bytes per workgroup of 4 waves; the forward: 4 x 64 records of 48 bytes
+    want_bwd = {(False, False): 39616, (False, True): 43904, (True, False): 23552, (True, True): 24576}
+    seen_bwd, seen_fwd = [], 0
+    for name, r in res.items():
+        assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, name
+        m = re.search(r"k_rasterize_backward_quadILj(\d)ELb([01])ELj4EJ(.*?)EEEv", name)
+        if m:
+            key = (int(m.group(1)), m.group(2) == "1", "DepthGrad" in m.group(3))
+            assert r["group_segment_fixed_size"] == want_bwd[key[1:]], name
+            seen_bwd.append(key)
+        else:
+            assert "k_rasterize_quadILb" in name, name
+            assert r["group_segment_fixed_size"] == 12288, name
+            seen_fwd += 1
+    nq_det = [(1, False), (2, False), (4, False), (4, True)]
+    assert sorted(seen_bwd) == sorted((nq, det, depth) for nq, det in nq_det for depth in (False, True))
+    assert seen_fwd == 3
+
+
 def test_product_and_bench_do_not_import_the_oracle():
     """The oracle is test infrastructure: importing the package, or bench.py up to its timed path
     (synthetic inputs included), must not load it; only bench.py's cpu_baseline leg and the tests do."""

@@ -16,6 +16,8 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
   eval_stats / EvalStats     <- brush-train/src/eval.rs (also `python -m brush_amd.eval`)
   train_scene / TrainLog     <- brush-viewer/src/train_loop.rs (also `python -m brush_amd.train_loop`)
   scene_loader.SceneLoader   <- brush-dataset/src/scene_loader.rs (training images resident on the device as u8)
+  mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
+                                is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
 All compute goes through the C ABI of include/brush_hip.h (libbrush_hip.so, hand-written HIP for
 gfx950).  There is no CPU fallback: importing the compute entry points without the built

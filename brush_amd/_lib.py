@@ -163,6 +163,10 @@ _SYMBOLS = [
     ("brush_normalize_quats", C.c_int, [_P, _P, C.c_uint32, _P]),
     ("brush_refine_stats", C.c_int,
      [C.POINTER(BrushAux), _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    ("brush_mcmc_inject_noise", C.c_int,
+     [_P, _P, _P, _P, C.c_uint32, C.c_float, C.c_size_t, C.c_uint32, _P, _P]),
+    ("brush_mcmc_reg_grads", C.c_int, [_P, _P, C.c_uint32, C.c_float, C.c_float, _P, _P, _P]),
+    ("brush_mcmc_relocation", C.c_int, [_P, _P, _P, C.c_uint32, C.c_float, _P, _P, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

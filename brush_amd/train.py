@@ -67,6 +67,19 @@ class TrainConfig:
     lr_pose_rot: float = 1e-3
     lr_pose_trans: float = 5e-4
     pose_reg: float = 1e-6
+    # Build extension: how the splat count evolves.  "default": refine_splats (clone / split / prune / opacity reset, the
+    # reference's train.rs:395-579).  "mcmc": a fixed budget (brush_amd/mcmc.py; Kheradmand et al. 2024, gsplat's
+    # MCMCStrategy): dead splats (opacity <= mcmc_min_opacity) are relocated onto live ones, the count grows by
+    # mcmc_growth per refinement up to mcmc_cap_max, every step adds noise of mcmc_noise_lr * lr_mean to the means and
+    # the opacity / scale regularisers to the gradients; the optimizer state is kept and opacities are never reset.
+    # Same schedule (warmup_steps, refine_every, max_refine_step).  Single-view training, separate-call optimizer path.
+    strategy: str = "default"
+    mcmc_cap_max: int = 1_000_000
+    mcmc_noise_lr: float = 5e5
+    mcmc_min_opacity: float = 0.005
+    mcmc_opacity_reg: float = 0.01
+    mcmc_scale_reg: float = 0.01
+    mcmc_growth: float = 1.05
 
 
 @dataclass
@@ -132,6 +145,8 @@ def l1_ssim_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_weight: float, windo
 class SplatTrainer:
     def __init__(self, splats: Splats, config: TrainConfig | None = None):
         self.config = config or TrainConfig()
+        if self.config.strategy not in ("default", "mcmc"):
+            raise ValueError(f"TrainConfig.strategy must be 'default' or 'mcmc', got {self.config.strategy!r}")
         dev = splats.means.device
         assert dev.type == "cuda", "brush_amd has no CPU path: the splats must live on the GPU"
         self.iter = 0
@@ -147,7 +162,7 @@ class SplatTrainer:
         # rotation/|rotation| left by the previous fused backward, valid only for the very Parameter object the
         # trainer updated (identity + storage + autograd version); see invalidate_cached_rotation().
         self._norm_rot, self._norm_rot_key, self._norm_rot_owner = None, None, None
-        self.last_refine: Optional[RefineStats] = None
+        self.last_refine = None  # RefineStats, or mcmc.McmcRefineStats with strategy "mcmc"
         self.rng = torch.Generator(device=dev)
         self.rng.manual_seed(self.config.seed)
         # deferred Adam of the SH block: per-splat optimizer time of the stored block, table of per-step constants
@@ -295,8 +310,16 @@ class SplatTrainer:
         (brush_amd.dist.allreduce_param_grads).
         `poses` (a brush_amd.pose.PoseTable) with `view_index`: the view's pending pose update is applied, the view is
         rendered through its current matrix, the backward also returns the view-matrix gradient (the `_pose` entry
-        points) and hands it to the table without waiting for it.  Not with `exchange` / `grad_sync`."""
+        points) and hands it to the table without waiting for it.  Not with `exchange` / `grad_sync`.
+        With TrainConfig.strategy = "mcmc" the step takes the separate-call path (backward, brush_mcmc_reg_grads,
+        brush_adam_step) whatever `fused_backward` says, then brush_mcmc_inject_noise; a refinement step ends in
+        mcmc.refine.  Not with `exchange` / `grad_sync` either."""
         c = self.config
+        use_mcmc = c.strategy == "mcmc"
+        if use_mcmc:
+            from . import mcmc
+            if exchange is not None or grad_sync is not None:
+                raise ValueError("the mcmc strategy is single-view: it cannot be combined with exchange / grad_sync")
         if poses is not None:
             if exchange is not None or grad_sync is not None:
                 raise ValueError("pose refinement is single-view: it cannot be combined with exchange / grad_sync")
@@ -326,7 +349,7 @@ class SplatTrainer:
         self.invalidate_cached_rotation()
         # the optimizer runs inside a kernel that sees which splats the step touches: the single-view fused backward, or
         # the data-parallel reduction of the views' records (both take BrushAdamConfig.lazy_sh)
-        fused = grad_sync is None and (exchange is not None or self.fused_backward)
+        fused = grad_sync is None and (exchange is not None or self.fused_backward) and not use_mcmc
         lazy = self._lazy_state(splats, n, ncoef) if fused else None
         if lazy is None:
             self.sync(splats)  # this step reads / steps every SH block: nothing may stay pending
@@ -343,7 +366,8 @@ class SplatTrainer:
         loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views, out=loss_out)
         do_refine = self.iter < c.max_refine_step and self.iter >= c.warmup_steps and self.iter % c.refine_every == 1
         pre_step = None
-        if do_refine:  # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)
+        # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)
+        if do_refine and not use_mcmc:
             self.sync(splats)  # (the forward above has read the pending state; the clones need the eager values)
             pre_step = {"means": means.clone(), "rotation": quats.clone(), "sh": sh.clone(), "opac": raw_opac.clone(),
                         "scales": log_scales.clone()}
@@ -354,7 +378,7 @@ class SplatTrainer:
                                    float(batch_views))
         if lazy is not None:
             cfg.lazy_sh = C.pointer(lazy)
-        want_stats = self.iter > c.warmup_steps  # housekeeping, train.rs:284-316
+        want_stats = self.iter > c.warmup_steps and not use_mcmc  # housekeeping, train.rs:284-316
         with torch.cuda.device(means.device):
             if exchange is not None:
                 # view-sharded data parallelism: records of this view -> all-gather -> per-splat sum -> Adam
@@ -366,7 +390,7 @@ class SplatTrainer:
                                      self.xy_grad_counts if want_stats else None)
                 self._norm_rot, self._norm_rot_key = next_rot, (quats.data_ptr(), n, splats.rotation._version)
                 self._norm_rot_owner = splats.rotation
-            elif grad_sync is None and self.fused_backward:
+            elif fused:
                 # single view: gradients go straight through the optimizer inside the backward kernel
                 nbytes = C.c_size_t()
                 _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, int(u.sh_degree), int(aux.max_intersects),
@@ -406,6 +430,9 @@ class SplatTrainer:
                         _lib.check(l.brush_refine_stats(C.byref(s_aux), v_xy.data_ptr(), n, w, h,
                                                         self.grad_2d_accum.data_ptr(), self.xy_grad_counts.data_ptr(),
                                                         stream), "brush_refine_stats")
+                if use_mcmc:  # the regularisers go through Adam, as in gsplat
+                    mcmc.reg_grads(raw_opac, log_scales, n, c.mcmc_opacity_reg, c.mcmc_scale_reg, grads["v_opac"],
+                                   grads["v_scales"], stream)
                 _lib.check(l.brush_adam_step(C.byref(cfg), n, R.sh_degree_from_coeffs(ncoef), means.data_ptr(),
                                              log_scales.data_ptr(), quats.data_ptr(), raw_opac.data_ptr(), sh.data_ptr(),
                                              grads["v_means"].data_ptr(), grads["v_scales"].data_ptr(),
@@ -413,6 +440,9 @@ class SplatTrainer:
                                              grads["v_sh"].data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
                                              stream),
                            "brush_adam_step")
+                if use_mcmc and c.mcmc_noise_lr != 0.0:
+                    mcmc.inject_noise(means, log_scales, quats, raw_opac, n,
+                                      c.mcmc_noise_lr * self._lr_mean(scene_extent), c.seed, self.iter, stream)
         if pose is not None:
             poses.push(view_index, pose[0])
         self.opt_time += 1
@@ -420,6 +450,9 @@ class SplatTrainer:
             self._lazy_pending = True
         if do_refine:
             self.sync(splats)  # refinement reads the post-step coefficients of every splat
-        self.last_refine = self.refine_splats(splats, pre_step) if do_refine else None
+        if use_mcmc:
+            self.last_refine = mcmc.refine(self, splats) if do_refine else None
+        else:
+            self.last_refine = self.refine_splats(splats, pre_step) if do_refine else None
         self.iter += 1
         return loss, pred, aux

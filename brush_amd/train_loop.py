@@ -14,6 +14,10 @@ Command line (one line per eval and a last line; --json also writes the eval row
     python -m brush_amd.train_loop DATASET [--steps 30000] [--format auto|nerf|colmap] [--max-resolution R]
         [--eval-split-every K] [--eval-every N] [--eval-views V] [--init PLY] [--init-count 10000] [--sh-degree 3]
         [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased] [--pose-opt] [--export-cameras CAMS.json]
+        [--strategy default|mcmc] [--cap-max 1000000]
+
+--strategy mcmc trains with a fixed splat budget of --cap-max (TrainConfig.strategy, brush_amd/mcmc.py) instead of the
+clone / split / prune refinement.
 
 --pose-opt refines every training view's camera pose beside the splats (TrainConfig.pose_opt, brush_amd/pose.py);
 --export-cameras writes the training views' names and 4x4 world-to-camera matrices as the run leaves them.  Eval views
@@ -254,6 +258,10 @@ def parser():
                    help="refine the training views' camera poses beside the splats (eval views are rendered as given)")
     p.add_argument("--export-cameras", default=None, metavar="FILE.json",
                    help="write name and 4x4 world-to-camera matrix of every training view after the run")
+    p.add_argument("--strategy", choices=("default", "mcmc"), default="default",
+                   help="how the splat count evolves: clone / split / prune, or MCMC relocation with a fixed budget")
+    p.add_argument("--cap-max", type=int, default=TrainConfig.mcmc_cap_max, metavar="N",
+                   help="--strategy mcmc: the splat budget")
     return p
 
 
@@ -268,6 +276,8 @@ def main(argv=None) -> int:
         p.error(f"dataset not found: {args.dataset}")
     if args.steps < 0 or args.eval_every < 0:
         p.error("--steps and --eval-every must be >= 0")
+    if args.cap_max < 1:
+        p.error("--cap-max must be >= 1")
     if args.init is not None and not os.path.isfile(args.init):
         p.error(f"--init file not found: {args.init}")
 
@@ -292,7 +302,9 @@ def main(argv=None) -> int:
         cameras.extend({"name": name, "world_to_camera": [[float(x) for x in row] for row in m]}
                        for name, m in loop.train_viewmats())
 
-    splats, log = train_scene(data, TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt), steps=args.steps,
+    config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
+                         mcmc_cap_max=args.cap_max)
+    splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,
                               eval_views=args.eval_views, on_eval=on_eval, device=dev, on_finish=on_finish)
@@ -308,7 +320,8 @@ def main(argv=None) -> int:
             json.dump({"pose_opt": bool(args.pose_opt), "cameras": cameras}, f, indent=1)
     if args.json:
         res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree,
-               "antialiased": bool(args.antialiased)}
+               "antialiased": bool(args.antialiased), "strategy": args.strategy,
+               "cap_max": int(args.cap_max) if args.strategy == "mcmc" else None}
         res.update(log.to_json())
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)

@@ -470,6 +470,33 @@ int brush_normalize_quats(const float *rotation, float *normalized, uint32_t n, 
 int brush_refine_stats(const BrushAux *h_aux, const float *v_xy, uint32_t n, uint32_t w, uint32_t h,
                        float *grad_2d_accum, float *xy_grad_counts, brush_stream_t stream);
 
+/* ---- MCMC densification (Kheradmand et al. 2024, "3D Gaussian Splatting as Markov Chain Monte Carlo") ---------- */
+/* The three per-splat kernels of the strategy (brush_amd/mcmc.py drives them).  All take a stream, allocate nothing,
+ * never synchronise, use no atomics and can be captured into a graph; a zero count returns BRUSH_OK without touching the
+ * pointers; a NULL or misaligned (floats: 4 bytes, rotation: 16 bytes) argument is BRUSH_ERR_INVALID_ARG. */
+/* means[g] += Sigma_g (xi_g gate_g scale): Sigma = R diag(exp(2 log_scale)) R^T with R from rotation / |rotation|
+ * ((w, x, y, z)), gate = 1 / (1 + exp(-100 ((1 - sigmoid(raw_opacity)) - 0.995))), scale = noise_lr * lr_mean of the step.
+ * xi_g: three standard normals from Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) (seed: 64 bits, carried by the
+ * ABI's one 64-bit scalar type) and counter (g, step, 0x4D434D43, 0): the output words x0..x3 give the uniforms
+ * u_i = ((x_i >> 8) + 0.5) 2^-24 and xi = (r cos(2 pi u1), r sin(2 pi u1), sqrt(-2 ln u2) cos(2 pi u3)), r = sqrt(-2 ln u0).
+ * A step is a pure function of (seed, step, g): repeatable bit for bit, whatever n and the other splats are.
+ * xi_out: NULL, or [n,3] that receives xi.  Only means (and xi_out) is written. */
+int brush_mcmc_inject_noise(float *means, const float *log_scales, const float *rotation, const float *raw_opacity,
+                            uint32_t n, float scale, size_t seed, uint32_t step, float *xi_out, brush_stream_t stream);
+/* Adds the gradients of opacity_reg * mean_g sigmoid(raw_g) and scale_reg * mean_{g,k} exp(log_scale_{g,k}) into the
+ * dense gradient arrays of brush_render_backward, before brush_adam_step consumes them:
+ * v_opac[g] += opacity_reg / n * s (1 - s), v_scales[g,k] += scale_reg / (3 n) * exp(log_scale).  The terms are formed
+ * in float64 and each sum is rounded to f32 once; a weight of 0 leaves its array's bits alone. */
+int brush_mcmc_reg_grads(const float *raw_opacity, const float *log_scales, uint32_t n, float opacity_reg,
+                         float scale_reg, float *v_opac, float *v_scales, brush_stream_t stream);
+/* Eq. 9 of the paper (gsplat's compute_relocation) on m gathered rows, each split into N = clamp(ratio, 1, 51) copies:
+ * with o = sigmoid(raw), o' = 1 - (1 - o)^(1/N) and D = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1),
+ * log_scales_out = log_scales_in + ln(o / D) on all three axes and raw_opacity_out = logit(clamp(o', min_opacity,
+ * 1 - 2^-24)) (the scale term uses the unclamped o').  Computed in float64 (the alternating sum cancels); the outputs
+ * must not alias the inputs.  ratio: [m] int32. */
+int brush_mcmc_relocation(const float *raw_opacity_in, const float *log_scales_in, const int32_t *ratio, uint32_t m,
+                          float min_opacity, float *raw_opacity_out, float *log_scales_out, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

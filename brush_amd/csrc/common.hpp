@@ -92,6 +92,9 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
 __device__ __forceinline__ uint32_t wave_bcast(uint32_t v, uint32_t src) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src);
 }
+__device__ __forceinline__ float wave_bcastf(float v, uint32_t src) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)src));
+}
 // Sum over the wave, in every lane.
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_bcast(wave_inclusive_scan(v), 63u); }
 

@@ -9,17 +9,20 @@ namespace brush {
 
 struct ViewParams;
 
-// project.hip
-// Device work queue of (splat, tile-chunk) items for the balanced tile walks.
+// Device work queue of (splat, tile-chunk) items for the balanced tile walks (tile_walk.hpp: WalkQueue is the
+// kernels' typed view of it, and states what the count pass leaves here for the emit pass).
 struct WalkWs {
-    uint32_t *counter;      // [1]
-    uint32_t *items;        // [capacity * 2]
+    uint32_t *counter;      // [1], zeroed by the cull kernel
+    uint32_t *items;        // [capacity * 2] (compact gid, chunk index)
     uint32_t *chunk_count;  // [capacity]
-    uint32_t *chunk_mask;   // [capacity * 8] (four 64-bit hit masks per item)
+    uint32_t *chunk_mask;   // one 64-bit hit mask per item: [capacity * 2] are used; the workspace carves
+                            //     [capacity * 8] (brush_fwd_workspace_size is observable)
     uint32_t *slot_of;      // [N]
     uint32_t *inline_mask;  // [N * 2] (64-bit hit mask per inline splat)
     uint32_t capacity;
 };
+
+// project.hip
 size_t cull_block_count(uint32_t n);
 hipError_t launch_project_cull(const ViewParams &vp, const BrushUniforms &u, const BrushAux &aux,
                                uint32_t num_tiles, const float *means, const float *log_scales,
@@ -27,9 +30,13 @@ hipError_t launch_project_cull(const ViewParams &vp, const BrushUniforms &u, con
                                uint32_t *key_all, uint32_t *block_counts, uint32_t *keys,
                                uint32_t *gids, uint32_t *bin_edges /* [num_tiles][2], zeroed here */,
                                const WalkWs &walk, const LazySh &lazy /* BrushAux::lazy_sh, or off */, hipStream_t s);
+
+// tile_count.hip (tile_walk.hpp)
 hipError_t launch_project_visible(const ViewParams &vp, const float *proj_global, const uint32_t *num_visible,
                                   uint32_t *global_from_compact, uint32_t *compact_from_global, float *projected,
                                   uint32_t *tiles_hit, const WalkWs &walk, hipStream_t s);
+
+// tile_emit.hip (tile_walk.hpp)
 hipError_t launch_map_intersects(const ViewParams &vp, const float *projected, const uint32_t *cum_tiles_hit,
                                  const uint32_t *num_visible, uint32_t cap, uint32_t *tile_ids, uint32_t *gids,
                                  const WalkWs &walk, hipStream_t s);

@@ -157,6 +157,48 @@ def test_compositing_kernels_static_lds_and_no_spills(lib):
     assert seen_fwd == 3
 
 
+def test_per_splat_forward_kernels_static_lds_and_spills(lib):
+    """The cull / compaction kernels (project.hip) and the two tile passes (tile_count.hip, tile_emit.hip): the static
+    LDS of every kernel, which for the two walk kernels is one LateRing of 4608 bytes per wave (tile_walk.hpp pins the
+    struct's size), every instantiation present, and no spills or scratch anywhere except the two deferred-SH degree-3
+    cull kernels, which are held to exactly the 6 VGPRs / 28 bytes they spill today (recorded, unmeasured)."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("kernel_diff", os.path.join(ROOT, "tools", "kernel_diff.py"))
+    kd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kd)
+    from brush_amd import _lib
+
+    assert lib is not None
+    res = kd.resources(_lib.LIB_PATH, r"k_project_cull|k_cull_scan|k_compact|k_project_visible|k_walk_count|"
+                                      r"k_map_intersects|k_tile_bin_edges")
+    want_lds = {"k_project_cull": 4112, "k_project_visible": 4 * 4608 + 20, "k_walk_count": 4 * 4608,
+                "k_map_intersects": 0, "k_tile_bin_edges": 0, "k_cull_scan": 68}
+    k_aa = 8  # internal.hpp: kAaMode, beside the SH degree in the cull kernel's first template argument
+    seen_cull, seen_compact, seen_other = [], [], []
+    for name, r in res.items():
+        m = re.search(r"\d+(k_[a-z_]+?)(?:ILi(\d+)ELb([01])EEE|ILb([01])EEE|E)", name)
+        assert m, name
+        kernel = m.group(1)
+        spills = (r["vgpr_spill_count"], r["sgpr_spill_count"], r["private_segment_fixed_size"])
+        if kernel == "k_project_cull":
+            dm, lazy = int(m.group(2)), m.group(3) == "1"
+            assert spills == ((6, 0, 28) if lazy and dm & 7 == 3 else (0, 0, 0)), name
+            seen_cull.append((dm, lazy))
+        else:
+            assert spills == (0, 0, 0), name
+            if kernel == "k_compact":
+                assert r["group_segment_fixed_size"] == (80 if m.group(4) == "1" else 64), name
+                seen_compact.append(m.group(4) == "1")
+                continue
+            seen_other.append(kernel)
+        assert r["group_segment_fixed_size"] == want_lds[kernel], name
+    assert sorted(seen_cull) == sorted([(d | aa, False) for d in range(5) for aa in (0, k_aa)] +
+                                       [(d | aa, True) for d in (1, 3) for aa in (0, k_aa)])
+    assert sorted(seen_compact) == [False, True]
+    assert sorted(seen_other) == sorted(set(want_lds) - {"k_project_cull"})
+
+
 def test_product_and_bench_do_not_import_the_oracle():
     """The oracle is test infrastructure: importing the package, or bench.py up to its timed path
     (synthetic inputs included), must not load it; only bench.py's cpu_baseline leg and the tests do."""

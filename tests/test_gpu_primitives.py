@@ -61,7 +61,11 @@ def test_sorting_big_clustered(dev):
 
 @pytest.mark.parametrize("n,bits", [(1, 32), (63, 32), (64, 8), (4096, 13), (4097, 13), (100000, 10), (100000, 4),
                                     (100000, 1), (1 << 20, 32), (3000000, 16), (5000, 0), (65536, 32), (65537, 32),
-                                    (12_000_000, 16)])  # the last one: > 512 tiles of 16384 keys, the 3-launch shape
+                                    (12_000_000, 16),  # > 512 tiles of 16384 keys, the 3-launch shape
+                                    # either side of every shape switch of radix_sort.hip: 131 072 x K keys (K = 1, 2, 4,
+                                    # 16 keys per lane) and 512 x 16 384 (fused / 3-launch)
+                                    (131072, 32), (131073, 32), (262144, 16), (262145, 16), (524288, 32), (524289, 32),
+                                    (2097152, 16), (2097153, 16), (8388608, 16), (8388609, 16)])
 def test_sort_matches_oracle(dev, n, bits):
     """Stability and the 'low 4*ceil(bits/4) bits only' rule vs the oracle, ragged sizes."""
     rng = np.random.default_rng(n + bits)
@@ -83,6 +87,20 @@ def test_sort_partial_count(dev):
         ko, vo = _sort_gpu(keys, vals, n_sort, 32, dev)
         idx = np.argsort(keys[:n_sort].astype(np.int64), kind="stable")
         assert np.array_equal(ko[:n_sort], keys[:n_sort][idx]) and np.array_equal(vo[:n_sort], vals[:n_sort][idx])
+
+
+@pytest.mark.parametrize("n_sort,length", [(100_000, 8_388_608), (3_000_000, 8_388_608), (100_000, 9_000_000)])
+def test_sort_count_far_below_capacity(dev, n_sort, length):
+    """n_sort far below the buffer length: the launch shape follows the capacity (fused up to 512 x 16 384 keys, three
+    launches above), the keys per lane follow the device-side count; the first n_sort pairs are sorted as the oracle
+    sorts them."""
+    rng = np.random.default_rng(n_sort + length)
+    keys = rng.integers(0, 2 ** 32, length, dtype=np.uint64).astype(np.uint32)
+    keys[: n_sort // 2] &= np.uint32(0x1FFF)  # many duplicates: stability
+    vals = np.arange(length, dtype=np.uint32)
+    ko, vo = _sort_gpu(keys, vals, n_sort, 17, dev)
+    rk, rv = O.radix_argsort(keys[:n_sort], vals[:n_sort], bits=17)
+    assert np.array_equal(ko[:n_sort], rk) and np.array_equal(vo[:n_sort], rv)
 
 
 def test_sort_large_properties(dev):
@@ -131,7 +149,8 @@ def test_prefix_sum_reference_vectors(dev):
     assert np.array_equal(_scan_gpu(data, dev), np.cumsum(data, dtype=np.uint64).astype(np.uint32))
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 5, 1023, 1024, 1025, 4099, 1 << 20, (1 << 20) + 7, 20_971_520])
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 1023, 1024, 1025, 4099, 1 << 20, (1 << 20) + 7, 2_097_152, 2_097_153,
+                               20_971_520])
 def test_prefix_sum_sizes(dev, n):
     rng = np.random.default_rng(n)
     data = rng.integers(0, 50, n, dtype=np.uint32)

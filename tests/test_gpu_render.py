@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import binning_check as BK
 from tests import helpers as H
 from tests import margins as M
 
@@ -226,30 +227,81 @@ def _arbiter_report(gpu, orc, tag=""):
     return rep
 
 
-def _assert_forward_parity(gpu, orc, w, h, saturation_flip_frac=0.0, named=False):
+def _assert_forward_parity(gpu, orc, w, h, saturation_flip_frac=0.0, named=False, rounding_flips=False):
     """named: one of the scenes BASELINE.json names (S1, S4 / c1, c2, c3): on top of the conditioning-aware allowance
     the HARD ceilings hold there — max |gpu - f64| <= 1e-4 flat (the north-star's L-inf figure, no allowance), no
     pixel whose allowance exceeds 2e-4 and at most 1e-3 of the pixels above 1.2e-4 (so the allowance cannot quietly
     become the test), at most 2e-3 of the pixels inside a threshold guard band."""
     aux, oa = gpu["aux"], orc["aux"]
-    V, I = int(oa["num_visible"][0]), int(oa["num_intersections"][0])
-    assert aux.read_num_visible() == V
-    assert gpu["u"]["num_visible"] == V  # uniforms_buffer word 25 (render.rs:145-149)
-    assert aux.read_num_intersections() == I
-    assert int(aux.overflow.item()) == int(oa["overflow"])
-    n = oa["global_from_compact_gid"].shape[0]
-    # integer / index outputs: bit-exact
-    assert np.array_equal(_np_u32(aux.global_from_compact_gid)[:n], oa["global_from_compact_gid"])
-    inv = _np_u32(aux.compact_from_global_gid)
-    want_inv = np.full(n, 0xFFFFFFFF, np.uint32)
-    want_inv[oa["global_from_compact_gid"][:V]] = np.arange(V, dtype=np.uint32)
-    assert np.array_equal(inv[:n], want_inv)
-    gp = aux.projected_splats.detach().cpu().numpy()[:V]
-    op = oa["projected_splats"][:V]
-    assert np.array_equal(gp.view(np.uint32), op.view(np.uint32)), "projected splats differ bitwise"
-    assert np.array_equal(_np_u32(aux.cum_tiles_hit)[:n], oa["cum_tiles_hit"])
-    assert np.array_equal(_np_u32(aux.compact_gid_from_isect)[:I], oa["compact_gid_from_isect"][:I])
-    assert np.array_equal(_np_u32(aux.tile_bins), oa["tile_bins"])
+    # integer / index outputs: bit-exact (the checker tests/test_gpu_binning.py shares)
+    V, I = BK.assert_integer_parity(BK.aux_arrays(aux, gpu["u"]["num_visible"]), oa)
+    _assert_pixel_parity(gpu, orc, saturation_flip_frac, named, rounding_flips)
+    return V, I
+
+
+def _rounding_flip_explains(px_gpu, fin_gpu, x, y, oa, tol):
+    """Is the GPU's pixel (rgba and final_index) the f64 composite of its tile's list under decisions that an f32
+    evaluation may take?  The oracle's guard band (flip_risk) is 1e-5 relative around `alpha >= 1/255` and the stop test,
+    the rounding of exp().  It does not know that sigma = 0.5 (a dx^2 + c dy^2) + b dx dy is itself only good to ~3 eps32
+    of its CANCELLING terms (the figure of the pixel allowance above): on a thin tilted splat those terms are thousands
+    of times sigma, alpha moves by 1e-4..1e-2 relative between two admissible f32 evaluations (with or without fused
+    multiply-adds), and an entry at alpha ~ 1/255 is taken by one and dropped by the other.  Here every entry whose
+    test sits inside ITS OWN band, 1e-5 + 3 eps32 (|t1| + |t2| + |t3|), may fall either way, the stop test may move by
+    the band its transmittance has accumulated, and the pixel passes only if one of those executions reproduces the
+    GPU's rgba within the unchanged pixel tolerance AND its final_index exactly."""
+    tbx = oa["tile_bins"].shape[1]
+    r0, r1 = (int(v) for v in oa["tile_bins"].reshape(-1, 2)[(y // 16) * tbx + x // 16])
+    m = r1 - r0
+    if m <= 0:
+        return False
+    p = oa["projected_splats"][oa["compact_gid_from_isect"][r0:r1]].astype(np.float64)
+    dx, dy = p[:, 0] - (x + 0.5), p[:, 1] - (y + 0.5)
+    t1, t2, t3 = 0.5 * p[:, 2] * dx * dx, 0.5 * p[:, 4] * dy * dy, p[:, 3] * dx * dy
+    sg = t1 + t2 + t3
+    band = 1e-5 + 3.0 * EPS32 * (np.abs(t1) + np.abs(t2) + np.abs(t3))  # of sigma (absolute) = of alpha (relative)
+    with np.errstate(over="ignore"):
+        a_u = p[:, 8] * np.exp(-sg)
+    a = np.minimum(0.999, a_u)
+    base = (sg >= 0.0) & (a_u >= 1.0 / 255.0)
+    cand = ((np.abs(a_u * 255.0 - 1.0) <= band) & (sg >= -band)) | ((np.abs(sg) <= band) & (a_u * 255.0 >= 1.0 - band))
+    # entries behind both walks' last entry decide nothing
+    nxt = np.cumprod(np.where(base, 1.0 - a, 1.0))
+    stops = np.flatnonzero(base & (nxt <= 1e-4 * (1.0 - 1e-3)))
+    limit = max(int(stops[0]) if stops.size else m, int(fin_gpu) - r0 + 1)
+    cand = np.flatnonzero(cand[:limit])
+    k = cand.size
+    if k > 4:  # 16 executions at most: far too few to come near an arbitrary colour (measured: k is 0 or 1)
+        return False
+    C = 1 << k
+    passes = np.repeat(base[None, :], C, axis=0)
+    passes[:, cand] ^= ((np.arange(C)[:, None] >> np.arange(k)[None, :]) & 1).astype(bool)
+    fac = np.where(passes, 1.0 - a, 1.0)
+    next_T = np.cumprod(fac, axis=1)
+    T_acc = 1e-5 + np.cumsum(np.where(passes, a / (1.0 - a) * (band + 2.0 * EPS32), 0.0), axis=1)  # relative, of T
+    rel = next_T / 1e-4 - 1.0
+    for c in range(C):
+        # the stop may fall on any passing entry from the first whose next_T can be <= 1e-4 to the first whose must be
+        may = np.flatnonzero(passes[c] & (rel[c] <= T_acc[c]))
+        must = np.flatnonzero(passes[c] & (rel[c] < -T_acc[c]))
+        last = int(must[0]) if must.size else m
+        for first in [int(v) for v in may[may <= last]] + ([m] if last == m else []):
+            live = passes[c].copy()
+            live[first:] = False
+            wgt = np.where(live, a * (next_T[c] / fac[c]), 0.0)
+            rgba = np.append(wgt @ p[:, 5:8], 1.0 - np.where(live, fac[c], 1.0).prod())
+            on = np.flatnonzero(live)
+            fin = r0 + int(on[-1]) if on.size else 0
+            if fin == int(fin_gpu) and np.abs(rgba - px_gpu).max() <= tol:
+                return True
+    return False
+
+
+def _assert_pixel_parity(gpu, orc, saturation_flip_frac=0.0, named=False, rounding_flips=False):
+    """The float half of _assert_forward_parity: the composited image and final_index.
+    rounding_flips (tests/test_gpu_binning.py: clouds with thin tilted splats at high opacity): a pixel that misses the
+    tolerance or the oracle's final_index is first put to _rounding_flip_explains; one it explains joins the guard band,
+    whose total is held to the bound the oracle's own band has.  Everything else is asserted as without it."""
+    aux, oa = gpu["aux"], orc["aux"]
     # composite: 1e-4 L-inf away from pixels where a threshold test is within 1e-5 of flipping, measured against the
     # f64 evaluation of the same walk (same f32 records, same decisions).  Where the quadratic form cancels heavily (a
     # splat tens of thousands of pixels wide, far off-screen) any f32 evaluation of sigma is off by up to ~3 eps32 of
@@ -270,6 +322,18 @@ def _assert_forward_parity(gpu, orc, w, h, saturation_flip_frac=0.0, named=False
     exact, cond = O.rasterize_forward_f64(gpu["u"], oa)
     gpu_err = np.abs(gpu["out"].astype(np.float64) - exact).max(axis=2)
     tol = PIX_TOL + 3.0 * EPS32 * cond
+    if rounding_flips:
+        fin_gpu = _np_u32(aux.final_index)
+        suspects = ((gpu_err > tol) | (fin_gpu != oa["final_index"])) & ~risk
+        explained = np.zeros_like(risk)
+        if suspects.mean() < 2e-3 + 2e-5 * depth or suspects.sum() <= 16:  # more than a guard band may hold: no excuse
+            for y, x in zip(*np.nonzero(suspects)):
+                explained[y, x] = _rounding_flip_explains(gpu["out"][y, x].astype(np.float64), fin_gpu[y, x], int(x),
+                                                          int(y), oa, float(tol[y, x]))
+        print(f"pixels off the tolerance or the oracle's final_index outside its guard band: {int(suspects.sum())}, "
+              f"of which an f32 rounding of sigma at a threshold explains {int(explained.sum())}")
+        risk = risk | explained
+        assert risk.mean() < 2e-3 + 2e-5 * depth or risk.sum() <= 16, (float(risk.mean()), depth)
     over = (gpu_err > tol) & ~risk
     assert not over.any(), (f"{int(over.sum())} pixels: max |gpu - f64| {gpu_err[over].max()} (allowance {tol[over].min()}); "
                             f"max |gpu - f32 restatement| {diff[~risk].max()}")
@@ -301,7 +365,6 @@ def _assert_forward_parity(gpu, orc, w, h, saturation_flip_frac=0.0, named=False
         assert differ.mean() <= saturation_flip_frac
         if differ.any():
             assert gpu["out"][..., 3][differ].min() >= 0.9998 and orc["out"][..., 3][differ].min() >= 0.9998
-    return V, I
 
 
 # Gradient tolerance, element by element, every term tied to a mechanism (no "fraction of the tensor's maximum"):

@@ -8,6 +8,8 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
   render_splats_pose         <- render_splats seen through an explicit world-to-camera matrix, differentiable with
                                 respect to it (build extension; gsplat's v_viewmats is the model)
   se3_exp / apply_delta / PoseTable  <- camera-frame twists and the per-view pose optimiser (brush_amd/pose.py)
+  apply_exposure / ExposureTable     <- per-view affine colour maps (exposure compensation) and their device-side
+                                optimiser (brush_amd/exposure.py; build extension, 3DGS's exposure compensation)
   Camera                     <- camera.rs
   Splats                     <- gaussian_splats.rs (render, from_safetensors / from_ply, from_point_cloud,
                                 from_random_config)
@@ -39,6 +41,7 @@ _EVAL_NAMES = ("eval_metrics", "eval_stats", "EvalStats", "EvalView")
 _TRAIN_LOOP_NAMES = ("train_scene", "TrainLog", "TrainLoop")
 # brush_amd.pose is imported on first use too: a run without pose refinement never loads it.
 _POSE_NAMES = ("se3_exp", "apply_delta", "PoseTable")
+_EXPOSURE_NAMES = ("apply_exposure", "ExposureTable")
 
 
 def __getattr__(name):
@@ -51,6 +54,9 @@ def __getattr__(name):
     if name in _POSE_NAMES:
         from . import pose as _pose
         return getattr(_pose, name)
+    if name in _EXPOSURE_NAMES:
+        from . import exposure as _exposure
+        return getattr(_exposure, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

@@ -85,6 +85,14 @@ class BrushAdamConfig(C.Structure):
     ]
 
 
+class BrushExposureAdam(C.Structure):
+    """Hyper-parameters of brush_exposure_backward_adam (include/brush_hip.h: BrushExposureAdam)."""
+    _fields_ = [
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("reg", C.c_float),
+        ("time", C.c_uint32),
+    ]
+
+
 class BrushError(RuntimeError):
     pass
 
@@ -167,6 +175,11 @@ _SYMBOLS = [
      [_P, _P, _P, _P, C.c_uint32, C.c_float, C.c_size_t, C.c_uint32, _P, _P]),
     ("brush_mcmc_reg_grads", C.c_int, [_P, _P, C.c_uint32, C.c_float, C.c_float, _P, _P, _P]),
     ("brush_mcmc_relocation", C.c_int, [_P, _P, _P, C.c_uint32, C.c_float, _P, _P, _P]),
+    ("brush_exposure_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("brush_exposure_forward", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    ("brush_exposure_backward", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_exposure_backward_adam", C.c_int,
+     [_P, _P, C.POINTER(BrushExposureAdam), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

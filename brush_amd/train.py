@@ -67,6 +67,16 @@ class TrainConfig:
     lr_pose_rot: float = 1e-3
     lr_pose_trans: float = 5e-4
     pose_reg: float = 1e-6
+    # Build extension: per-view exposure compensation (brush_amd/exposure.py; the 3DGS trainer's exposure compensation
+    # is the model, gsplat's app_opt covers the same ground).  Each training view carries a 3x4 affine colour map,
+    # applied to the render before the loss and stepped by Adam on the device.  lr_exposure decays by the total factor
+    # lr_exposure_decay over `total_steps` (formed like the mean rate); exposure_reg pulls the maps back to the identity
+    # (and pins the gain the scene shares with its exposures).  Single-view training only; eval views are rendered as
+    # given.  DESIGN §8 row 11.
+    exposure_opt: bool = False
+    lr_exposure: float = 1e-2
+    lr_exposure_decay: float = 0.1
+    exposure_reg: float = 1e-6
     # Build extension: how the splat count evolves.  "default": refine_splats (clone / split / prune / opacity reset, the
     # reference's train.rs:395-579).  "mcmc": a fixed budget (brush_amd/mcmc.py; Kheradmand et al. 2024, gsplat's
     # MCMCStrategy): dead splats (opacity <= mcmc_min_opacity) are relocated onto live ones, the count grows by
@@ -297,9 +307,15 @@ class SplatTrainer:
         gamma = c.lr_mean_decay ** (1.0 / c.total_steps)
         return c.lr_mean * gamma ** self.iter * scene_extent
 
+    def _lr_exposure(self) -> float:
+        c = self.config
+        gamma = c.lr_exposure_decay ** (1.0 / c.total_steps)
+        return c.lr_exposure * gamma ** self.iter
+
     def step(self, splats: Splats, camera: Camera, gt_image: torch.Tensor, scene_extent: float = 1.0,
              batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None,
-             loss_out: Optional[torch.Tensor] = None, view_index: Optional[int] = None, poses=None):
+             loss_out: Optional[torch.Tensor] = None, view_index: Optional[int] = None, poses=None,
+             exposures=None):
         """One reference training iteration on one view (batch size is 1 in the reference,
         train.rs:216-219).  `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the
         same bits as its float32 twin; brush_amd.scene_loader keeps the training images on the device in this form).
@@ -311,6 +327,10 @@ class SplatTrainer:
         `poses` (a brush_amd.pose.PoseTable) with `view_index`: the view's pending pose update is applied, the view is
         rendered through its current matrix, the backward also returns the view-matrix gradient (the `_pose` entry
         points) and hands it to the table without waiting for it.  Not with `exchange` / `grad_sync`.
+        `exposures` (a brush_amd.exposure.ExposureTable) with `view_index`: the view's affine colour map is applied to
+        the render, the loss is taken on the result, and the table's backward returns the gradient at the raw render
+        (which every backward path then receives beside the raw render) and steps the view's map, all on the device.
+        Not with `exchange` / `grad_sync`.  The step still returns the raw render.
         With TrainConfig.strategy = "mcmc" the step takes the separate-call path (backward, brush_mcmc_reg_grads,
         brush_adam_step) whatever `fused_backward` says, then brush_mcmc_inject_noise; a refinement step ends in
         mcmc.refine.  Not with `exchange` / `grad_sync` either."""
@@ -325,6 +345,11 @@ class SplatTrainer:
                 raise ValueError("pose refinement is single-view: it cannot be combined with exchange / grad_sync")
             if view_index is None:
                 raise ValueError("poses needs view_index")
+        if exposures is not None:
+            if exchange is not None or grad_sync is not None:
+                raise ValueError("exposure compensation is single-view: it cannot be combined with exchange / grad_sync")
+            if view_index is None:
+                raise ValueError("exposures needs view_index")
         if c.antialiased and exchange is not None:
             raise ValueError("antialiased training has no data-parallel record path (brush_render_backward_records)")
         h, w = int(gt_image.shape[0]), int(gt_image.shape[1])
@@ -363,7 +388,13 @@ class SplatTrainer:
                                        lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
-        loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views, out=loss_out)
+        if exposures is None:
+            loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views,
+                                        out=loss_out)
+        else:  # the loss sees the compensated image; the backward below sees the raw render and the gradient at it
+            loss, v_out = l1_ssim_loss(exposures.forward(view_index, pred), gt_image, c.ssim_weight,
+                                       c.ssim_window_size, 1.0 / batch_views, out=loss_out)
+            v_pred = exposures.backward_step(view_index, pred, v_out, lr=self._lr_exposure())
         do_refine = self.iter < c.max_refine_step and self.iter >= c.warmup_steps and self.iter % c.refine_every == 1
         pre_step = None
         # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)

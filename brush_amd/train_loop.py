@@ -14,7 +14,7 @@ Command line (one line per eval and a last line; --json also writes the eval row
     python -m brush_amd.train_loop DATASET [--steps 30000] [--format auto|nerf|colmap] [--max-resolution R]
         [--eval-split-every K] [--eval-every N] [--eval-views V] [--init PLY] [--init-count 10000] [--sh-degree 3]
         [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased] [--pose-opt] [--export-cameras CAMS.json]
-        [--strategy default|mcmc] [--cap-max 1000000]
+        [--strategy default|mcmc] [--cap-max 1000000] [--exposure-opt] [--export-exposures EXP.json]
 
 --strategy mcmc trains with a fixed splat budget of --cap-max (TrainConfig.strategy, brush_amd/mcmc.py) instead of the
 clone / split / prune refinement.
@@ -22,6 +22,10 @@ clone / split / prune refinement.
 --pose-opt refines every training view's camera pose beside the splats (TrainConfig.pose_opt, brush_amd/pose.py);
 --export-cameras writes the training views' names and 4x4 world-to-camera matrices as the run leaves them.  Eval views
 carry no correction and are rendered as given.
+
+--exposure-opt fits a 3x4 affine colour map per training view beside the splats (TrainConfig.exposure_opt,
+brush_amd/exposure.py); --export-exposures writes the training views' names and maps as the run leaves them.  Eval views
+are rendered as given.
 
 BRUSH_DETERMINISTIC=1 makes the renders (and so a run with a fixed seed) bitwise repeatable.
 """
@@ -63,11 +67,13 @@ class TrainLog:
     num_splats: int = 0
     pose_opt: bool = False
     pose_deltas: Optional[List[List[float]]] = None  # pose_opt: the twist (omega, tau) of every training view
+    exposure_opt: bool = False
+    exposures: Optional[List[List[float]]] = None    # exposure_opt: the 3x4 map (12 floats, row-major) of every view
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
                 "image_bytes": self.image_bytes, "num_splats": self.num_splats, "pose_opt": self.pose_opt,
-                "pose_deltas": self.pose_deltas,
+                "pose_deltas": self.pose_deltas, "exposure_opt": self.exposure_opt, "exposures": self.exposures,
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -133,6 +139,12 @@ class TrainLoop:
 
             self.poses = PoseTable(len(self.loader), self.config.lr_pose_rot, self.config.lr_pose_trans,
                                    self.config.pose_reg)
+        self.exposures = None
+        if self.config.exposure_opt:
+            from .exposure import ExposureTable
+
+            self.exposures = ExposureTable(len(self.loader), self.device, self.config.lr_exposure,
+                                           self.config.exposure_reg)
         self.losses = torch.zeros(self.steps, dtype=torch.float32, device=self.device)
         self.done = 0
         self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes)
@@ -144,14 +156,15 @@ class TrainLoop:
         """One training iteration on a random view; its loss lands in the device log."""
         if self.done >= self.steps:
             raise RuntimeError(f"the run has {self.steps} steps, all done")
-        if self.poses is None:
+        if self.poses is None and self.exposures is None:
             view, gt = self.loader.next_batch()
             self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
                               loss_out=self.losses[self.done:self.done + 1])
         else:
             i, view, gt = self.loader.next_indexed()
             self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
-                              loss_out=self.losses[self.done:self.done + 1], view_index=i, poses=self.poses)
+                              loss_out=self.losses[self.done:self.done + 1], view_index=i, poses=self.poses,
+                              exposures=self.exposures)
         self.done += 1
 
     def train_viewmats(self) -> List[Tuple[str, np.ndarray]]:
@@ -193,6 +206,9 @@ class TrainLoop:
         if self.poses is not None:
             self.poses.apply_all()
             self.log.pose_deltas = self.poses.deltas()
+        self.log.exposure_opt = self.exposures is not None
+        if self.exposures is not None:
+            self.log.exposures = self.exposures.exposures()
         self.log.losses = self.losses.cpu().numpy()  # synchronises
         self.log.seconds = time.perf_counter() - self._t0
         self.log.train_seconds = self.log.seconds - self._eval_seconds
@@ -258,6 +274,10 @@ def parser():
                    help="refine the training views' camera poses beside the splats (eval views are rendered as given)")
     p.add_argument("--export-cameras", default=None, metavar="FILE.json",
                    help="write name and 4x4 world-to-camera matrix of every training view after the run")
+    p.add_argument("--exposure-opt", action="store_true",
+                   help="fit a per-view affine colour map (exposure / white balance) beside the splats")
+    p.add_argument("--export-exposures", default=None, metavar="FILE.json",
+                   help="write name and 3x4 exposure map of every training view after the run")
     p.add_argument("--strategy", choices=("default", "mcmc"), default="default",
                    help="how the splat count evolves: clone / split / prune, or MCMC relocation with a fixed budget")
     p.add_argument("--cap-max", type=int, default=TrainConfig.mcmc_cap_max, metavar="N",
@@ -298,12 +318,17 @@ def main(argv=None) -> int:
 
     cameras = []
 
+    exposures = []
+
     def on_finish(loop):
+        if loop.exposures is not None:
+            exposures.extend({"name": v.name, "exposure": [[float(x) for x in row] for row in m]}
+                             for v, m in zip(loop.dataset.train.views, loop.exposures.matrices()))
         cameras.extend({"name": name, "world_to_camera": [[float(x) for x in row] for row in m]}
                        for name, m in loop.train_viewmats())
 
     config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
-                         mcmc_cap_max=args.cap_max)
+                         mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt)
     splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,
@@ -318,6 +343,12 @@ def main(argv=None) -> int:
     if args.export_cameras:
         with open(args.export_cameras, "w") as f:
             json.dump({"pose_opt": bool(args.pose_opt), "cameras": cameras}, f, indent=1)
+    if args.export_exposures:
+        if not args.exposure_opt:
+            exposures.extend({"name": v.name, "exposure": [[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0],
+                                                           [0.0, 0.0, 1.0, 0.0]]} for v in data.train.views)
+        with open(args.export_exposures, "w") as f:
+            json.dump({"exposure_opt": bool(args.exposure_opt), "views": exposures}, f, indent=1)
     if args.json:
         res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree,
                "antialiased": bool(args.antialiased), "strategy": args.strategy,

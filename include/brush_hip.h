@@ -497,6 +497,39 @@ int brush_mcmc_reg_grads(const float *raw_opacity, const float *log_scales, uint
 int brush_mcmc_relocation(const float *raw_opacity_in, const float *log_scales_in, const int32_t *ratio, uint32_t m,
                           float min_opacity, float *raw_opacity_out, float *log_scales_out, brush_stream_t stream);
 
+/* ---- per-view exposure compensation (build extension; 3DGS's exposure compensation, gsplat's app_opt) ---------- */
+/* A training view carries a 3x4 affine colour map E = [A | b], 12 floats row-major, identity [I | 0] at the start.  For
+ * a rendered pixel p = (r, g, b, alpha) (premultiplied, as brush_render_forward writes it):
+ *   out_c = A[c][0] r + A[c][1] g + A[c][2] b + alpha b_c  (c = 0..2)      out_alpha = alpha
+ * which is A c + b on the un-premultiplied colour, premultiplied again: an uncovered pixel stays empty.  The loss is
+ * taken on `out`; with v' = d L / d out the backward returns
+ *   v_pred[k] = sum_c A[c][k] v'_c,  v_pred[alpha] = v'_alpha + sum_c b_c v'_c,
+ *   v_exposure[c][k] = sum_pixels v'_c p_k (k = 0..2),  v_exposure[c][3] = sum_pixels v'_c alpha
+ * the latter summed in float64 (every product exact) in a fixed order with no atomics and rounded to f32 once: the same
+ * inputs give the same twelve words, all written on every call.  Images are [h][w][4] f32, 16-byte aligned, w h in
+ * [1, 2^28).  `out` may not alias `pred` (the compositing backward needs the raw render); `v_pred` may alias `v_out`.
+ * workspace: brush_exposure_workspace_size(w, h) bytes (8-byte aligned, at most 48 KiB), scratch, no state between
+ * calls.  All pointers are device pointers except `cfg`.  No allocation, no synchronisation: graph-capturable. */
+int brush_exposure_workspace_size(uint32_t w, uint32_t h, size_t *bytes);
+int brush_exposure_forward(const float *pred, const float *exposure, uint32_t w, uint32_t h, float *out,
+                           brush_stream_t stream);
+int brush_exposure_backward(const float *pred, const float *v_out, const float *exposure, uint32_t w, uint32_t h,
+                            float *v_pred, float *v_exposure, void *workspace, size_t workspace_bytes,
+                            brush_stream_t stream);
+/* brush_exposure_backward that also takes the Adam step of this view's E inside its last kernel: with G the float64
+ * sums above, g = G + reg (E - [I|0]) (the coupled penalty), m1 = beta1 m1 + (1 - beta1) g, m2 = beta2 m2 + (1 - beta2) g^2,
+ * E -= lr (m1 / (1 - beta1^time)) / (sqrt(m2 / (1 - beta2^time)) + epsilon), evaluated in float64 from the stored f32
+ * words, each stored word rounded once.  time: the view's 1-based step count (0 is rejected).  exposure / moment1 /
+ * moment2: this view's 12 words each, updated in place; v_pred uses E as it was before the step; v_exposure is written
+ * as by brush_exposure_backward (before the penalty). */
+typedef struct BrushExposureAdam {
+    float lr, beta1, beta2, epsilon, reg;
+    uint32_t time;
+} BrushExposureAdam;
+int brush_exposure_backward_adam(const float *pred, const float *v_out, const BrushExposureAdam *cfg, uint32_t w,
+                                 uint32_t h, float *v_pred, float *exposure, float *moment1, float *moment2,
+                                 float *v_exposure, void *workspace, size_t workspace_bytes, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

@@ -18,6 +18,8 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
   eval_stats / EvalStats     <- brush-train/src/eval.rs (also `python -m brush_amd.eval`)
   train_scene / TrainLog     <- brush-viewer/src/train_loop.rs (also `python -m brush_amd.train_loop`)
   scene_loader.SceneLoader   <- brush-dataset/src/scene_loader.rs (training images resident on the device as u8)
+  depth_loss / depth_loss_into       <- depth supervision: a fused L1 depth (or disparity) loss on the renderer's
+                                depth output (brush_amd/depth_loss.py; build extension, 3DGS's depth regulariser)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -33,11 +35,14 @@ from .prefix_sum import prefix_sum  # noqa: F401
 from .gaussian_splats import Splats  # noqa: F401
 from .train import SplatTrainer, TrainConfig  # noqa: F401
 from . import dataset  # noqa: F401
+# (imported eagerly and after the submodule: the package attribute `depth_loss` is the function, the module stays
+# reachable as `from brush_amd.depth_loss import ...`)
+from .depth_loss import depth_loss, depth_loss_into  # noqa: F401
 
 # brush_amd.eval and brush_amd.train_loop are imported on first use: importing them here would load the module before
 # `python -m brush_amd.eval` / `python -m brush_amd.train_loop` runs it as __main__ (runpy then warns that it is loaded
 # twice).
-_EVAL_NAMES = ("eval_metrics", "eval_stats", "EvalStats", "EvalView")
+_EVAL_NAMES = ("eval_metrics", "eval_stats", "EvalStats", "EvalView", "eval_depth", "DepthEvalView")
 _TRAIN_LOOP_NAMES = ("train_scene", "TrainLog", "TrainLoop")
 # brush_amd.pose is imported on first use too: a run without pose refinement never loads it.
 _POSE_NAMES = ("se3_exp", "apply_delta", "PoseTable")

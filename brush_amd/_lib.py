@@ -15,6 +15,10 @@ AUX_ACCUM_ZEROED = 2   # BrushAux.flags: BRUSH_AUX_ACCUM_ZEROED (backward only)
 AUX_ANTIALIASED = 4    # BrushAux.flags: BRUSH_AUX_ANTIALIASED (opacity compensation for the 2D blur)
 EVAL_GT_U8 = 0         # brush_eval_metrics / brush_l1_ssim_loss_gt gt_dtype: BRUSH_EVAL_GT_U8
 EVAL_GT_F32 = 1        # BRUSH_EVAL_GT_F32
+DEPTH_LOSS_DEPTH = 0   # BrushDepthLoss.mode: BRUSH_DEPTH_LOSS_DEPTH
+DEPTH_LOSS_DISPARITY = 1  # BRUSH_DEPTH_LOSS_DISPARITY
+DEPTH_GT_U16 = 0       # BrushDepthLoss.gt_dtype: BRUSH_DEPTH_GT_U16
+DEPTH_GT_F32 = 1       # BRUSH_DEPTH_GT_F32
 UNIFORM_WORDS = 28
 NUM_VISIBLE_WORD = 25
 TILE_WIDTH = 16
@@ -90,6 +94,14 @@ class BrushExposureAdam(C.Structure):
     _fields_ = [
         ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("reg", C.c_float),
         ("time", C.c_uint32),
+    ]
+
+
+class BrushDepthLoss(C.Structure):
+    """Per-call configuration of brush_depth_loss (include/brush_hip.h: BrushDepthLoss)."""
+    _fields_ = [
+        ("weight", C.c_float), ("scale", C.c_float), ("offset", C.c_float), ("alpha_min", C.c_float),
+        ("mode", C.c_uint32), ("gt_dtype", C.c_uint32),
     ]
 
 
@@ -180,6 +192,9 @@ _SYMBOLS = [
     ("brush_exposure_backward", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
     ("brush_exposure_backward_adam", C.c_int,
      [_P, _P, C.POINTER(BrushExposureAdam), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_depth_loss_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("brush_depth_loss", C.c_int,
+     [_P, _P, _P, C.POINTER(BrushDepthLoss), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

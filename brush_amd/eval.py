@@ -8,6 +8,7 @@ Command line (prints one line per view, then the means):
 
     python -m brush_amd.eval SPLATS DATASET [--format auto|nerf|colmap] [--eval-split-every K]
                              [--max-resolution R] [--num-frames K] [--seed S] [--window 11] [--json OUT]
+                             [--depth-metrics] [--depth-mode depth|disparity]
 """
 from __future__ import annotations
 
@@ -129,6 +130,44 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
                       for k, (i, (r, a)) in enumerate(zip(idx, rendered))])
 
 
+@dataclass
+class DepthEvalView:
+    """One view of eval_depth.  `mean_abs_error`: mean |r| over the view's valid pixels (nan when none is valid), r as
+    brush_depth_loss defines it for the mode; `valid_fraction`: valid pixels / all pixels."""
+    view: object  # dataset.SceneView
+    mean_abs_error: float
+    valid_fraction: float
+
+
+def eval_depth(splats, scene, *, mode: str = "depth", alpha_min: float = 0.5,
+               antialiased: bool = False) -> List[DepthEvalView]:
+    """The depth error of `splats` on every view of `scene` (a dataset.Scene) that has a depth map: the view is
+    rendered with its depth output at the map's size (Splats.render_depth under no_grad) and scored by
+    brush_depth_loss, metrics only, with weight 1 against the map as stored (uint16 or float32, with the view's
+    depth_scale / depth_offset).  The kernel's mean runs over all pixels and its second word is the valid fraction, so
+    the mean over the valid pixels is stats[0] / stats[1].  The statistics of all views are read back once, after the
+    last view.  Views without a depth map are skipped; the result is empty when no view has one."""
+    from .depth_loss import depth_loss_into
+
+    views = [v for v in scene.views if getattr(v, "depth", None) is not None]
+    dev = splats.means.device
+    stats = torch.empty((len(views), 2), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for row, v in enumerate(views):
+            d = np.require(v.depth, requirements=["C", "W"])
+            if d.ndim != 2 or d.dtype not in (np.uint16, np.float32):
+                raise ValueError(f"{v.name}: the view's depth map must be uint16 or float32 [h,w], got {d.dtype} {d.shape}")
+            h, w = int(d.shape[0]), int(d.shape[1])
+            img, depth, _ = splats.render_depth(v.camera, (w, h), antialiased=antialiased)
+            _, st = depth_loss_into(img, depth, torch.from_numpy(d).to(dev), None, weight=1.0,
+                                    scale=float(v.depth_scale), offset=float(v.depth_offset), alpha_min=alpha_min,
+                                    mode=mode, want_v_depth=False)
+            stats[row].copy_(st)
+    host = stats.cpu().numpy().astype(np.float64)  # the one readback
+    return [DepthEvalView(v, float(host[k, 0] / host[k, 1]) if host[k, 1] > 0 else float("nan"), float(host[k, 1]))
+            for k, v in enumerate(views)]
+
+
 def write_depth_maps(splats, views, out_dir: str):
     """For each view: <stem>_depth.npy, the accumulated depth D = sum T alpha z (Splats.render_depth), and
     <stem>_depth_norm.npy, D / max(alpha, 1e-6) with 0 where alpha is 0; both f32 [h,w].  Returns the written paths."""
@@ -194,6 +233,11 @@ def parser():
     p.add_argument("--antialiased", action="store_true",
                    help="render in the antialiased mode (opacity compensation of the 2D blur), e.g. for splats "
                         "trained with it")
+    p.add_argument("--depth-metrics", action="store_true",
+                   help="also score the rendered depth of every eval view that has a depth map: mean absolute error "
+                        "over the valid pixels and the valid fraction (eval_depth)")
+    p.add_argument("--depth-mode", choices=("depth", "disparity"), default="depth",
+                   help="--depth-metrics: compare depth / alpha, or alpha / depth (maps of inverse depths)")
     return p
 
 
@@ -222,11 +266,24 @@ def main(argv=None) -> int:
     print(f"mean ({len(stats.samples)} views)\tpsnr {stats.mean_psnr():.4f}\tssim {stats.mean_ssim():.6f}")
     if args.depth_dir:
         write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir)
+    depth_rows = None
+    if args.depth_metrics:
+        depth_rows = eval_depth(splats, data.eval, mode=args.depth_mode, antialiased=args.antialiased)
+        for r in depth_rows:
+            print(f"{r.view.name}\tdepth_mae {r.mean_abs_error:.6f}\tvalid {r.valid_fraction:.4f}")
+        mae = float(np.mean([r.mean_abs_error for r in depth_rows])) if depth_rows else float("nan")
+        print(f"mean ({len(depth_rows)} views with depth)\tdepth_mae {mae:.6f}")
     if args.json:
         res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "window": args.window,
                "antialiased": bool(args.antialiased),
                "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in stats.samples],
                "mean_psnr": stats.mean_psnr(), "mean_ssim": stats.mean_ssim()}
+        if depth_rows is not None:
+            res["depth_mode"] = args.depth_mode
+            res["depth_views"] = [{"name": r.view.name, "mean_abs_error": r.mean_abs_error,
+                                   "valid_fraction": r.valid_fraction} for r in depth_rows]
+            res["mean_depth_abs_error"] = (float(np.mean([r.mean_abs_error for r in depth_rows])) if depth_rows
+                                           else float("nan"))
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
     return 0

@@ -5,7 +5,8 @@ The reference spawns a task that picks `rng.gen_range(0..len)` views, turns each
 construction, as the u8 it was decoded as (alpha kept when present, as image_to_tensor keeps it); the loss kernels read
 u8 directly (brush_l1_ssim_loss_gt).  `next_batch` then only draws an index: no host<->device traffic, no
 synchronisation and nothing left for a prefetch thread to do.  Batch size is 1, as the reference asserts
-(train.rs:216-219).
+(train.rs:216-219).  A view's depth map (build extension, SceneView.depth) is uploaded the same way, once and in the
+dtype it is stored in; brush_depth_loss reads uint16 and float32 directly.
 """
 from __future__ import annotations
 
@@ -38,18 +39,31 @@ class SceneLoader:
         self.scene_extent = scene_extent(scene)
         self.rng = np.random.default_rng(seed)
         self.images = []
+        self.depths = []  # parallel to images: the view's depth map as stored (uint16 / float32 [h,w]), or None
         for v in scene.views:
             img = np.require(v.image, requirements=["C"])
             if img.ndim != 3 or img.dtype != np.uint8 or img.shape[2] not in (3, 4):
                 raise ValueError(f"{v.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
             self.images.append(torch.from_numpy(np.array(img, copy=True)).to(self.device))  # the one upload
-        self.total_bytes = int(sum(t.numel() * t.element_size() for t in self.images))
+            depth = getattr(v, "depth", None)
+            if depth is not None:
+                if depth.dtype not in (np.uint16, np.float32) or tuple(depth.shape) != tuple(img.shape[:2]):
+                    raise ValueError(f"{v.name}: the view's depth map must be uint16 or float32 [h,w] = "
+                                     f"{tuple(img.shape[:2])}, got {depth.dtype} {depth.shape}")
+                depth = torch.from_numpy(np.array(depth, copy=True, order="C")).to(self.device)  # as stored, once
+            self.depths.append(depth)
+        self.total_bytes = int(sum(t.numel() * t.element_size() for t in self.images + self.depths if t is not None))
 
     def __len__(self) -> int:
         return len(self.images)
 
     def next_index(self) -> int:
         return int(self.rng.integers(0, len(self.images)))
+
+    def depth(self, i: int) -> Optional[torch.Tensor]:
+        """View i's depth map on the device (uint16 or float32 [h,w], as stored; the view's depth_scale / depth_offset
+        turn it into scene units), or None when the view has none."""
+        return self.depths[i]
 
     def next_batch(self) -> Tuple[object, torch.Tensor]:
         """(SceneView, its image as a uint8 [h,w,3|4] device tensor)."""

@@ -90,6 +90,17 @@ class TrainConfig:
     mcmc_opacity_reg: float = 0.01
     mcmc_scale_reg: float = 0.01
     mcmc_growth: float = 1.05
+    # Build extension: depth supervision (brush_amd/depth_loss.py; the 3DGS trainer's depth regulariser and gsplat's
+    # depth_loss are the models).  A step given a view's depth map adds depth_weight * mean over all pixels of
+    # |rendered - target| to the loss, on depth / alpha ("depth") or alpha / depth ("disparity": the map then holds
+    # inverse depths), over the pixels with a measurement and alpha >= depth_alpha_min ("mostly covered": a
+    # hyper-parameter default, not a measured number).  The weight goes from depth_weight to depth_weight_final (None:
+    # constant) exponentially over `total_steps`, formed like the exposure rate.  0 (the default) is the step without the
+    # option, bit for bit.  Single-view training, separate-call optimizer path.  DESIGN §8 row 12.
+    depth_weight: float = 0.0
+    depth_weight_final: Optional[float] = None
+    depth_mode: str = "depth"
+    depth_alpha_min: float = 0.5
 
 
 @dataclass
@@ -157,6 +168,10 @@ class SplatTrainer:
         self.config = config or TrainConfig()
         if self.config.strategy not in ("default", "mcmc"):
             raise ValueError(f"TrainConfig.strategy must be 'default' or 'mcmc', got {self.config.strategy!r}")
+        if self.config.depth_mode not in ("depth", "disparity"):
+            raise ValueError(f"TrainConfig.depth_mode must be 'depth' or 'disparity', got {self.config.depth_mode!r}")
+        if self.config.depth_weight < 0 or (self.config.depth_weight_final or 0.0) < 0:
+            raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
         dev = splats.means.device
         assert dev.type == "cuda", "brush_amd has no CPU path: the splats must live on the GPU"
         self.iter = 0
@@ -312,10 +327,18 @@ class SplatTrainer:
         gamma = c.lr_exposure_decay ** (1.0 / c.total_steps)
         return c.lr_exposure * gamma ** self.iter
 
+    def _depth_weight(self) -> float:
+        c = self.config
+        if c.depth_weight_final is None or c.depth_weight <= 0.0 or c.depth_weight_final <= 0.0:
+            return c.depth_weight  # (an exponential ramp needs two positive ends)
+        gamma = (c.depth_weight_final / c.depth_weight) ** (1.0 / c.total_steps)
+        return c.depth_weight * gamma ** self.iter
+
     def step(self, splats: Splats, camera: Camera, gt_image: torch.Tensor, scene_extent: float = 1.0,
              batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None,
              loss_out: Optional[torch.Tensor] = None, view_index: Optional[int] = None, poses=None,
-             exposures=None):
+             exposures=None, gt_depth: Optional[torch.Tensor] = None, depth_scale: float = 1.0,
+             depth_offset: float = 0.0):
         """One reference training iteration on one view (batch size is 1 in the reference,
         train.rs:216-219).  `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the
         same bits as its float32 twin; brush_amd.scene_loader keeps the training images on the device in this form).
@@ -333,9 +356,19 @@ class SplatTrainer:
         Not with `exchange` / `grad_sync`.  The step still returns the raw render.
         With TrainConfig.strategy = "mcmc" the step takes the separate-call path (backward, brush_mcmc_reg_grads,
         brush_adam_step) whatever `fused_backward` says, then brush_mcmc_inject_noise; a refinement step ends in
-        mcmc.refine.  Not with `exchange` / `grad_sync` either."""
+        mcmc.refine.  Not with `exchange` / `grad_sync` either.
+        `gt_depth` (the view's depth map, [h,w] uint16 or float32 on the device, read as raw * depth_scale +
+        depth_offset; scene_loader keeps it there as stored) with a positive current TrainConfig.depth_weight: the view
+        is rendered with its depth output, brush_depth_loss adds the depth term's alpha gradient into the colour loss's
+        gradient and the term itself into the step's loss, and the backward carries the depth gradient
+        (brush_render_backward_depth); the step then takes the separate-call path whatever `fused_backward` says.  With
+        gt_depth None or a zero weight the step is the one without the option.  Not with `exchange` / `grad_sync`."""
         c = self.config
         use_mcmc = c.strategy == "mcmc"
+        if gt_depth is not None and (exchange is not None or grad_sync is not None):
+            raise ValueError("depth supervision is single-view: it cannot be combined with exchange / grad_sync")
+        depth_w = self._depth_weight() if gt_depth is not None else 0.0
+        use_depth = depth_w > 0.0
         if use_mcmc:
             from . import mcmc
             if exchange is not None or grad_sync is not None:
@@ -374,7 +407,7 @@ class SplatTrainer:
         self.invalidate_cached_rotation()
         # the optimizer runs inside a kernel that sees which splats the step touches: the single-view fused backward, or
         # the data-parallel reduction of the views' records (both take BrushAdamConfig.lazy_sh)
-        fused = grad_sync is None and (exchange is not None or self.fused_backward) and not use_mcmc
+        fused = grad_sync is None and (exchange is not None or self.fused_backward) and not use_mcmc and not use_depth
         lazy = self._lazy_state(splats, n, ncoef) if fused else None
         if lazy is None:
             self.sync(splats)  # this step reads / steps every SH block: nothing may stay pending
@@ -384,8 +417,9 @@ class SplatTrainer:
             poses.apply(view_index)  # the update this view's previous draw left
             viewmat = poses.viewmat(view_index, camera).numpy()
             pose = R.pose_buffers(n, means.device)
+        depth_bufs = R._depth_buffers(n, (w, h), means.device) if use_depth else None  # (depth map, compact depth)
         pred, aux, u = R._forward_impl(camera, (w, h), means, log_scales, norm_rot, sh, raw_opac, False, None,
-                                       lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat)
+                                       lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat, depth=depth_bufs)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
         if exposures is None:
@@ -395,6 +429,13 @@ class SplatTrainer:
             loss, v_out = l1_ssim_loss(exposures.forward(view_index, pred), gt_image, c.ssim_weight,
                                        c.ssim_window_size, 1.0 / batch_views, out=loss_out)
             v_pred = exposures.backward_step(view_index, pred, v_out, lr=self._lr_exposure())
+        depth_grad = None
+        if use_depth:  # on the raw render: alpha gradient into v_pred, the term into the step's loss, no read-back
+            from .depth_loss import depth_loss_into
+            v_depth, _ = depth_loss_into(pred, depth_bufs[0], gt_depth, v_pred, weight=depth_w / batch_views,
+                                         scale=depth_scale, offset=depth_offset, alpha_min=c.depth_alpha_min,
+                                         mode=c.depth_mode, loss_accum=loss)
+            depth_grad = (depth_bufs[1], v_depth)
         do_refine = self.iter < c.max_refine_step and self.iter >= c.warmup_steps and self.iter % c.refine_every == 1
         pre_step = None
         # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)
@@ -445,7 +486,7 @@ class SplatTrainer:
                 self._norm_rot_owner = splats.rotation
             else:
                 grads, block = R._backward_impl(u, aux, means, log_scales, norm_rot, raw_opac, ncoef, pred, v_pred,
-                                                pose=pose)
+                                                depth=depth_grad, pose=pose)
                 if grad_sync is not None:  # view-sharded data parallelism: sum the per-view gradients
                     grad_sync(block, aux)
                 if want_stats:

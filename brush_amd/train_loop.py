@@ -15,6 +15,12 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--eval-split-every K] [--eval-every N] [--eval-views V] [--init PLY] [--init-count 10000] [--sh-degree 3]
         [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased] [--pose-opt] [--export-cameras CAMS.json]
         [--strategy default|mcmc] [--cap-max 1000000] [--exposure-opt] [--export-exposures EXP.json]
+        [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
+
+--depth-weight W > 0 supervises the rendered depth with the dataset's depth maps (nerfstudio's depth_file_path; COLMAP's
+depths/<image stem>.png|.npy): W times the mean absolute difference of depth / alpha (--depth-mode disparity: alpha /
+depth, for maps that hold inverse depths) is added to the loss of every view that has a map (TrainConfig.depth_weight,
+brush_amd/depth_loss.py).  --depth-weight-final W2 moves the weight exponentially from W to W2 over the run.
 
 --strategy mcmc trains with a fixed splat budget of --cap-max (TrainConfig.strategy, brush_amd/mcmc.py) instead of the
 clone / split / prune refinement.
@@ -145,6 +151,8 @@ class TrainLoop:
 
             self.exposures = ExposureTable(len(self.loader), self.device, self.config.lr_exposure,
                                            self.config.exposure_reg)
+        # depth supervision: the drawn view's resident depth map goes with the step (views without one train as before)
+        self._depth = self.config.depth_weight > 0.0 and any(d is not None for d in self.loader.depths)
         self.losses = torch.zeros(self.steps, dtype=torch.float32, device=self.device)
         self.done = 0
         self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes)
@@ -156,15 +164,19 @@ class TrainLoop:
         """One training iteration on a random view; its loss lands in the device log."""
         if self.done >= self.steps:
             raise RuntimeError(f"the run has {self.steps} steps, all done")
-        if self.poses is None and self.exposures is None:
+        if self.poses is None and self.exposures is None and not self._depth:
             view, gt = self.loader.next_batch()
             self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
                               loss_out=self.losses[self.done:self.done + 1])
         else:
             i, view, gt = self.loader.next_indexed()
+            depth = self.loader.depth(i) if self._depth else None
             self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
-                              loss_out=self.losses[self.done:self.done + 1], view_index=i, poses=self.poses,
-                              exposures=self.exposures)
+                              loss_out=self.losses[self.done:self.done + 1],
+                              view_index=i if (self.poses is not None or self.exposures is not None) else None,
+                              poses=self.poses, exposures=self.exposures, gt_depth=depth,
+                              depth_scale=getattr(view, "depth_scale", 1.0),
+                              depth_offset=getattr(view, "depth_offset", 0.0))
         self.done += 1
 
     def train_viewmats(self) -> List[Tuple[str, np.ndarray]]:
@@ -282,6 +294,12 @@ def parser():
                    help="how the splat count evolves: clone / split / prune, or MCMC relocation with a fixed budget")
     p.add_argument("--cap-max", type=int, default=TrainConfig.mcmc_cap_max, metavar="N",
                    help="--strategy mcmc: the splat budget")
+    p.add_argument("--depth-weight", type=float, default=0.0, metavar="W",
+                   help="supervise the rendered depth with the dataset's depth maps, with this weight (0: off)")
+    p.add_argument("--depth-weight-final", type=float, default=None, metavar="W",
+                   help="move the depth weight exponentially from --depth-weight to this value over the run")
+    p.add_argument("--depth-mode", choices=("depth", "disparity"), default="depth",
+                   help="compare depth / alpha, or alpha / depth (the maps then hold inverse depths)")
     return p
 
 
@@ -298,12 +316,17 @@ def main(argv=None) -> int:
         p.error("--steps and --eval-every must be >= 0")
     if args.cap_max < 1:
         p.error("--cap-max must be >= 1")
+    if args.depth_weight < 0 or (args.depth_weight_final is not None and args.depth_weight_final < 0):
+        p.error("--depth-weight and --depth-weight-final must be >= 0")
     if args.init is not None and not os.path.isfile(args.init):
         p.error(f"--init file not found: {args.init}")
 
     data, points = load_dataset(args.dataset, args.format, args.max_resolution, args.eval_split_every)  # host only
     if not data.train.views:
         print(f"{args.dataset}: the dataset has no training views", file=sys.stderr)
+        return 2
+    if args.depth_weight > 0 and not any(v.depth is not None for v in data.train.views):
+        print(f"{args.dataset}: --depth-weight needs training views with depth maps", file=sys.stderr)
         return 2
     if args.eval_every > 0 and (data.eval is None or not data.eval.views):
         print(f"{args.dataset}: --eval-every needs eval views (try --eval-split-every K)", file=sys.stderr)
@@ -328,7 +351,8 @@ def main(argv=None) -> int:
                        for name, m in loop.train_viewmats())
 
     config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
-                         mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt)
+                         mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt, depth_weight=args.depth_weight,
+                         depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode)
     splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,

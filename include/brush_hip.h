@@ -530,6 +530,43 @@ int brush_exposure_backward_adam(const float *pred, const float *v_out, const Br
                                  uint32_t h, float *v_pred, float *exposure, float *moment1, float *moment2,
                                  float *v_exposure, void *workspace, size_t workspace_bytes, brush_stream_t stream);
 
+/* ---- depth supervision (build extension; the 3DGS trainer's depth regulariser, gsplat's depth_loss) ------------- */
+/* An L1 loss between the rendered expected depth and a per-view depth map, and both of its gradients, in one pass.
+ * Per pixel p: a = pred[p].w, the alpha of the raw render pred [h][w][4] f32 (brush_render_forward_depth's image);
+ * D = depth[p], its accumulated depth sum T alpha z, [h][w] f32; raw = target[p], [h][w] u16 (BRUSH_DEPTH_GT_U16, e.g.
+ * a 16-bit PNG kept on the device as decoded) or f32 (BRUSH_DEPTH_GT_F32), and t = raw * scale + offset (an f32
+ * multiply, then an f32 add: a millimetre u16 map is scale = 0.001).  The target is given in the space of the loss
+ * (a depth for BRUSH_DEPTH_LOSS_DEPTH, an inverse depth for BRUSH_DEPTH_LOSS_DISPARITY).  A pixel is valid when the
+ * target is present (u16: raw != 0; f32: raw finite and > 0), t > 0, D > 0 and a >= alpha_min.  With
+ * c = (float)(weight / (w h)) formed in double precision, g = c sign(r), sign(0) = 0, and IEEE divisions:
+ *   BRUSH_DEPTH_LOSS_DEPTH      d = D / a,  r = d - t,  v_D = g / a,         v_a = -(g d) / a
+ *   BRUSH_DEPTH_LOSS_DISPARITY  q = a / D,  r = q - t,  v_D = -(g q) / D,    v_a = g / D
+ * The loss is c sum_valid |r|: the mean runs over ALL w h pixels, as the 3DGS trainer's depth term does, not over the
+ * valid ones; that is what lets the gradient be written in the pass that computes the sum (the valid fraction is
+ * returned beside it for callers who want the other mean).
+ * Outputs: v_depth [h][w] (NULL to skip) is written at every pixel, 0 where invalid.  v_a is ADDED into v_pred[p].w,
+ * v_pred [h][w][4] (NULL to skip) being the gradient the colour loss has already written (stream order); its r, g, b
+ * words and every word of an invalid pixel keep their bits.  stats[0] = (float)((double) c * sum (double) |r|), the sum
+ * taken in float64 in a fixed order without atomics; stats[1] = (float)(valid pixels / (w h)), from an exact count.  A
+ * non-NULL loss_accum receives *loss_accum += stats[0] (one f32 add), so a per-step loss log holds the total.
+ * pred / v_pred: 16-byte aligned and distinct; w h in [1, 2^28); alpha_min > 0; any other mode / gt_dtype, a NULL
+ * required pointer or a misaligned one is BRUSH_ERR_INVALID_ARG, checked before any GPU call.  workspace:
+ * brush_depth_loss_workspace_size(w, h) bytes (8-byte aligned, at most 16 KiB), scratch, no state between calls.  All
+ * pointers are device pointers except `cfg`.  No allocation, no synchronisation: graph-capturable; the same inputs give
+ * the same bits on every call. */
+#define BRUSH_DEPTH_LOSS_DEPTH 0u
+#define BRUSH_DEPTH_LOSS_DISPARITY 1u
+#define BRUSH_DEPTH_GT_U16 0u
+#define BRUSH_DEPTH_GT_F32 1u
+typedef struct BrushDepthLoss {
+    float weight, scale, offset, alpha_min;
+    uint32_t mode, gt_dtype;
+} BrushDepthLoss;
+int brush_depth_loss_workspace_size(uint32_t w, uint32_t h, size_t *bytes);
+int brush_depth_loss(const float *pred, const float *depth, const void *target, const BrushDepthLoss *cfg, uint32_t w,
+                     uint32_t h, float *v_depth, float *v_pred, float *stats, float *loss_accum, void *workspace,
+                     size_t workspace_bytes, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

@@ -20,6 +20,10 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
   scene_loader.SceneLoader   <- brush-dataset/src/scene_loader.rs (training images resident on the device as u8)
   depth_loss / depth_loss_into       <- depth supervision: a fused L1 depth (or disparity) loss on the renderer's
                                 depth output (brush_amd/depth_loss.py; build extension, 3DGS's depth regulariser)
+  area_resize / nearest_resize / downscaled_size  <- device image pyramids: an exact integer area filter for the u8
+                                images and a nearest pick for depth maps (brush_amd/pyramid.py; build extension,
+                                nerfstudio's resolution schedule and Mip-Splatting's multi-scale eval are the users:
+                                TrainConfig.downscale_schedule, SceneLoader.set_downscale, eval_stats(downscale=))
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -38,6 +42,7 @@ from . import dataset  # noqa: F401
 # (imported eagerly and after the submodule: the package attribute `depth_loss` is the function, the module stays
 # reachable as `from brush_amd.depth_loss import ...`)
 from .depth_loss import depth_loss, depth_loss_into  # noqa: F401
+from .pyramid import area_resize, downscaled_size, nearest_resize  # noqa: F401
 
 # brush_amd.eval and brush_amd.train_loop are imported on first use: importing them here would load the module before
 # `python -m brush_amd.eval` / `python -m brush_amd.train_loop` runs it as __main__ (runpy then warns that it is loaded

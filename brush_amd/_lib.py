@@ -195,6 +195,8 @@ _SYMBOLS = [
     ("brush_depth_loss_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     ("brush_depth_loss", C.c_int,
      [_P, _P, _P, C.POINTER(BrushDepthLoss), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_area_resize_u8", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P]),
+    ("brush_nearest_resize", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

@@ -8,7 +8,11 @@ Command line (prints one line per view, then the means):
 
     python -m brush_amd.eval SPLATS DATASET [--format auto|nerf|colmap] [--eval-split-every K]
                              [--max-resolution R] [--num-frames K] [--seed S] [--window 11] [--json OUT]
-                             [--depth-metrics] [--depth-mode depth|disparity]
+                             [--depth-metrics] [--depth-mode depth|disparity] [--downscale 1,2,4,8]
+
+--downscale 1,2,4,8 is Mip-Splatting's multi-scale protocol: the views are scored once per scale, rendered at 1 / scale
+of their size against the image area-filtered to that size on the device (brush_amd/pyramid.py); one block of lines per
+scale, and a `scales` list in --json.
 """
 from __future__ import annotations
 
@@ -97,11 +101,13 @@ def select_views(num_views: int, num_frames: Optional[int] = None,
 
 
 def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np.random.Generator] = None,
-               window: int = 11, keep_aux: bool = False, antialiased: bool = False) -> EvalStats:
+               window: int = 11, keep_aux: bool = False, antialiased: bool = False, downscale: int = 1) -> EvalStats:
     """eval.rs:27-77: render each selected view of `scene` (a dataset.Scene, e.g. Dataset.eval) at its image's size
     through Splats.render under no_grad and score it against the image's RGB, uploaded as uint8, with eval_metrics.
     The metrics of all views go into one [V,3] device tensor that is read back once, after the last view.
     `antialiased`: render in the antialiased mode (render.render_splats), e.g. splats trained in it.
+    `downscale` = f > 1 scores at 1 / f: the uploaded image goes through pyramid.area_resize and the view is rendered at
+    pyramid.downscaled_size of its size (the camera is a field of view: it holds at any size); 1 is the call without it.
 
     One deviation from the reference: `aux` is kept only with keep_aux=True, because a RenderAux holds the
     intersection lists of its view (hundreds of MB for a large scene).
@@ -109,6 +115,9 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
     Trainer state: rendering goes through Splats.render, which applies the SH optimizer steps a SplatTrainer has
     deferred (Splats.sync), exactly as any render or trainer.sync() does; nothing else of the trainer changes.  Call it
     from the trainer's thread and stream, between step() calls."""
+    from .pyramid import area_resize, check_factor
+
+    downscale = check_factor(downscale)
     views = scene.views
     idx = select_views(len(views), num_frames, rng)
     dev = splats.means.device
@@ -122,6 +131,9 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
                 raise ValueError(f"{v.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
             h, w = int(img.shape[0]), int(img.shape[1])
             gt = torch.from_numpy(img).to(dev)  # u8, as the reference uploads to_rgb8() (the kernel divides by 255)
+            if downscale > 1:
+                gt = area_resize(gt, factor=downscale)
+                h, w = int(gt.shape[0]), int(gt.shape[1])
             pred, aux = splats.render(v.camera, (w, h), False, antialiased=antialiased)
             eval_metrics(pred, gt, window, out=metrics[row])
             rendered.append((pred[..., :3], aux if keep_aux else None))
@@ -238,7 +250,20 @@ def parser():
                         "over the valid pixels and the valid fraction (eval_depth)")
     p.add_argument("--depth-mode", choices=("depth", "disparity"), default="depth",
                    help="--depth-metrics: compare depth / alpha, or alpha / depth (maps of inverse depths)")
+    p.add_argument("--downscale", default=None, metavar="F,...",
+                   help="multi-scale eval: score once per factor (1..16, e.g. 1,2,4,8), rendering at 1 / F of each "
+                        "view's size against the area-filtered image")
     return p
+
+
+def parse_scales(text: str) -> List[int]:
+    """'1,2,4,8' -> [1, 2, 4, 8]; ValueError for anything that is not a list of factors 1..16."""
+    from .pyramid import check_factor
+
+    try:
+        return [check_factor(int(x)) for x in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--downscale takes factors from 1 to 16 separated by commas, got {text!r}") from None
 
 
 def main(argv=None) -> int:
@@ -246,7 +271,14 @@ def main(argv=None) -> int:
     import os
     import sys
 
-    args = parser().parse_args(argv)
+    p = parser()
+    args = p.parse_args(argv)
+    scales = None
+    if args.downscale is not None:
+        try:
+            scales = parse_scales(args.downscale)
+        except ValueError as e:
+            p.error(str(e))
 
     data = _load_dataset(args)  # before any GPU work
     if data.eval is None or not data.eval.views:
@@ -260,10 +292,27 @@ def main(argv=None) -> int:
     else:
         splats = Splats.from_ply(args.splats, dev)
     rng = np.random.default_rng(args.seed)
-    stats = eval_stats(splats, data.eval, args.num_frames, rng, args.window, antialiased=args.antialiased)
-    for s in stats.samples:
-        print(f"{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
-    print(f"mean ({len(stats.samples)} views)\tpsnr {stats.mean_psnr():.4f}\tssim {stats.mean_ssim():.6f}")
+    scale_rows = None
+    if scales is None:
+        stats = eval_stats(splats, data.eval, args.num_frames, rng, args.window, antialiased=args.antialiased)
+        for s in stats.samples:
+            print(f"{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
+        print(f"mean ({len(stats.samples)} views)\tpsnr {stats.mean_psnr():.4f}\tssim {stats.mean_ssim():.6f}")
+    else:
+        # the same views at every scale: chosen once, then scored as a scene of their own
+        from .dataset import Scene
+
+        chosen = Scene([data.eval.views[i] for i in select_views(len(data.eval.views), args.num_frames, rng)])
+        scale_rows, stats = [], None
+        for f in scales:
+            st = eval_stats(splats, chosen, None, None, args.window, antialiased=args.antialiased, downscale=f)
+            stats = st if stats is None or f == 1 else stats  # the top-level rows: scale 1 when asked for, else the first
+            for s in st.samples:
+                print(f"scale 1/{f}\t{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
+            print(f"scale 1/{f}\tmean ({len(st.samples)} views)\tpsnr {st.mean_psnr():.4f}\tssim {st.mean_ssim():.6f}")
+            scale_rows.append({"downscale": f,
+                               "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in st.samples],
+                               "mean_psnr": st.mean_psnr(), "mean_ssim": st.mean_ssim()})
     if args.depth_dir:
         write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir)
     depth_rows = None
@@ -278,6 +327,8 @@ def main(argv=None) -> int:
                "antialiased": bool(args.antialiased),
                "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in stats.samples],
                "mean_psnr": stats.mean_psnr(), "mean_ssim": stats.mean_ssim()}
+        if scale_rows is not None:
+            res["scales"] = scale_rows
         if depth_rows is not None:
             res["depth_mode"] = args.depth_mode
             res["depth_views"] = [{"name": r.view.name, "mean_abs_error": r.mean_abs_error,

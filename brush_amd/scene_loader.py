@@ -6,7 +6,8 @@ construction, as the u8 it was decoded as (alpha kept when present, as image_to_
 u8 directly (brush_l1_ssim_loss_gt).  `next_batch` then only draws an index: no host<->device traffic, no
 synchronisation and nothing left for a prefetch thread to do.  Batch size is 1, as the reference asserts
 (train.rs:216-219).  A view's depth map (build extension, SceneView.depth) is uploaded the same way, once and in the
-dtype it is stored in; brush_depth_loss reads uint16 and float32 directly.
+dtype it is stored in; brush_depth_loss reads uint16 and float32 directly.  `set_downscale` (build extension) makes the
+loader hand out every view at 1 / factor, resized on the device from the resident copies (brush_amd/pyramid.py).
 """
 from __future__ import annotations
 
@@ -53,17 +54,40 @@ class SceneLoader:
                 depth = torch.from_numpy(np.array(depth, copy=True, order="C")).to(self.device)  # as stored, once
             self.depths.append(depth)
         self.total_bytes = int(sum(t.numel() * t.element_size() for t in self.images + self.depths if t is not None))
+        # the level next_batch / next_indexed / depth hand out: at factor 1 the uploaded tensors themselves
+        self.downscale = 1
+        self.level_bytes = 0
+        self._images, self._depths = self.images, self.depths
 
     def __len__(self) -> int:
         return len(self.images)
+
+    def set_downscale(self, factor: int) -> None:
+        """Hands out every view at 1 / factor from now on (coarse-to-fine training): the image through
+        pyramid.area_resize and the depth map, where the view has one, through pyramid.nearest_resize, each to
+        pyramid.downscaled_size of that view's own size.  The previous level is dropped first; factor 1 goes back to the
+        uploaded tensors and holds nothing.  Launches on the current stream and nothing else: no read-back, no
+        synchronisation.  `level_bytes` is what the level holds beside `total_bytes`.  The random draw does not depend
+        on the factor."""
+        from .pyramid import area_resize, check_factor, nearest_resize
+
+        factor = check_factor(factor)
+        self._images, self._depths = self.images, self.depths  # drops the previous level
+        self.downscale, self.level_bytes = 1, 0
+        if factor == 1:
+            return
+        self._images = [area_resize(t, factor=factor) for t in self.images]
+        self._depths = [None if t is None else nearest_resize(t, factor=factor) for t in self.depths]
+        self.downscale = factor
+        self.level_bytes = int(sum(t.numel() * t.element_size() for t in self._images + self._depths if t is not None))
 
     def next_index(self) -> int:
         return int(self.rng.integers(0, len(self.images)))
 
     def depth(self, i: int) -> Optional[torch.Tensor]:
         """View i's depth map on the device (uint16 or float32 [h,w], as stored; the view's depth_scale / depth_offset
-        turn it into scene units), or None when the view has none."""
-        return self.depths[i]
+        turn it into scene units), or None when the view has none.  At the current level's size."""
+        return self._depths[i]
 
     def next_batch(self) -> Tuple[object, torch.Tensor]:
         """(SceneView, its image as a uint8 [h,w,3|4] device tensor)."""
@@ -73,4 +97,4 @@ class SceneLoader:
     def next_indexed(self) -> Tuple[int, object, torch.Tensor]:
         """next_batch with the drawn view's index in scene.views in front (the same draw from the same rng)."""
         i = self.next_index()
-        return i, self.scene.views[i], self.images[i]
+        return i, self.scene.views[i], self._images[i]

@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Callable, Optional
+from typing import Callable, Optional, Tuple
 
 import torch
 
@@ -101,6 +101,40 @@ class TrainConfig:
     depth_weight_final: Optional[float] = None
     depth_mode: str = "depth"
     depth_alpha_min: float = 0.5
+    # Build extension: coarse-to-fine training (brush_amd/pyramid.py; nerfstudio's num_downscales / resolution_schedule
+    # is the model).  (step, factor) pairs, steps non-negative and strictly increasing, factors 1..16: from `step` on the
+    # training loop draws its targets at 1 / factor of their stored size (SceneLoader.set_downscale).  The trainer's step
+    # takes its size from the target, so nothing else changes; () (the default) is the run without the option, bit for
+    # bit.  DESIGN §8 row 13.
+    downscale_schedule: Tuple[Tuple[int, int], ...] = ()
+
+    def check_downscale_schedule(self) -> Tuple[Tuple[int, int], ...]:
+        """The schedule as a tuple of (int step, int factor), or a ValueError naming what is wrong with it."""
+        from .pyramid import MAX_FACTOR
+
+        pairs = []
+        for p in self.downscale_schedule:
+            if not isinstance(p, (tuple, list)) or len(p) != 2 or any(isinstance(x, bool) or int(x) != x for x in p):
+                raise ValueError(f"TrainConfig.downscale_schedule holds (step, factor) pairs of integers, got {p!r}")
+            step, factor = int(p[0]), int(p[1])
+            if step < 0:
+                raise ValueError(f"TrainConfig.downscale_schedule: steps must be >= 0, got {step}")
+            if not 1 <= factor <= MAX_FACTOR:
+                raise ValueError(f"TrainConfig.downscale_schedule: factors must be 1..{MAX_FACTOR}, got {factor}")
+            if pairs and step <= pairs[-1][0]:
+                raise ValueError(f"TrainConfig.downscale_schedule: steps must be strictly increasing, got {step} after "
+                                 f"{pairs[-1][0]}")
+            pairs.append((step, factor))
+        return tuple(pairs)
+
+    def downscale_at(self, step: int) -> int:
+        """The factor of the last pair of downscale_schedule with pair.step <= step; 1 when there is none."""
+        factor = 1
+        for s, f in self.downscale_schedule:
+            if s > step:
+                break
+            factor = int(f)
+        return factor
 
 
 @dataclass
@@ -172,6 +206,7 @@ class SplatTrainer:
             raise ValueError(f"TrainConfig.depth_mode must be 'depth' or 'disparity', got {self.config.depth_mode!r}")
         if self.config.depth_weight < 0 or (self.config.depth_weight_final or 0.0) < 0:
             raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
+        self.config.check_downscale_schedule()
         dev = splats.means.device
         assert dev.type == "cuda", "brush_amd has no CPU path: the splats must live on the GPU"
         self.iter = 0

@@ -16,6 +16,12 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased] [--pose-opt] [--export-cameras CAMS.json]
         [--strategy default|mcmc] [--cap-max 1000000] [--exposure-opt] [--export-exposures EXP.json]
         [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
+        [--downscale-schedule STEP:FACTOR,...] [--num-downscales K] [--resolution-schedule S]
+
+--downscale-schedule 0:4,3000:2,6000:1 trains coarse to fine (TrainConfig.downscale_schedule, brush_amd/pyramid.py): from
+each STEP on, the training targets are the resident images at 1 / FACTOR of their stored size, area-filtered on the device
+(depth maps: nearest neighbour).  --num-downscales K --resolution-schedule S is nerfstudio's spelling of the same thing:
+the pairs (i S, 2^(K - i)) for i = 0..K.  Evals render at the eval views' full size whatever the schedule says.
 
 --depth-weight W > 0 supervises the rendered depth with the dataset's depth maps (nerfstudio's depth_file_path; COLMAP's
 depths/<image stem>.png|.npy): W times the mean absolute difference of depth / alpha (--depth-mode disparity: alpha /
@@ -75,11 +81,13 @@ class TrainLog:
     pose_deltas: Optional[List[List[float]]] = None  # pose_opt: the twist (omega, tau) of every training view
     exposure_opt: bool = False
     exposures: Optional[List[List[float]]] = None    # exposure_opt: the 3x4 map (12 floats, row-major) of every view
+    downscales: List[Tuple[int, int]] = field(default_factory=list)  # (step, factor): the level switches that happened
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
                 "image_bytes": self.image_bytes, "num_splats": self.num_splats, "pose_opt": self.pose_opt,
                 "pose_deltas": self.pose_deltas, "exposure_opt": self.exposure_opt, "exposures": self.exposures,
+                "downscales": [[int(s), int(f)] for s, f in self.downscales],
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -161,9 +169,14 @@ class TrainLoop:
         self._last = (0, 0.0)  # (step, training seconds) of the previous eval row
 
     def step(self):
-        """One training iteration on a random view; its loss lands in the device log."""
+        """One training iteration on a random view, at the level TrainConfig.downscale_at gives for this step; its loss
+        lands in the device log."""
         if self.done >= self.steps:
             raise RuntimeError(f"the run has {self.steps} steps, all done")
+        factor = self.config.downscale_at(self.done)
+        if factor != self.loader.downscale:  # a level switch: launches only (SceneLoader.set_downscale)
+            self.loader.set_downscale(factor)
+            self.log.downscales.append((self.done, factor))
         if self.poses is None and self.exposures is None and not self._depth:
             view, gt = self.loader.next_batch()
             self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
@@ -191,7 +204,8 @@ class TrainLoop:
 
     def evaluate(self, eval_views: Optional[int] = None) -> Tuple[EvalRow, object]:
         """eval_stats on the dataset's eval views, between steps, on this thread and stream (its docstring's rule);
-        appends and returns the EvalRow (and the EvalStats)."""
+        appends and returns the EvalRow (and the EvalStats).  Always at the eval views' full size, whatever level the
+        downscale schedule has the training at: the rows of one run stay comparable."""
         from .eval import eval_stats
 
         if self.dataset.eval is None or not self.dataset.eval.views:
@@ -262,6 +276,43 @@ def train_scene(dataset: Dataset, config: Optional[TrainConfig] = None, *, steps
 
 
 # ---------------------------------------------------------------------------- command line
+def parse_downscale_schedule(text: str) -> Tuple[Tuple[int, int], ...]:
+    """'0:4,3000:2,6000:1' -> ((0, 4), (3000, 2), (6000, 1)); the pairs are validated by TrainConfig."""
+    pairs = []
+    for item in text.split(","):
+        step, sep, factor = item.partition(":")
+        try:
+            if not sep:
+                raise ValueError
+            pairs.append((int(step), int(factor)))
+        except ValueError:
+            raise ValueError(f"--downscale-schedule takes STEP:FACTOR pairs separated by commas, got {item!r}") from None
+    return tuple(pairs)
+
+
+def downscale_schedule_from_args(args) -> Tuple[Tuple[int, int], ...]:
+    """The (step, factor) pairs the command line asks for, from either spelling; () when it asks for none.  Raises
+    ValueError when both spellings are given or one is malformed."""
+    explicit = args.downscale_schedule is not None
+    shorthand = args.num_downscales is not None
+    if explicit and (shorthand or args.resolution_schedule is not None):
+        raise ValueError("--downscale-schedule and --num-downscales / --resolution-schedule are two spellings of one "
+                         "option: give one of them")
+    if explicit:
+        pairs = parse_downscale_schedule(args.downscale_schedule)
+    elif shorthand:
+        k = args.num_downscales
+        every = 3000 if args.resolution_schedule is None else args.resolution_schedule  # splatfacto's default
+        if not 0 <= k <= 4 or every < 1:
+            raise ValueError("--num-downscales must be 0..4 (factors up to 16) and --resolution-schedule >= 1")
+        pairs = tuple((i * every, 2 ** (k - i)) for i in range(k + 1))
+    elif args.resolution_schedule is not None:
+        raise ValueError("--resolution-schedule needs --num-downscales")
+    else:
+        return ()
+    return TrainConfig(downscale_schedule=pairs).check_downscale_schedule()
+
+
 def parser():
     import argparse
 
@@ -300,6 +351,12 @@ def parser():
                    help="move the depth weight exponentially from --depth-weight to this value over the run")
     p.add_argument("--depth-mode", choices=("depth", "disparity"), default="depth",
                    help="compare depth / alpha, or alpha / depth (the maps then hold inverse depths)")
+    p.add_argument("--downscale-schedule", default=None, metavar="STEP:FACTOR,...",
+                   help="coarse-to-fine training: from STEP on, train on the images at 1 / FACTOR (e.g. 0:4,3000:2,6000:1)")
+    p.add_argument("--num-downscales", type=int, default=None, metavar="K",
+                   help="nerfstudio's spelling: start at 1 / 2^K and double the resolution every --resolution-schedule steps")
+    p.add_argument("--resolution-schedule", type=int, default=None, metavar="S",
+                   help="--num-downscales: steps between two doublings (default 3000)")
     return p
 
 
@@ -310,6 +367,10 @@ def main(argv=None) -> int:
 
     p = parser()
     args = p.parse_args(argv)
+    try:
+        schedule = downscale_schedule_from_args(args)
+    except ValueError as e:
+        p.error(str(e))
     if not os.path.exists(args.dataset):
         p.error(f"dataset not found: {args.dataset}")
     if args.steps < 0 or args.eval_every < 0:
@@ -352,7 +413,8 @@ def main(argv=None) -> int:
 
     config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
                          mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt, depth_weight=args.depth_weight,
-                         depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode)
+                         depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
+                         downscale_schedule=schedule)
     splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,

@@ -567,6 +567,27 @@ int brush_depth_loss(const float *pred, const float *depth, const void *target, 
                      uint32_t h, float *v_depth, float *v_pred, float *stats, float *loss_accum, void *workspace,
                      size_t workspace_bytes, brush_stream_t stream);
 
+/* ---- device image pyramid (build extension; nerfstudio's num_downscales, Mip-Splatting's multi-scale eval) -------- */
+/* brush_area_resize_u8: an exact area (box) filter on an interleaved u8 image src [h][w][channels], channels 3 or 4,
+ * every channel on its own (alpha like the others), to dst [oh][ow][channels] for any 1 <= ow <= w, 1 <= oh <= h.
+ * Defined in integers: with x in units where a source pixel is ow wide and an output pixel w wide (y: oh and h),
+ *   wx(X,s) = max(0, min((X+1) w, (s+1) ow) - max(X w, s ow)),  wy(Y,r) the same with h and oh,  D = w h,
+ *   dst[Y][X][c] = floor((sum_r sum_s wy(Y,r) wx(X,s) src[r][s][c] + floor(D / 2)) / D).
+ * One rounding, at the end, and no floating point: an even-sized image halved is (a + b + c + d + 2) >> 2, ow = w and
+ * oh = h is the identity, a constant image stays constant.  The sum is held in 32 bits while 255 D + D / 2 < 2^32 and
+ * in 64 bits above; both divide exactly.
+ * brush_nearest_resize: dst[Y][X] = src[min(((2Y+1) h) / (2 oh), h-1)][min(((2X+1) w) / (2 ow), w-1)] on [h][w]
+ * elements of elem_bytes = 2 (u16) or 4 (f32, moved as bits), the rule of the dataset reader for depth maps: a "no
+ * measurement" zero never blends into its neighbours.  src / dst aligned to elem_bytes.
+ * Both: a NULL pointer, a zero size, ow > w or oh > h, a side above 16384, channels not in {3, 4}, elem_bytes not in
+ * {2, 4} or overlapping src / dst ranges return BRUSH_ERR_INVALID_ARG and write nothing, checked before any GPU call.
+ * Device pointers.  No workspace, no allocation, no synchronisation, no atomics: graph-capturable; the same inputs give
+ * the same bits on every call. */
+int brush_area_resize_u8(const uint8_t *src, uint32_t w, uint32_t h, uint32_t channels, uint8_t *dst, uint32_t ow,
+                         uint32_t oh, brush_stream_t stream);
+int brush_nearest_resize(const void *src, uint32_t elem_bytes, uint32_t w, uint32_t h, void *dst, uint32_t ow,
+                         uint32_t oh, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

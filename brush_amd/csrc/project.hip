@@ -168,6 +168,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
                 // radius <= 3*sqrt(lambda_max + quirk slack) + 1 with lambda_max(cov2d) <= trace <=
                 // s_max^2 * cull_k / z^2 + 0.6; if even that radius leaves the tile bbox empty, the exact
                 // test (:54-62) would reject as well.
+                // CONTRACT: the bound takes |V|_2 = s_max^2, i.e. a UNIT quaternion (no load of it here: Phase A is
+                // an HBM stream).  quat_to_rotmat does not normalise: for |q| = s it yields
+                // R(q) = (1 - s^2) I + s^2 R(q/s), of norm |2 s^2 - 1|, so |V|_2 <= (2 s^2 - 1)^2 s_max^2.  cull_k
+                // carries |W|_F^2 = 3 where an orthonormal view rotation needs |W|_2^2 = 1, and 1 % on top: the
+                // bound stays safe while (2 s^2 - 1)^2 <= 3.03, s <= 1.17, and for every s <= 1.  Callers are told
+                // |q| <= 1.1 (brush_hip.h, render_splats); beyond that a splat whose centre is off-frame may be
+                // culled here where the reference keeps it (tests/test_cull_cpu.py asserts that |q| = 2 does it).
                 const float smax = det_expf(smax_r[r]) * 1.001f;
                 const float rz = 1.0f / p_view[2];
                 const float lam = smax * smax * vp.cull_k * rz * rz + 1.0f;

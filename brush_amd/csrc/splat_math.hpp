@@ -351,8 +351,11 @@ __device__ __forceinline__ void walk_rect(const float xy[2], const float conic[3
     for (int i = 0; i < 2; i++) {
         if (!(rr[i] < 3.0e37f)) continue;  // reach unknown: the whole bbox
         // tile t can be reached only if |xy - (16 t + 8)| <= r  <=>  t in [(xy - r - 8) / 16, (xy + r - 8) / 16]
-        const int32_t lo = f2i_sat(floorf((xy[i] - rr[i] - half) / (float)kTileWidth)) - 1;
-        const int32_t hi = f2i_sat(floorf((xy[i] + rr[i] - half) / (float)kTileWidth)) + 2;  // exclusive
+        // (the slack is added in float, before the saturating conversion: with a centre or a reach beyond 2^31 tiles the
+        // integer form wrapped around, INT_MIN - 1 and INT_MAX + 2, and the clamps below then emptied the rectangle of
+        // a splat that covers the frame; below 2^24 tiles the float sums are exact, above they clamp to the bbox anyway)
+        const int32_t lo = f2i_sat(floorf((xy[i] - rr[i] - half) / (float)kTileWidth) - 1.0f);
+        const int32_t hi = f2i_sat(floorf((xy[i] + rr[i] - half) / (float)kTileWidth) + 2.0f);  // exclusive
         const uint32_t nlo = (uint32_t)iclamp(lo, (int32_t)bb[i], (int32_t)bb[2 + i]);
         const uint32_t nhi = (uint32_t)iclamp(hi, (int32_t)bb[i], (int32_t)bb[2 + i]);
         bb[i] = nlo;

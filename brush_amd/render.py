@@ -373,6 +373,9 @@ def render_splats(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Opt
     selects bitwise reproducible gradients for this call (default: render.DETERMINISTIC, then BRUSH_DETERMINISTIC).
     `antialiased` (build extension, BRUSH_AUX_ANTIALIASED): each splat's opacity is scaled by
     sqrt(det(S) / det(S + 0.3 I)), so that the 0.3 px^2 blur keeps its integrated weight (Mip-Splatting's 2D filter).
+    Quaternion contract: `quats` must be unit, as `Splats.render` and the trainer provide them.  Results equal the
+    reference's for |q| <= 1.1; beyond that a splat whose centre is off-frame may be culled where the reference keeps it
+    (the cull's screen-bounds prefilter bounds the covariance without reading the quaternion, csrc/project.hip).
     """
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
     tracked = torch.is_grad_enabled() and not render_u32_buffer and any(
@@ -432,7 +435,9 @@ def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dumm
     the colour composites (z_i: camera-space z of splat i's mean).  Returns (img [h,w,4], depth [h,w], aux); the image
     and aux are bitwise those of render_splats.  D is not normalised: D / img[..., 3] is the expected depth of the
     covered part.  Differentiable for gradients on img, on depth or both, into the same six parents.
-    `antialiased`: as render_splats."""
+    `antialiased`: as render_splats.
+    Quaternion contract (unit `quats`; the reference's results for |q| <= 1.1): as render_splats.
+    """
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
     tracked = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity))
@@ -521,7 +526,9 @@ def render_splats_pose(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy
     per backward: that readback is the op's single synchronisation (SplatTrainer uses a form that leaves them on
     the device).  Conventions of the gradient (include/brush_hip.h): the Jacobian at the unclamped p_view, no gradient
     through the SH view direction (above SH degree 0: the gradient with the colours held fixed), piecewise-constant
-    culling and tiling, none for focal / centre."""
+    culling and tiling, none for focal / centre.
+    Quaternion contract (unit `quats`; the reference's results for |q| <= 1.1): as render_splats.
+    """
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
     viewmat = _check_viewmat(viewmat)
     tracked = torch.is_grad_enabled() and any(
@@ -554,7 +561,9 @@ def render_rgba8(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, raw
     """Forward-only display path: packed RGBA8 with rows `row_pitch` pixels apart (default
     rgba8_row_pitch(width)), i.e. the padded tensor burn_texture.rs:17-26 builds with a zero-fill
     and a slice_assign, written by the rasterizer directly.  Returns (int32 [h, row_pitch, 1], aux).
-    `antialiased`: as render_splats."""
+    `antialiased`: as render_splats.
+    Quaternion contract (unit `quats`; the reference's results for |q| <= 1.1): as render_splats.
+    """
     _check_inputs(means, None, log_scales, quats, sh_coeffs, raw_opacity)
     pitch = rgba8_row_pitch(img_size[0]) if row_pitch is None else int(row_pitch)
     with torch.no_grad():

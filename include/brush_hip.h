@@ -198,7 +198,12 @@ int brush_inclusive_scan_u32(const uint32_t *in, uint32_t *out, uint32_t n, void
 int brush_fwd_workspace_size(uint32_t n, uint32_t w, uint32_t h, uint32_t sh_degree,
                              uint32_t max_intersects, size_t *bytes);
 /* means[N,3] log_scales[N,3] quats[N,4] (w,x,y,z; already normalised) sh_coeffs[N,C,3]
- * raw_opacity[N].  out_img: raster_u32 == 0 -> float[h,w,4] (rgb, 1-T); != 0 -> uint32[h,w]
+ * raw_opacity[N].
+ * Quaternion contract (this entry point, brush_render_forward_rgba8 and brush_render_forward_depth): quats must be
+ * unit, as Splats.render and the trainer (brush_normalize_quats) provide them.  Results equal the reference's for
+ * |q| <= 1.1; beyond that a splat whose centre is off-frame may be culled where the reference keeps it (the cull's
+ * screen-bounds prefilter bounds the covariance by s_max^2 without reading the quaternion, project.hip).
+ * out_img: raster_u32 == 0 -> float[h,w,4] (rgb, 1-T); != 0 -> uint32[h,w]
  * packed RGBA8 (rasterize.wgsl:106-109) and aux->final_index is not written. */
 int brush_render_forward(const BrushUniforms *h_uniforms, const float *means,
                          const float *log_scales, const float *quats, const float *sh_coeffs,

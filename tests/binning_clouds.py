@@ -108,8 +108,9 @@ def classify(projected, tile_bounds):
         half = TILE_WIDTH / 2.0
         for i, hh in enumerate((hx, hy)):
             r = hh * 1.001 + (half + 0.02)
-            lo = _trunc_clamp(np.floor((xy[:, i] - r - half) / TILE_WIDTH), -2**31, 2**31) - 1
-            hi = _trunc_clamp(np.floor((xy[:, i] + r - half) / TILE_WIDTH), -2**31, 2**31) + 2
+            # the slack goes in before the saturating conversion, as in walk_rect
+            lo = _trunc_clamp(np.floor((xy[:, i] - r - half) / TILE_WIDTH) - 1.0, -2**31, 2**31)
+            hi = _trunc_clamp(np.floor((xy[:, i] + r - half) / TILE_WIDTH) + 2.0, -2**31, 2**31)
             nlo = np.clip(lo, bb[:, i], bb[:, 2 + i])
             nhi = np.maximum(np.clip(hi, bb[:, i], bb[:, 2 + i]), nlo)
             bb[:, i] = np.where(ok, nlo, bb[:, i])

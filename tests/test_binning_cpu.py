@@ -107,6 +107,37 @@ def test_rounding_flip_excuse_is_narrow(group16):
     assert n_cov > 100
 
 
+def test_nan_equal_is_narrow(group16):
+    """assert_integer_parity(nan_equal=True) lets a NaN differ in sign and payload and nothing else: a NaN moved to
+    another word and a finite word changed by one ulp are both rejected; the default stays bitwise."""
+    _, _, oa, _ = group16
+    oa = dict(oa, projected_splats=oa["projected_splats"].copy())
+    words = oa["projected_splats"].view(np.uint32)
+    words[5, 2], words[9, 4] = 0x7FC00000, 0xFFC00001  # two NaNs, as `inf - inf` leaves them on the host
+    good = BK.oracle_arrays(oa)
+    BK.assert_integer_parity(good, oa)
+    BK.assert_integer_parity(good, oa, nan_equal=True)
+    flipped = BK.oracle_arrays(oa)
+    flipped["projected_splats"].view(np.uint32)[5, 2] = 0xFFC00000  # the device's sign
+    BK.assert_integer_parity(flipped, oa, nan_equal=True)
+    with pytest.raises(AssertionError):
+        BK.assert_integer_parity(flipped, oa)
+    moved = BK.oracle_arrays(oa)
+    w = moved["projected_splats"].view(np.uint32)
+    w[5, 2], w[5, 3] = w[5, 3], w[5, 2]
+    with pytest.raises(AssertionError):
+        BK.assert_integer_parity(moved, oa, nan_equal=True)
+    ulp = BK.oracle_arrays(oa)
+    ulp["projected_splats"].view(np.uint32)[9, 3] += 1
+    assert np.isfinite(ulp["projected_splats"][9, 3])
+    with pytest.raises(AssertionError):
+        BK.assert_integer_parity(ulp, oa, nan_equal=True)
+    extra = BK.oracle_arrays(oa)
+    extra["projected_splats"][11, 0] = np.nan
+    with pytest.raises(AssertionError):
+        BK.assert_integer_parity(extra, oa, nan_equal=True)
+
+
 def test_properties_hold_on_a_truncated_list():
     """The oracle's own truncated list (flat_truncated: 1 000 003 of 2.5 M entries) passes the properties, with the
     per-splat counts bounded by, not equal to, the steps of cum_tiles_hit."""

@@ -24,6 +24,10 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 images and a nearest pick for depth maps (brush_amd/pyramid.py; build extension,
                                 nerfstudio's resolution schedule and Mip-Splatting's multi-scale eval are the users:
                                 TrainConfig.downscale_schedule, SceneLoader.set_downscale, eval_stats(downscale=))
+  Distortion / fit_scale / undistort_image / undistort_depth / undistorted_camera / undistort_dataset  <- COLMAP
+                                views with lens distortion (SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) resampled on the
+                                device into the pinhole camera the rasterizer assumes (brush_amd/undistort.py; build
+                                extension, COLMAP's image_undistorter is the model; both command lines apply it)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -43,6 +47,8 @@ from . import dataset  # noqa: F401
 # reachable as `from brush_amd.depth_loss import ...`)
 from .depth_loss import depth_loss, depth_loss_into  # noqa: F401
 from .pyramid import area_resize, downscaled_size, nearest_resize  # noqa: F401
+from .undistort import (Distortion, fit_scale, undistort_dataset, undistort_depth, undistort_image,  # noqa: F401
+                        undistorted_camera)
 
 # brush_amd.eval and brush_amd.train_loop are imported on first use: importing them here would load the module before
 # `python -m brush_amd.eval` / `python -m brush_amd.train_loop` runs it as __main__ (runpy then warns that it is loaded

@@ -105,6 +105,12 @@ class BrushDepthLoss(C.Structure):
     ]
 
 
+class BrushUndistort(C.Structure):
+    """The map of brush_undistort_u8 / brush_undistort_nearest (include/brush_hip.h: BrushUndistort)."""
+    _fields_ = [(name, C.c_float) for name in ("fx", "fy", "cx", "cy", "iofx", "iofy", "ocx", "ocy", "k1", "k2", "k3",
+                                               "k4", "k5", "k6", "p1", "p2")]
+
+
 class BrushError(RuntimeError):
     pass
 
@@ -197,6 +203,10 @@ _SYMBOLS = [
      [_P, _P, _P, C.POINTER(BrushDepthLoss), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     ("brush_area_resize_u8", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P]),
     ("brush_nearest_resize", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P]),
+    ("brush_undistort_u8", C.c_int,
+     [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(BrushUndistort), _P]),
+    ("brush_undistort_nearest", C.c_int,
+     [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.POINTER(BrushUndistort), _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

@@ -83,6 +83,9 @@ class SceneView:
     depth: Optional[np.ndarray] = None
     depth_scale: float = 1.0
     depth_offset: float = 0.0
+    # Build extension (brush_amd/undistort.py): the lens distortion `camera` leaves out (a COLMAP camera with non-zero
+    # distortion coefficients), or None for a pinhole view; undistort_dataset resamples such a view and clears it.
+    distortion: Optional["Distortion"] = None  # noqa: F821
 
     def image_f32(self) -> np.ndarray:
         """The trainer's target tensor: u8 / 255, alpha kept when present (brush-train/src/image.rs)."""
@@ -467,7 +470,11 @@ def read_colmap(root: str, max_frames: Optional[int] = None, max_resolution: Opt
     """colmap.rs:15-146: views sorted by image id; every eval_split_every-th view goes to eval.
     Build extension: a view whose image is images/<stem>.<ext> takes the depth map depths/<stem>.png (16-bit, kept as
     uint16, millimetres) or depths/<stem>.npy (float32, scene units) when there is one; an optional
-    sparse/0/depth_params.json {stem: {"scale": s, "offset": o}} replaces that view's scale and offset."""
+    sparse/0/depth_params.json {stem: {"scale": s, "offset": o}} replaces that view's scale and offset.  A view whose
+    camera has non-zero distortion coefficients carries them as `distortion` (brush_amd/undistort.py); camera and image
+    are the ones of the pinhole reading either way."""
+    from .undistort import Distortion
+
     files = DatasetFiles(root)
     is_binary, base, ext = _colmap_paths(files)
     params_path = DatasetFiles.join(base, "sparse/0/depth_params.json")
@@ -486,6 +493,7 @@ def read_colmap(root: str, max_frames: Optional[int] = None, max_resolution: Opt
         else:
             img = np.zeros((0, 0, 3), dtype=np.uint8)
         view = SceneView(path, colmap_camera(info.quat_wxyz, info.tvec, cams[info.camera_id]), img)
+        view.distortion = Distortion.from_colmap(cams[info.camera_id], img.shape[1], img.shape[0])
         stem = os.path.splitext(info.name)[0]
         for dext in (".png", ".npy") if load_images else ():
             dpath = DatasetFiles.join(base, f"depths/{stem}{dext}")

@@ -253,6 +253,9 @@ def parser():
     p.add_argument("--downscale", default=None, metavar="F,...",
                    help="multi-scale eval: score once per factor (1..16, e.g. 1,2,4,8), rendering at 1 / F of each "
                         "view's size against the area-filtered image")
+    p.add_argument("--no-undistort", action="store_true",
+                   help="score views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
+                        "loaded, as if they were pinhole, instead of undistorting them first")
     return p
 
 
@@ -287,6 +290,9 @@ def main(argv=None) -> int:
     from .gaussian_splats import Splats
 
     dev = torch.device("cuda", torch.cuda.current_device())
+    from .undistort import undistort_for_cli
+
+    data = undistort_for_cli(data, not args.no_undistort, dev)
     if args.splats.endswith(".safetensors"):
         splats = Splats.from_safetensors(args.splats, dev)
     else:

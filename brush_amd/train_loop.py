@@ -357,6 +357,9 @@ def parser():
                    help="nerfstudio's spelling: start at 1 / 2^K and double the resolution every --resolution-schedule steps")
     p.add_argument("--resolution-schedule", type=int, default=None, metavar="S",
                    help="--num-downscales: steps between two doublings (default 3000)")
+    p.add_argument("--no-undistort", action="store_true",
+                   help="train on views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
+                        "loaded, as if they were pinhole, instead of undistorting them first")
     return p
 
 
@@ -394,6 +397,9 @@ def main(argv=None) -> int:
         return 2
 
     dev = torch.device("cuda", torch.cuda.current_device())
+    from .undistort import undistort_for_cli
+
+    data = undistort_for_cli(data, not args.no_undistort, dev)  # distorted views become pinhole views, once
     init = Splats.from_ply(args.init, dev) if args.init else points
 
     def on_eval(row, stats):

@@ -593,6 +593,41 @@ int brush_area_resize_u8(const uint8_t *src, uint32_t w, uint32_t h, uint32_t ch
 int brush_nearest_resize(const void *src, uint32_t elem_bytes, uint32_t w, uint32_t h, void *dst, uint32_t ow,
                          uint32_t oh, brush_stream_t stream);
 
+/* ---- undistortion of COLMAP views (build extension; COLMAP's image_undistorter is the model) ---------------------- */
+/* Resamples a distorted w x h source into an ow x oh pinhole image.  All float operations are float32, round to
+ * nearest, never contracted; pixel centres are at +0.5.  For output pixel (X, Y):
+ *   x  = ((float)X + 0.5f - ocx) * iofx            y likewise
+ *   r2 = x*x + y*y
+ *   num = 1 + r2*(k1 + r2*(k2 + r2*k3))            den = 1 + r2*(k4 + r2*(k5 + r2*k6))
+ *   rad = num / den                                 (always divided; IEEE division)
+ *   a  = x*y
+ *   xd = x*rad + ((2*p1)*a + p2*(r2 + (2*x)*x))
+ *   yd = y*rad + (p1*(r2 + (2*y)*y) + (2*p2)*a)
+ *   u  = (fx*xd + cx) - 0.5f                        v = (fy*yd + cy) - 0.5f      (source index space)
+ *   qx = (int32) rintf(u * 256.0f)                  qy likewise                  (Q8; NaN or |.| >= 2^30: invalid)
+ * (fx, fy, cx, cy): the source camera; (1 / iofx, 1 / iofy, ocx, ocy): the output camera, the host divides in float32;
+ * k1..k6, p1, p2: OpenCV's rational model, a model's missing coefficients are zero (COLMAP's SIMPLE_RADIAL, RADIAL,
+ * OPENCV and FULL_OPENCV).  A pixel is valid iff 0 <= qx <= (w-1) 256 and 0 <= qy <= (h-1) 256.
+ * brush_undistort_u8: interleaved u8 src [h][w][channels], channels 3 or 4, to dst [oh][ow][channels]: x0 = qx >> 8,
+ * ax = qx & 255, x1 = min(x0+1, w-1), the same in y, every channel on its own
+ *   dst = (sum over the four taps of (256-ax | ax) (256-ay | ay) src + 32768) >> 16
+ * (one rounding, in integers); an invalid pixel is 0 in every channel; `valid`, when not NULL, is a u8 [oh][ow] mask
+ * that receives 1 for a valid pixel and 0 for an invalid one (it may overlap neither image).
+ * brush_undistort_nearest: [h][w] elements of elem_bytes = 2 (u16) or 4 (f32, moved as bits) to [oh][ow]: the element
+ * at ((qx+128)>>8, (qy+128)>>8), each clamped to the image; an invalid pixel is 0 ("no measurement"), and a zero never
+ * blends into a neighbour.  src / dst aligned to elem_bytes.
+ * Both: a NULL pointer (`valid` excepted), a zero size, a side above 8192 (beyond it float32 no longer resolves 1/256
+ * px comfortably), channels not in {3, 4}, elem_bytes not in {2, 4} or overlapping ranges return BRUSH_ERR_INVALID_ARG
+ * and write nothing, checked before any GPU call.  Device pointers except `map`.  No workspace, no allocation, no
+ * synchronisation, no atomics: graph-capturable; the same inputs give the same bits on every call. */
+typedef struct BrushUndistort {
+    float fx, fy, cx, cy, iofx, iofy, ocx, ocy, k1, k2, k3, k4, k5, k6, p1, p2;
+} BrushUndistort;
+int brush_undistort_u8(const uint8_t *src, uint32_t w, uint32_t h, uint32_t channels, uint8_t *dst, uint32_t ow,
+                       uint32_t oh, uint8_t *valid, const BrushUndistort *map, brush_stream_t stream);
+int brush_undistort_nearest(const void *src, uint32_t elem_bytes, uint32_t w, uint32_t h, void *dst, uint32_t ow,
+                            uint32_t oh, const BrushUndistort *map, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

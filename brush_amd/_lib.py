@@ -252,5 +252,20 @@ def check(status: int, what: str):
         raise BrushError(f"{what} failed: {msg} (status {status}, hipError {l.brush_last_hip_error()})")
 
 
+def size_query(name: str, *args) -> int:
+    """The byte count a size entry point (brush_*_workspace_size, brush_view_index_size) writes through its trailing
+    size_t pointer."""
+    n = C.c_size_t()
+    check(getattr(lib(), name)(*args, C.byref(n)), name)
+    return n.value
+
+
+def current_stream(device=None) -> int:
+    """The handle of torch's current stream on `device` (None: the current device), as the entry points take it."""
+    import torch
+
+    return torch.cuda.current_stream(device).cuda_stream
+
+
 def version() -> str:
     return lib().brush_version().decode()

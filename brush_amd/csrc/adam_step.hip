@@ -151,7 +151,7 @@ extern "C" int brush_adam_step(const BrushAdamConfig *cfg, uint32_t n, uint32_t 
     adam_bias_corrections(cfg->beta1, cfg->beta2, cfg->time, &a.rbc1, &a.rbc2);  // burn Adam: 1 - beta^time
     a.n = n, a.ncoef = C, a.quat_vjp = cfg->rotation_grad_wrt_normalized;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto aligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    auto aligned = [](const void *p) { return !misaligned(p, 16); };
     const bool vec = (n % 4 == 0) && aligned(means) && aligned(log_scales) && aligned(quats) && aligned(raw_opac) &&
                      aligned(sh) && aligned(v_means) && aligned(v_scales) && aligned(v_quats) && aligned(v_opac) &&
                      aligned(v_sh) && aligned(moment1) && aligned(moment2);
@@ -167,7 +167,7 @@ extern "C" int brush_adam_step(const BrushAdamConfig *cfg, uint32_t n, uint32_t 
 
 extern "C" int brush_normalize_quats(const float *rotation, float *normalized, uint32_t n, brush_stream_t stream) {
     if (n == 0) return BRUSH_OK;
-    if (!rotation || !normalized || (reinterpret_cast<uintptr_t>(rotation) & 15) || (reinterpret_cast<uintptr_t>(normalized) & 15))
+    if (!rotation || !normalized || misaligned(rotation, 16) || misaligned(normalized, 16))
         return BRUSH_ERR_INVALID_ARG;
     hipLaunchKernelGGL(k_normalize_quats, dim3(ceil_div(n, 256u)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const float4 *>(rotation), reinterpret_cast<float4 *>(normalized), n);

@@ -51,6 +51,26 @@ static inline int current_device_slot() {
 __host__ __device__ static inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// ---- host argument checks and reduction-grid sizes of the entry points ---------------
+// a: a power of two.
+__host__ __device__ static inline bool misaligned(const void *p, uintptr_t a) {
+    return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0;
+}
+// w h as a pixel count, or 0 when the image is empty or has 2^28 pixels or more.
+constexpr uint64_t kMaxPixels = 1ull << 28;
+static inline uint32_t checked_pixels(uint32_t w, uint32_t h) {
+    const uint64_t npix = (uint64_t)w * (uint64_t)h;
+    return (npix == 0 || npix >= kMaxPixels) ? 0u : (uint32_t)npix;
+}
+// Grid of a fixed-order reduction (fixed_sum.hpp) over n items, `threads` a workgroup and at most `cap` workgroups, and
+// the bytes of its workspace: one row of `words` doubles per workgroup.  Both are observable (*_workspace_size).
+static inline uint32_t capped_rows(uint32_t n, uint32_t threads, uint32_t cap) {
+    return min(ceil_div(n, threads), cap);
+}
+static inline size_t row_bytes(uint32_t rows, uint32_t words) {
+    return align_up((size_t)rows * words * sizeof(double), 256);
+}
+
 // Bump allocator over the caller's workspace (256-B aligned carve-outs).
 struct Carver {
     char *base;

@@ -10,9 +10,9 @@
 //
 //   k_depth_loss<MODE, GT>: one pixel per lane, grid-stride.  Writes v_depth[p] (0 where invalid), adds v_a into the
 //       alpha word of v_pred[p] (valid pixels only: every other word of v_pred keeps its bits), and carries one float64
-//       accumulator of |r| and one exact integer count of valid pixels per lane; then the reduction of exposure.hip: a
-//       fixed shuffle tree per wave, the four waves through LDS in wave order, one row {sum, count} per workgroup with
-//       ordinary stores.
+//       accumulator of |r| and one exact integer count of valid pixels per lane; then the reduction of fixed_sum.hpp:
+//       the fixed shuffle tree per wave (the count as uint32), the four waves through LDS in wave order, one row
+//       {sum, count} per workgroup with ordinary stores.
 //   k_depth_loss_finalize : one workgroup sums the rows at fixed strides through the same tree and writes
 //       stats = {(float)(c sum), (float)(count / (w h))}; with loss_accum it then does *loss_accum += stats[0].
 // No atomics, no counters, no allocation, no synchronisation: graph-capturable, and the same inputs give the same bits
@@ -22,27 +22,16 @@
 // 16 + 4 + 2|4 + 4 + 16 + 16 = 58|60 bytes per pixel.
 #include <cmath>
 
+#include "fixed_sum.hpp"
 #include "internal.hpp"
 
 namespace brush {
 namespace {
 
-constexpr uint32_t kThreads = 256;
+constexpr uint32_t kThreads = kSumThreads;
 // Workgroups of k_depth_loss: four per CU; larger images take further sweeps of the grid-stride loop.
 constexpr uint32_t kMaxDepthRows = 1024;
 constexpr uint32_t kRowWords = 2;  // {sum |r|, valid count}, both float64 (a count below 2^28 is exact)
-constexpr uint64_t kMaxPixels = 1ull << 28;
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // The raw target word as f32, and whether the map holds a measurement there.
 __device__ __forceinline__ bool ld_target(const uint16_t *t, uint32_t i, float &raw) {
@@ -98,33 +87,33 @@ __global__ __launch_bounds__(kThreads) void k_depth_loss(const float4 *__restric
         }
         if (v_depth) v_depth[i] = vD;
     }
-    acc = wave_sum_d(acc);
-    cnt = wave_sum_u(cnt);
+    acc = tree_sum(acc);
+    cnt = tree_sum(cnt);
     if (lane_id() == 0) red_sum[threadIdx.x / kWave] = acc, red_cnt[threadIdx.x / kWave] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) {
-        rows[(size_t)blockIdx.x * kRowWords + 0] = ((red_sum[0] + red_sum[1]) + red_sum[2]) + red_sum[3];
-        rows[(size_t)blockIdx.x * kRowWords + 1] = (double)(((red_cnt[0] + red_cnt[1]) + red_cnt[2]) + red_cnt[3]);
+        rows[(size_t)blockIdx.x * kRowWords + 0] = sum_waves_in_order(red_sum);
+        rows[(size_t)blockIdx.x * kRowWords + 1] = (double)sum_waves_in_order(red_cnt);  // uint32 until here
     }
 }
 
-// Fixed per-thread strides over the rows, the fixed shuffle tree, the four waves in order.
+// Fixed per-thread strides over the rows, the fixed shuffle tree, the four waves in order (fixed_sum.hpp).
 __global__ __launch_bounds__(kThreads) void k_depth_loss_finalize(const double *__restrict__ rows, uint32_t nrows,
                                                                   float c, uint32_t npix, float *__restrict__ stats,
                                                                   float *__restrict__ loss_accum) {
     __shared__ double red[kThreads / kWave][kRowWords];
-    double sum = 0.0, cnt = 0.0;
+    double sum = 0.0, cnt = 0.0;  // block_sum_rows (fixed_sum.hpp) written out: thread 0 takes both words
     for (uint32_t r = threadIdx.x; r < nrows; r += kThreads) {
         sum += rows[(size_t)r * kRowWords + 0];
         cnt += rows[(size_t)r * kRowWords + 1];
     }
-    sum = wave_sum_d(sum);
-    cnt = wave_sum_d(cnt);
+    sum = tree_sum(sum);
+    cnt = tree_sum(cnt);
     if (lane_id() == 0) red[threadIdx.x / kWave][0] = sum, red[threadIdx.x / kWave][1] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double s = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        const double n = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+        const double s = sum_waves_in_order(&red[0][0], kRowWords);
+        const double n = sum_waves_in_order(&red[0][1], kRowWords);
         const float loss = (float)((double)c * s);
         stats[0] = loss;
         stats[1] = (float)(n / (double)npix);
@@ -132,25 +121,8 @@ __global__ __launch_bounds__(kThreads) void k_depth_loss_finalize(const double *
     }
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-uint32_t depth_loss_rows(uint32_t npix) { return min(ceil_div(npix, kThreads), kMaxDepthRows); }
-size_t depth_loss_workspace_bytes(uint32_t npix) {
-    return align_up((size_t)depth_loss_rows(npix) * kRowWords * sizeof(double), 256);
-}
-// w h as a pixel count, or 0 when the image is empty or has 2^28 pixels or more.
-uint32_t checked_pixels(uint32_t w, uint32_t h) {
-    const uint64_t npix = (uint64_t)w * (uint64_t)h;
-    return (npix == 0 || npix >= kMaxPixels) ? 0u : (uint32_t)npix;
-}
-
-template <uint32_t MODE, typename GT>
-void launch_depth_loss(uint32_t nrows, hipStream_t s, const float *pred, const float *depth, const void *target,
-                       const DepthLossArgs &a, uint32_t npix, float *v_depth, float *v_pred, double *rows) {
-    hipLaunchKernelGGL((k_depth_loss<MODE, GT>), dim3(nrows), dim3(kThreads), 0, s,
-                       reinterpret_cast<const float4 *>(pred), depth, static_cast<const GT *>(target), a, npix, v_depth,
-                       v_pred, rows);
-}
+uint32_t depth_loss_rows(uint32_t npix) { return capped_rows(npix, kThreads, kMaxDepthRows); }
+size_t depth_loss_workspace_bytes(uint32_t npix) { return row_bytes(depth_loss_rows(npix), kRowWords); }
 
 }  // namespace
 }  // namespace brush
@@ -183,19 +155,15 @@ extern "C" int brush_depth_loss(const float *pred, const float *depth, const voi
     DepthLossArgs a;
     a.c = (float)((double)cfg->weight / (double)npix);
     a.scale = cfg->scale, a.offset = cfg->offset, a.alpha_min = cfg->alpha_min;
-    if (cfg->mode == BRUSH_DEPTH_LOSS_DEPTH) {
-        if (u16)
-            launch_depth_loss<BRUSH_DEPTH_LOSS_DEPTH, uint16_t>(nrows, s, pred, depth, target, a, npix, v_depth, v_pred, rows);
-        else
-            launch_depth_loss<BRUSH_DEPTH_LOSS_DEPTH, float>(nrows, s, pred, depth, target, a, npix, v_depth, v_pred, rows);
-    } else {
-        if (u16)
-            launch_depth_loss<BRUSH_DEPTH_LOSS_DISPARITY, uint16_t>(nrows, s, pred, depth, target, a, npix, v_depth, v_pred,
-                                                                    rows);
-        else
-            launch_depth_loss<BRUSH_DEPTH_LOSS_DISPARITY, float>(nrows, s, pred, depth, target, a, npix, v_depth, v_pred,
-                                                                 rows);
-    }
+    auto launch = [&](auto mode, auto gt) {  // (mode, target type) -> template arguments, as dispatch_dm
+        using GT = decltype(gt);
+        hipLaunchKernelGGL((k_depth_loss<mode(), GT>), dim3(nrows), dim3(kThreads), 0, s,
+                           reinterpret_cast<const float4 *>(pred), depth, static_cast<const GT *>(target), a, npix,
+                           v_depth, v_pred, rows);
+    };
+    auto by_dtype = [&](auto mode) { u16 ? launch(mode, uint16_t{}) : launch(mode, float{}); };
+    cfg->mode == BRUSH_DEPTH_LOSS_DEPTH ? by_dtype(IntC<BRUSH_DEPTH_LOSS_DEPTH>{})
+                                        : by_dtype(IntC<BRUSH_DEPTH_LOSS_DISPARITY>{});
     hipLaunchKernelGGL(k_depth_loss_finalize, dim3(1), dim3(kThreads), 0, s, rows, nrows, a.c, npix, stats, loss_accum);
     BRUSH_HIP_CHECK(hipGetLastError());
     return BRUSH_OK;

@@ -8,7 +8,8 @@
 //       ring of the last WIN blurred rows.  Reads 4 B of pred and 1 or 4 B of gt per pixel and channel (the halo
 //       re-reads stay in L2); writes 16 B per wave.  Alpha is never read: the reference compares to_rgb8() images,
 //       dropping alpha without blending (eval.rs:50-57).
-//   k_eval_finalize : one workgroup sums the partials in a fixed order (f64) and writes {mse, psnr, ssim}.
+//   k_eval_finalize : one workgroup sums the partials in a fixed order (f64; fixed_sum.hpp, the four waves pairwise)
+//       and writes {mse, psnr, ssim}.
 // No atomics and a fixed reduction order: the same inputs give the same bits on every call and stream.
 #include "internal.hpp"
 #include "ssim_dev.hpp"
@@ -17,13 +18,7 @@ namespace brush {
 namespace {
 
 constexpr float kLn10 = 2.30258509299404568402f;  // std::f32::consts::LN_10
-constexpr int kFinalizeThreads = 256;
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+constexpr int kFinalizeThreads = kSumThreads;
 
 // SSIM map position (oy, ox) for oy in the block's kSegRows rows, ox in the wave's kOutCols columns; the squared error
 // of input pixel (iy, ix) is counted by the wave holding map position (iy+1, ix+1), as k_ssim_forward counts |pred-gt|.
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(192) void k_eval_metrics(const float *__restrict__ 
             pf[2] = pf[1], pf[1] = pf[0], pf[0] = t;
         }
     }
-    msum = wave_sum_d(msum), se = wave_sum_d(se);
+    msum = tree_sum(msum), se = tree_sum(se);
     const uint32_t nwave = gridDim.x * gridDim.y * 3, wv = (blockIdx.y * gridDim.x + blockIdx.x) * 3 + ch;
     if (l == 0) partials[wv] = msum, partials[nwave + wv] = se;
 }
@@ -130,12 +125,12 @@ __global__ __launch_bounds__(kFinalizeThreads) void k_eval_finalize(const double
     __shared__ double red[2][kFinalizeThreads / kWave];
     double ms = 0.0, se = 0.0;
     for (uint32_t i = threadIdx.x; i < nwave; i += kFinalizeThreads) ms += partials[i], se += partials[nwave + i];
-    ms = wave_sum_d(ms), se = wave_sum_d(se);
+    ms = tree_sum(ms), se = tree_sum(se);
     if (lane_id() == 0) red[0][threadIdx.x / kWave] = ms, red[1][threadIdx.x / kWave] = se;
     __syncthreads();
     if (threadIdx.x == 0) {
-        ms = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        se = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        ms = sum_waves_pairwise(red[0]);
+        se = sum_waves_pairwise(red[1]);
         const float mse = (float)(se * inv_rgb_count);
         out[0] = mse;
         out[1] = logf(1.0f / mse) * 10.0f / kLn10;
@@ -154,24 +149,13 @@ void launch_eval(const float *pred, const GT *gt, uint32_t gt_channels, uint32_t
                  double *partials, float *out, hipStream_t s) {
     const Window win = make_window((int)ssim_window);
     uint32_t nwave = 0;
-#define BRUSH_EVAL(W)                                                                                                \
-    do {                                                                                                             \
-        using G = Geo<W>;                                                                                            \
-        const dim3 grid(ceil_div(w + 2, (uint32_t)G::kOutCols), ceil_div(h + 2, (uint32_t)G::kSegRows));             \
-        nwave = grid.x * grid.y * 3;                                                                                 \
-        hipLaunchKernelGGL((k_eval_metrics<W, GT>), grid, dim3(192), 0, s, pred, gt, gt_channels, w, h, win,           \
-                           partials);                                                                                \
-    } while (0)
-    switch (ssim_window) {
-        case 3: BRUSH_EVAL(3); break;
-        case 5: BRUSH_EVAL(5); break;
-        case 7: BRUSH_EVAL(7); break;
-        case 9: BRUSH_EVAL(9); break;
-        case 11: BRUSH_EVAL(11); break;
-        case 13: BRUSH_EVAL(13); break;
-        default: BRUSH_EVAL(15); break;
-    }
-#undef BRUSH_EVAL
+    dispatch_window(ssim_window, [&](auto wc) {
+        using G = Geo<wc()>;
+        const dim3 grid(ceil_div(w + 2, (uint32_t)G::kOutCols), ceil_div(h + 2, (uint32_t)G::kSegRows));
+        nwave = grid.x * grid.y * 3;
+        hipLaunchKernelGGL((k_eval_metrics<wc(), GT>), grid, dim3(192), 0, s, pred, gt, gt_channels, w, h, win,
+                           partials);
+    });
     const double inv_rgb = 1.0 / (3.0 * (double)w * (double)h);
     const double inv_map = 1.0 / (3.0 * (double)(w + 2) * (double)(h + 2));
     hipLaunchKernelGGL(k_eval_finalize, dim3(1), dim3(kFinalizeThreads), 0, s, partials, nwave, inv_rgb, inv_map, out);

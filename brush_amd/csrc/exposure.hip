@@ -8,34 +8,28 @@
 //   k_exposure_forward      : one pixel per lane, one 16-byte load and one 16-byte store; E is 12 wave-uniform words.
 //   k_exposure_backward     : one pixel per lane, grid-stride; writes v_pred (may alias v_out: a lane reads its pixel
 //       before it writes it) and carries 12 float64 accumulators, each product (double) v' * (double) p exact, added in
-//       loop order; then the reduction of pose_grad.hip: a fixed shuffle tree per wave, the four waves through LDS in
+//       loop order; then block_sum_words (fixed_sum.hpp): a fixed shuffle tree per wave, the four waves through LDS in
 //       wave order, one row of 12 doubles per workgroup with ordinary stores.
-//   k_exposure_finalize<ADAM>: one workgroup sums the rows at fixed strides through the same tree and writes the 12
-//       words as f32, zeros included; with ADAM it then adds the penalty reg (E - [I|0]) and steps m1, m2 and E of the
-//       view in place, in float64 from the stored f32 words, each stored word rounded once.
+//   k_exposure_finalize<ADAM>: one workgroup sums the rows at fixed strides through the same tree (block_sum_rows) and
+//       writes the 12 words as f32, zeros included; with ADAM it then adds the penalty reg (E - [I|0]) and steps m1, m2
+//       and E of the view in place, in float64 from the stored f32 words, each stored word rounded once.
 // No atomics, no counters, no allocation, no synchronisation: graph-capturable, and the same inputs give the same bits
 // on every call.  The grids are functions of w h alone.  Compiled with -ffp-contract=off.
 // Roofline: HBM streams (forward 16 B read + 16 B written per pixel; backward 32 B read + 16 B written).
 #include <cmath>
 
+#include "fixed_sum.hpp"
 #include "internal.hpp"
 
 namespace brush {
 namespace {
 
-constexpr uint32_t kThreads = 256;
+constexpr uint32_t kThreads = kSumThreads;
 constexpr uint32_t kExpWords = 12;       // row-major 3x4: [A row c | b_c]
 // Workgroups of k_exposure_backward: two per CU.  The wave reduction behind the loop is 144 LDS-crossbar shuffles per
 // wave whatever the image, so more workgroups cost more than they hide (1080p: 24.6 us at 2048, 21.3 at 1024, 18.2 at
 // 512, 19.4 at 256).
 constexpr uint32_t kMaxExpRows = 512;
-constexpr uint64_t kMaxPixels = 1ull << 28;
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void k_exposure_forward(const float4 *__restrict__ pred,
                                                                const float *__restrict__ E, uint32_t npix,
@@ -55,7 +49,6 @@ __global__ __launch_bounds__(kThreads) void k_exposure_forward(const float4 *__r
 __global__ __launch_bounds__(kThreads) void k_exposure_backward(const float4 *__restrict__ pred, const float4 *v_out,
                                                                 const float *__restrict__ E, uint32_t npix,
                                                                 float4 *v_pred, double *__restrict__ rows) {
-    __shared__ double red[kThreads / kWave][kExpWords];
     float e[kExpWords];
 #pragma unroll
     for (uint32_t i = 0; i < kExpWords; i++) e[i] = E[i];
@@ -79,16 +72,7 @@ __global__ __launch_bounds__(kThreads) void k_exposure_backward(const float4 *__
             for (int k = 0; k < 4; k++) acc[c * 4 + k] += vc[c] * pk[k];
         }
     }
-#pragma unroll
-    for (uint32_t i = 0; i < kExpWords; i++) acc[i] = wave_sum_d(acc[i]);
-    if (lane_id() == 0) {
-#pragma unroll
-        for (uint32_t i = 0; i < kExpWords; i++) red[threadIdx.x / kWave][i] = acc[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < kExpWords)
-        rows[(size_t)blockIdx.x * kExpWords + threadIdx.x] =
-            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    block_sum_words(acc, [&](uint32_t t, double sum) { rows[(size_t)blockIdx.x * kExpWords + t] = sum; });
 }
 
 struct ExposureAdam {
@@ -96,28 +80,12 @@ struct ExposureAdam {
     double lr, beta1, beta2, eps, reg, bc1, bc2;  // bc = 1 - beta^time
 };
 
-// Fixed per-thread strides over the rows, the fixed shuffle tree, the four waves in order: all 12 words every call.
+// block_sum_rows: fixed per-thread strides over the rows, the fixed shuffle tree, the four waves in order: all 12 words
+// every call.
 template <bool ADAM>
 __global__ __launch_bounds__(kThreads) void k_exposure_finalize(const double *__restrict__ rows, uint32_t nrows,
                                                                 float *__restrict__ v_exposure, const ExposureAdam a) {
-    __shared__ double red[kThreads / kWave][kExpWords];
-    double acc[kExpWords];
-#pragma unroll
-    for (uint32_t i = 0; i < kExpWords; i++) acc[i] = 0.0;
-    for (uint32_t r = threadIdx.x; r < nrows; r += kThreads) {
-#pragma unroll
-        for (uint32_t i = 0; i < kExpWords; i++) acc[i] += rows[(size_t)r * kExpWords + i];
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kExpWords; i++) acc[i] = wave_sum_d(acc[i]);
-    if (lane_id() == 0) {
-#pragma unroll
-        for (uint32_t i = 0; i < kExpWords; i++) red[threadIdx.x / kWave][i] = acc[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < kExpWords) {
-        const uint32_t t = threadIdx.x;
-        const double sum = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    block_sum_rows<kExpWords>(rows, nrows, [&](uint32_t t, double sum) {
         v_exposure[t] = (float)sum;
         if constexpr (ADAM) {
             const double x = (double)a.E[t];
@@ -129,20 +97,11 @@ __global__ __launch_bounds__(kThreads) void k_exposure_finalize(const double *__
             a.m2[t] = (float)v;
             a.E[t] = (float)(x - a.lr * (m / a.bc1) / (sqrt(v / a.bc2) + a.eps));
         }
-    }
+    });
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-uint32_t exposure_rows(uint32_t npix) { return min(ceil_div(npix, kThreads), kMaxExpRows); }
-size_t exposure_workspace_bytes(uint32_t npix) {
-    return align_up((size_t)exposure_rows(npix) * kExpWords * sizeof(double), 256);
-}
-// w h as a pixel count, or 0 when the image is empty or has 2^28 pixels or more.
-uint32_t checked_pixels(uint32_t w, uint32_t h) {
-    const uint64_t npix = (uint64_t)w * (uint64_t)h;
-    return (npix == 0 || npix >= kMaxPixels) ? 0u : (uint32_t)npix;
-}
+uint32_t exposure_rows(uint32_t npix) { return capped_rows(npix, kThreads, kMaxExpRows); }
+size_t exposure_workspace_bytes(uint32_t npix) { return row_bytes(exposure_rows(npix), kExpWords); }
 
 int backward_common(const float *pred, const float *v_out, const float *exposure, uint32_t w, uint32_t h, float *v_pred,
                     float *v_exposure, void *workspace, size_t workspace_bytes, const ExposureAdam *adam,

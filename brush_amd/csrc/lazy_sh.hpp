@@ -30,9 +30,8 @@ inline bool make_lazy_sh(const BrushLazySh *l, uint32_t sh_degree, LazySh *out) 
     *out = LazySh{};
     if (!l) return true;
     const uint32_t row = 3u * (sh_degree + 1u) * (sh_degree + 1u);
-    auto aligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if ((row & 3u) != 0u || !l->table || !l->sh_time || !l->sh_moment1 || !l->sh_moment2) return false;
-    if (!aligned(l->table) || !aligned(l->sh_moment1) || !aligned(l->sh_moment2)) return false;
+    if (misaligned(l->table, 16) || misaligned(l->sh_moment1, 16) || misaligned(l->sh_moment2, 16)) return false;
     if (l->now < l->base || l->now - l->base > l->capacity) return false;  // every pending time has its table row
     out->table = reinterpret_cast<const float4 *>(l->table);
     out->base = l->base, out->now = l->now;

@@ -130,8 +130,6 @@ __global__ __launch_bounds__(256) void k_mcmc_relocation(const float *__restrict
     raw_out[g] = (float)logit;
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 }  // namespace
 }  // namespace brush
 

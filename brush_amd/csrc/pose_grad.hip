@@ -9,27 +9,23 @@
 // piecewise constant.
 //
 //   k_view_grad<AA>      : one lane per visible splat in compact order, grid-stride; 12 float64 accumulators per lane,
-//       added in loop order; a fixed shuffle tree per wave, the four waves of a workgroup through LDS in wave order; one
-//       row of 12 doubles per workgroup.  Reads the compact-order sums the way the parameter VJP does (det_sums.hpp), so
-//       the atomic and the deterministic layout both work.  ~100 B gathered per visible splat.
+//       added in loop order; then block_sum_words (fixed_sum.hpp): a fixed shuffle tree per wave, the four waves of a
+//       workgroup through LDS in wave order; one row of 12 doubles per workgroup.  Reads the compact-order sums the way
+//       the parameter VJP does (det_sums.hpp), so the atomic and the deterministic layout both work.  ~100 B gathered
+//       per visible splat.
 //   k_view_grad_finalize : one workgroup sums the rows in a fixed order and writes the 12 words as f32, zeros included.
 // No atomics, no counters to reset, no allocation, no synchronisation: graph-capturable, and the same inputs give the
 // same bits on every call.  The grid is a function of n alone.  Compiled with -ffp-contract=off like the parameter VJP.
 #include "det_sums.hpp"
+#include "fixed_sum.hpp"
 #include "splat_vjp.hpp"
 
 namespace brush {
 namespace {
 
-constexpr uint32_t kThreads = 256;
+constexpr uint32_t kThreads = kSumThreads;
 constexpr uint32_t kPoseWords = 12;      // row-major 3x4: [v_W row r | v_t_view[r]]
 constexpr uint32_t kMaxPoseRows = 2048;  // workgroups of k_view_grad
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <bool AA>
 __global__ __launch_bounds__(kThreads) void k_view_grad(
@@ -37,7 +33,6 @@ __global__ __launch_bounds__(kThreads) void k_view_grad(
     const float *__restrict__ quats, const float *__restrict__ raw_opac, const uint32_t *__restrict__ num_visible,
     uint32_t n, const uint32_t *__restrict__ global_from_compact, const float *__restrict__ v_compact, const DetSums det,
     uint32_t has_depth, double *__restrict__ rows) {
-    __shared__ double red[kThreads / kWave][kPoseWords];
     const uint32_t V = min(*num_visible, n);
     double acc[kPoseWords];
 #pragma unroll
@@ -69,48 +64,21 @@ __global__ __launch_bounds__(kThreads) void k_view_grad(
             acc[a * 4 + 3] += (double)pt.v_p[a];
         }
     }
-#pragma unroll
-    for (uint32_t i = 0; i < kPoseWords; i++) acc[i] = wave_sum_d(acc[i]);
-    if (lane_id() == 0) {
-#pragma unroll
-        for (uint32_t i = 0; i < kPoseWords; i++) red[threadIdx.x / kWave][i] = acc[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < kPoseWords)
-        rows[(size_t)blockIdx.x * kPoseWords + threadIdx.x] =
-            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    block_sum_words(acc, [&](uint32_t t, double sum) { rows[(size_t)blockIdx.x * kPoseWords + t] = sum; });
 }
 
-// Fixed per-thread strides over the rows, the fixed shuffle tree, the four waves in order: all 12 words every call.
+// block_sum_rows: fixed per-thread strides over the rows, the fixed shuffle tree, the four waves in order: all 12 words
+// every call.
 __global__ __launch_bounds__(kThreads) void k_view_grad_finalize(const double *__restrict__ rows, uint32_t nrows,
                                                                  float *__restrict__ v_viewmat) {
-    __shared__ double red[kThreads / kWave][kPoseWords];
-    double acc[kPoseWords];
-#pragma unroll
-    for (uint32_t i = 0; i < kPoseWords; i++) acc[i] = 0.0;
-    for (uint32_t r = threadIdx.x; r < nrows; r += kThreads) {
-#pragma unroll
-        for (uint32_t i = 0; i < kPoseWords; i++) acc[i] += rows[(size_t)r * kPoseWords + i];
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kPoseWords; i++) acc[i] = wave_sum_d(acc[i]);
-    if (lane_id() == 0) {
-#pragma unroll
-        for (uint32_t i = 0; i < kPoseWords; i++) red[threadIdx.x / kWave][i] = acc[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < kPoseWords)
-        v_viewmat[threadIdx.x] =
-            (float)(((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x]);
+    block_sum_rows<kPoseWords>(rows, nrows, [&](uint32_t t, double sum) { v_viewmat[t] = (float)sum; });
 }
 
 }  // namespace
 
-uint32_t pose_grad_rows(uint32_t n) { return min(ceil_div(n, kThreads), kMaxPoseRows); }
+uint32_t pose_grad_rows(uint32_t n) { return capped_rows(n, kThreads, kMaxPoseRows); }
 
-size_t pose_grad_workspace_bytes(uint32_t n) {
-    return align_up((size_t)max(pose_grad_rows(n), 1u) * kPoseWords * sizeof(double), 256);
-}
+size_t pose_grad_workspace_bytes(uint32_t n) { return row_bytes(max(pose_grad_rows(n), 1u), kPoseWords); }
 
 hipError_t launch_view_grad(const ViewParams &vp, const float *means, const float *log_scales, const float *quats,
                             const float *raw_opac, const uint32_t *num_visible, uint32_t n,

@@ -528,7 +528,7 @@ bool make_zero_fill(ZeroFill *zf, float *const *arrays, const size_t *floats, ui
         zf->first_block[i] = (uint32_t)blocks;
         if (i >= count || !arrays[i] || floats[i] == 0) continue;
         const uint64_t chunks = floats[i] / 4u;
-        if ((reinterpret_cast<uintptr_t>(arrays[i]) & 15u) != 0 || chunks >= (1ull << 32) - 64u)
+        if (misaligned(arrays[i], 16) || chunks >= (1ull << 32) - 64u)
             return fail();
         zf->base[i] = arrays[i];
         zf->full[i] = (uint32_t)chunks;

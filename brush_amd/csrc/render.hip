@@ -445,7 +445,7 @@ static bool fill_adam_fuse(const BrushAdamConfig *cfg, float *means, float *log_
                            uint32_t sh_degree, AdamFuse *out) {
     if (!cfg || cfg->time == 0) return false;
     if (n > 0 && (!means || !log_scales || !rotation || !raw_opacity || !sh || !moment1 || !moment2)) return false;
-    auto aligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    auto aligned = [](const void *p) { return !misaligned(p, 16); };
     if (!aligned(rotation) || (next_quats_fed && !aligned(next_quats_fed))) return false;
     if ((grad_2d_accum == nullptr) != (xy_grad_counts == nullptr)) return false;
     AdamFuse af{};
@@ -523,7 +523,7 @@ static int render_backward_adam_impl(const BrushUniforms *h_uniforms, const Brus
                                      size_t workspace_bytes, brush_stream_t stream, float *v_viewmat,
                                      void *pose_ws) {
     if (!cfg || cfg->time == 0 || !h_uniforms || h_uniforms->sh_degree > 4) return BRUSH_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(quats_fed) & 15) != 0) return BRUSH_ERR_INVALID_ARG;
+    if (misaligned(quats_fed, 16)) return BRUSH_ERR_INVALID_ARG;
     AdamFuse af{};
     if (!fill_adam_fuse(cfg, means, log_scales, rotation, raw_opacity, sh, n, moment1, moment2, next_quats_fed,
                         grad_2d_accum, xy_grad_counts, h_uniforms->img_size[0], h_uniforms->img_size[1],
@@ -572,7 +572,7 @@ extern "C" int brush_render_backward_records(const BrushUniforms *h_uniforms, co
         return BRUSH_ERR_INVALID_ARG;
     if (n > 0 && (!means || !log_scales || !quats || !raw_opacity || (max_rows > 0 && !records)))
         return BRUSH_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(records) & 15) != 0) return BRUSH_ERR_INVALID_ARG;
+    if (misaligned(records, 16)) return BRUSH_ERR_INVALID_ARG;
     if (h_aux->flags & BRUSH_AUX_ANTIALIASED) return BRUSH_ERR_INVALID_ARG;  // out of scope (brush_hip.h)
     const BrushAux &aux = *h_aux;
     const BwdWs ws = carve_bwd(workspace, n, aux.max_intersects, aux_det(aux));
@@ -607,7 +607,7 @@ static int reduce_views_impl(const float *records, uint32_t num_views, uint32_t 
     if (sh_degree > 4 || num_views == 0) return BRUSH_ERR_INVALID_ARG;
     if (n == 0) return BRUSH_OK;
     if (!means || !view_index || !view_rows || !campos || (rows_per_view > 0 && !records)) return BRUSH_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(records) & 15) != 0) return BRUSH_ERR_INVALID_ARG;
+    if (misaligned(records, 16)) return BRUSH_ERR_INVALID_ARG;
     if (!adam && (!v_means || !v_scales || !v_quats || !v_sh || !v_opac)) return BRUSH_ERR_INVALID_ARG;
     if (view_index_bytes < sizeof(uint32_t) * (size_t)n * num_views) return BRUSH_ERR_WORKSPACE_SMALL;
     if (!view_offsets && (uint64_t)num_views * rows_per_view > 0xFFFFFFFFull) return BRUSH_ERR_INVALID_ARG;
@@ -649,7 +649,7 @@ extern "C" int brush_lazy_sh_flush(const BrushLazySh *h_lazy, float *sh, uint32_
     LazySh lazy;
     if (!h_lazy || sh_degree > 4 || !make_lazy_sh(h_lazy, sh_degree, &lazy)) return BRUSH_ERR_INVALID_ARG;
     if (n == 0) return BRUSH_OK;
-    if (!sh || (reinterpret_cast<uintptr_t>(sh) & 15) != 0) return BRUSH_ERR_INVALID_ARG;
+    if (!sh || misaligned(sh, 16)) return BRUSH_ERR_INVALID_ARG;
     BRUSH_HIP_CHECK(launch_lazy_sh_flush(lazy, sh, n, 3u * (sh_degree + 1u) * (sh_degree + 1u),
                                          static_cast<hipStream_t>(stream)));
     return BRUSH_OK;

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const uint32_t *__
     BRUSH_KTRACE(kTrScanReduce, 0);
     const uint32_t valid_n = d_valid_n ? min(*d_valid_n, n) : n;
     BRUSH_KTRACE_MARK(1, valid_n);
-    const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15u) == 0;
+    const bool aligned = !misaligned(in, 16);
     const uint32_t idx = blockIdx.x * kScanTile + threadIdx.x * 4;
     const uint4 v = load_tile4(in, idx, n, valid_n, aligned);
     uint32_t s = v.x + v.y + v.z + v.w;
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_down(const uint32_t *__re
         if (lane_id() == 0) pre_s[threadIdx.x / kWave] = before;
     }
     const uint32_t valid_n = d_valid_n ? min(*d_valid_n, n) : n;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
+    const bool aligned = !misaligned(in, 16) && !misaligned(out, 16);
     const uint32_t idx = blockIdx.x * kScanTile + threadIdx.x * 4;
     BRUSH_KTRACE_MARK(2, valid_n);
     uint4 v = load_tile4(in, idx, n, valid_n, aligned);

@@ -1,8 +1,9 @@
 // ssim_dev.hpp — the pieces of the separable SSIM blur shared by the training loss (train_step.hip) and the
 // metrics-only evaluation pass (eval.hip): the window and its geometry, the wave-uniform-row loads (ground truth as f32
-// or u8), the wave reduction.
+// or u8), the window dispatch.  The wave reduction is tree_sum of fixed_sum.hpp.
 #pragma once
-#include "common.hpp"
+#include "fixed_sum.hpp"
+#include "internal.hpp"
 
 namespace brush {
 namespace {
@@ -24,12 +25,6 @@ constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 struct Window {
     float g[kMaxWin];
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // Element at a wave-uniform base plus a per-lane BYTE offset below 4 GiB: global_load/store with an SGPR base and a
 // 32-bit VGPR offset, no 64-bit vector address arithmetic.
@@ -69,6 +64,20 @@ Window make_window(int n) {
 }
 
 inline bool window_ok(uint32_t n) { return n >= 3 && n <= (uint32_t)kMaxWin && (n & 1u); }
+// Runtime window (window_ok) -> the WIN template argument of a kernel launch: f receives an IntC<WIN>, as
+// dispatch_degree (internal.hpp).
+template <typename F>
+void dispatch_window(uint32_t n, F &&f) {
+    switch (n) {
+        case 3: return f(IntC<3>{});
+        case 5: return f(IntC<5>{});
+        case 7: return f(IntC<7>{});
+        case 9: return f(IntC<9>{});
+        case 11: return f(IntC<11>{});
+        case 13: return f(IntC<13>{});
+        default: return f(IntC<15>{});
+    }
+}
 
 }  // namespace
 }  // namespace brush

@@ -27,11 +27,11 @@ namespace {
 
 // Sum over the 256 threads of a block in a fixed order (deterministic); valid in thread 0.
 __device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
+    v = tree_sum(v);
     if (lane_id() == 0) red[threadIdx.x / kWave] = v;
     __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
+    const float r = sum_waves_pairwise(red);
+    __syncthreads();  // red may be staged again
     return r;
 }
 
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(192) void k_ssim_forward(const float *__restrict__ 
             pf[2] = pf[1], pf[1] = pf[0], pf[0] = t;
         }
     }
-    msum = wave_sum(msum), l1 = wave_sum(l1);
+    msum = tree_sum(msum), l1 = tree_sum(l1);
     const uint32_t nwave = gridDim.x * gridDim.y * 3, wv = (blockIdx.y * gridDim.x + blockIdx.x) * 3 + ch;
     if (l == 0) partials[wv] = msum, partials[nwave + wv] = l1;
 }
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(192) void k_ssim_backward(const float *__restrict__
     if (blockIdx.x == 0 && blockIdx.y == 0 && ch == 0) {
         float ms = 0.0f, ls = 0.0f;
         for (uint32_t i = l; i < nwave_fwd; i += kWave) ms += partials[i], ls += partials[nwave_fwd + i];
-        ms = wave_sum(ms), ls = wave_sum(ls);
+        ms = tree_sum(ms), ls = tree_sum(ls);
         if (l == 0) loss[0] = ls * inv_l1_count * l1_weight - ms * inv_ssim_count * ssim_weight;
     }
 }
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(64) void k_l1_finalize(const float *__restrict__ pa
                                                     float *__restrict__ loss) {
     float s = 0.0f;
     for (uint32_t i = threadIdx.x; i < nblk; i += kWave) s += partials[i];
-    s = wave_sum(s);
+    s = tree_sum(s);
     if (threadIdx.x == 0) loss[0] = s * inv_count;
 }
 
@@ -327,7 +327,7 @@ extern "C" int brush_loss_workspace_size(uint32_t w, uint32_t h, size_t *bytes) 
 namespace brush {
 namespace {
 
-// Argument checks shared by both loss entry points (the workspace size is checked by the caller).
+// Argument checks of the loss entry points (the dtype and the workspace size are checked by the caller, in that order).
 int loss_args_ok(const float *pred, const void *gt, uint32_t w, uint32_t h, uint32_t gt_channels, float ssim_weight,
                  uint32_t ssim_window, const float *loss, const float *v_pred, const void *workspace) {
     if (!pred || !gt || !loss || !v_pred || !workspace || w == 0 || h == 0) return BRUSH_ERR_INVALID_ARG;
@@ -355,27 +355,16 @@ void launch_loss(const float *pred, const GT *gt, uint32_t w, uint32_t h, uint32
     }
     const Window win = make_window((int)ssim_window);
     const float inv_ssim = 1.0f / (3.0f * (float)plane);
-#define BRUSH_SSIM(W)                                                                                                \
-    do {                                                                                                             \
-        using G = Geo<W>;                                                                                            \
-        const dim3 gf(ceil_div(w + 2, (uint32_t)G::kOutCols), ceil_div(h + 2, (uint32_t)G::kSegRows));               \
-        const dim3 gb(ceil_div(w, (uint32_t)G::kOutCols), ceil_div(h, (uint32_t)G::kSegRows));                       \
-        hipLaunchKernelGGL((k_ssim_forward<W, GT>), gf, dim3(192), 0, s, pred, gt, gt_channels, w, h, win,           \
-                           -ssim_weight * inv_ssim * grad_scale, dmaps, partials);                                   \
-        hipLaunchKernelGGL((k_ssim_backward<W, GT>), gb, dim3(192), 0, s, pred, gt, gt_channels, w, h, win, dmaps,   \
-                           (1.0f - ssim_weight) * inv_l1 * grad_scale, v_pred, partials, gf.x * gf.y * 3,            \
-                           1.0f - ssim_weight, ssim_weight, inv_l1, inv_ssim, loss);                                 \
-    } while (0)
-    switch (ssim_window) {
-        case 3: BRUSH_SSIM(3); break;
-        case 5: BRUSH_SSIM(5); break;
-        case 7: BRUSH_SSIM(7); break;
-        case 9: BRUSH_SSIM(9); break;
-        case 11: BRUSH_SSIM(11); break;
-        case 13: BRUSH_SSIM(13); break;
-        default: BRUSH_SSIM(15); break;
-    }
-#undef BRUSH_SSIM
+    dispatch_window(ssim_window, [&](auto wc) {
+        using G = Geo<wc()>;
+        const dim3 gf(ceil_div(w + 2, (uint32_t)G::kOutCols), ceil_div(h + 2, (uint32_t)G::kSegRows));
+        const dim3 gb(ceil_div(w, (uint32_t)G::kOutCols), ceil_div(h, (uint32_t)G::kSegRows));
+        hipLaunchKernelGGL((k_ssim_forward<wc(), GT>), gf, dim3(192), 0, s, pred, gt, gt_channels, w, h, win,
+                           -ssim_weight * inv_ssim * grad_scale, dmaps, partials);
+        hipLaunchKernelGGL((k_ssim_backward<wc(), GT>), gb, dim3(192), 0, s, pred, gt, gt_channels, w, h, win, dmaps,
+                           (1.0f - ssim_weight) * inv_l1 * grad_scale, v_pred, partials, gf.x * gf.y * 3,
+                           1.0f - ssim_weight, ssim_weight, inv_l1, inv_ssim, loss);
+    });
 }
 
 }  // namespace
@@ -384,15 +373,8 @@ void launch_loss(const float *pred, const GT *gt, uint32_t w, uint32_t h, uint32
 extern "C" int brush_l1_ssim_loss(const float *pred, const float *gt, uint32_t w, uint32_t h, uint32_t gt_channels,
                                   float ssim_weight, uint32_t ssim_window, float grad_scale, float *loss,
                                   float *v_pred, void *workspace, size_t workspace_bytes, brush_stream_t stream) {
-    const int st = loss_args_ok(pred, gt, w, h, gt_channels, ssim_weight, ssim_window, loss, v_pred, workspace);
-    if (st != BRUSH_OK) return st;
-    size_t need = 0;
-    brush_loss_workspace_size(w, h, &need);
-    if (workspace_bytes < need) return BRUSH_ERR_WORKSPACE_SMALL;
-    launch_loss(pred, gt, w, h, gt_channels, ssim_weight, ssim_window, grad_scale, loss, v_pred, workspace,
-                static_cast<hipStream_t>(stream));
-    BRUSH_HIP_CHECK(hipGetLastError());
-    return BRUSH_OK;
+    return brush_l1_ssim_loss_gt(pred, gt, BRUSH_EVAL_GT_F32, w, h, gt_channels, ssim_weight, ssim_window, grad_scale,
+                                 loss, v_pred, workspace, workspace_bytes, stream);
 }
 
 extern "C" int brush_l1_ssim_loss_gt(const float *pred, const void *gt, uint32_t gt_dtype, uint32_t w, uint32_t h,

@@ -31,10 +31,7 @@ DEFAULT_ALPHA_MIN = 0.5
 
 
 def workspace_bytes(w: int, h: int) -> int:
-    n = C.c_size_t()
-    _lib.check(_lib.lib().brush_depth_loss_workspace_size(int(w), int(h), C.byref(n)),
-               "brush_depth_loss_workspace_size")
-    return n.value
+    return _lib.size_query("brush_depth_loss_workspace_size", int(w), int(h))
 
 
 def _mode(mode: str) -> int:
@@ -96,7 +93,7 @@ def depth_loss_into(pred: torch.Tensor, depth: torch.Tensor, target: torch.Tenso
             pred.data_ptr(), depth.data_ptr(), target.data_ptr(), C.byref(cfg), w, h,
             None if v_depth is None else v_depth.data_ptr(), None if v_pred is None else v_pred.data_ptr(),
             stats.data_ptr(), None if loss_accum is None else loss_accum.data_ptr(), workspace.data_ptr(),
-            workspace.numel() * workspace.element_size(), torch.cuda.current_stream(dev).cuda_stream),
+            workspace.numel() * workspace.element_size(), _lib.current_stream(dev)),
             "brush_depth_loss")
     return v_depth, stats
 

@@ -259,16 +259,15 @@ class ViewExchange:
         l = _lib.lib()
         n = means.shape[0]
         w, h = int(u.img_size[0]), int(u.img_size[1])
-        nbytes = C.c_size_t()
-        _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, int(u.sh_degree), int(aux.max_intersects), int(aux.flags),
-                                                    C.byref(nbytes)), "brush_bwd_workspace_size_flags")
-        self._ws, s = aux.backward_workspace(nbytes.value, self.device)
+        nbytes = _lib.size_query("brush_bwd_workspace_size_flags", n, w, h, int(u.sh_degree), int(aux.max_intersects),
+                                 int(aux.flags))
+        self._ws, s = aux.backward_workspace(nbytes, self.device)
         with torch.cuda.device(self.device):
             _lib.check(l.brush_render_backward_records(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
                                                        quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
                                                        v_out.contiguous().data_ptr(), self.local.data_ptr(), self.capacity,
-                                                       self._ws.data_ptr(), nbytes.value,
-                                                       torch.cuda.current_stream().cuda_stream),
+                                                       self._ws.data_ptr(), nbytes,
+                                                       _lib.current_stream()),
                        "brush_render_backward_records")
 
     def set_local_records(self, rec: torch.Tensor):
@@ -334,21 +333,20 @@ class ViewExchange:
 
         from . import _lib
 
-        nbytes = C.c_size_t()
-        _lib.check(_lib.lib().brush_view_index_size(n, self.world, C.byref(nbytes)), "brush_view_index_size")
-        if self.index is None or n != self.n or self.index.numel() < nbytes.value:
+        nbytes = _lib.size_query("brush_view_index_size", n, self.world)
+        if self.index is None or n != self.n or self.index.numel() < nbytes:
             # The splat count follows the PARAMETERS of the call, not the count this object was built with: refinement
             # (train.rs:395-579) clones, splits and prunes between steps, and the index is laid out [view][n].
             # all-ones = "no row": the reduction clears what it consumes, so the buffer never holds stale entries
             self.n = int(n)
-            self.index = torch.full((nbytes.value,), 0xFF, dtype=torch.uint8, device=self.device)
+            self.index = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=self.device)
         if self.packed:
             recs = self.gathered[:max(self._rows, 1) * _REC]
         else:
             recs = self.gathered[:self.world * self._rows * _REC]
         view_rows = self.metas[:, 0].contiguous()
         campos = self.metas[:, 1:4].contiguous().view(torch.float32)
-        return recs, view_rows, campos, nbytes.value
+        return recs, view_rows, campos, nbytes
 
     def _offsets_ptr(self):
         return self._offsets_dev.data_ptr() if self.packed else None
@@ -368,7 +366,7 @@ class ViewExchange:
                 recs.data_ptr(), self.world, self._rows, view_rows.data_ptr(), self._offsets_ptr(), campos.data_ptr(),
                 means.data_ptr(), n, self.degree, _seg_ptr(block, layout, "v_means"), _seg_ptr(block, layout, "v_scales"),
                 _seg_ptr(block, layout, "v_quats"), _seg_ptr(block, layout, "v_sh"), _seg_ptr(block, layout, "v_opac"),
-                self.index.data_ptr(), ibytes, torch.cuda.current_stream().cuda_stream), "brush_reduce_view_records")
+                self.index.data_ptr(), ibytes, _lib.current_stream()), "brush_reduce_view_records")
         self._keep = (view_rows, campos)  # alive until the kernel has run
 
         def seg(name, shape):
@@ -397,7 +395,7 @@ class ViewExchange:
                 int(img_size[0]), int(img_size[1]), means.data_ptr(), log_scales.data_ptr(), rotation.data_ptr(),
                 raw_opacity.data_ptr(), sh.data_ptr(), n, self.degree, moment1.data_ptr(), moment2.data_ptr(),
                 ptr(next_quats_fed), ptr(grad_2d_accum), ptr(xy_grad_counts), self.index.data_ptr(), ibytes,
-                torch.cuda.current_stream().cuda_stream), "brush_reduce_view_records_adam")
+                _lib.current_stream()), "brush_reduce_view_records_adam")
         self._keep = (view_rows, campos)
 
 

@@ -16,7 +16,6 @@ scale, and a `scales` list in --json.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -51,13 +50,12 @@ def eval_metrics(pred: torch.Tensor, gt: torch.Tensor, window: int = 11,
         raise ValueError("out must be a contiguous float32 [3] tensor on pred's device")
     pred, gt = pred.contiguous(), gt.contiguous()
     l = _lib.lib()
-    nbytes = C.c_size_t()
-    _lib.check(l.brush_eval_workspace_size(w, h, C.byref(nbytes)), "brush_eval_workspace_size")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=pred.device)
+    nbytes = _lib.size_query("brush_eval_workspace_size", w, h)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     with torch.cuda.device(pred.device):
         _lib.check(l.brush_eval_metrics(pred.data_ptr(), gt.data_ptr(), dtypes[gt.dtype], w, h, int(gt.shape[2]),
-                                        int(window), out.data_ptr(), ws.data_ptr(), nbytes.value,
-                                        torch.cuda.current_stream().cuda_stream),
+                                        int(window), out.data_ptr(), ws.data_ptr(), nbytes,
+                                        _lib.current_stream()),
                    "brush_eval_metrics")
     return out
 

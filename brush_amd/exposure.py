@@ -34,13 +34,7 @@ def _check_image(img: torch.Tensor, what: str):
 
 
 def workspace_bytes(w: int, h: int) -> int:
-    n = C.c_size_t()
-    _lib.check(_lib.lib().brush_exposure_workspace_size(int(w), int(h), C.byref(n)), "brush_exposure_workspace_size")
-    return n.value
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
+    return _lib.size_query("brush_exposure_workspace_size", int(w), int(h))
 
 
 class _ApplyExposure(torch.autograd.Function):
@@ -54,7 +48,7 @@ class _ApplyExposure(torch.autograd.Function):
         out = torch.empty_like(img_c)
         with torch.cuda.device(img_c.device):
             _lib.check(_lib.lib().brush_exposure_forward(img_c.data_ptr(), e_c.data_ptr(), w, h, out.data_ptr(),
-                                                         _stream(img_c.device)), "brush_exposure_forward")
+                                                         _lib.current_stream(img_c.device)), "brush_exposure_forward")
         ctx.save_for_backward(img_c, e_c)
         ctx.e_shape = tuple(E.shape)
         return out
@@ -71,7 +65,7 @@ class _ApplyExposure(torch.autograd.Function):
         with torch.cuda.device(img_c.device):
             _lib.check(_lib.lib().brush_exposure_backward(img_c.data_ptr(), v_out.data_ptr(), e_c.data_ptr(), w, h,
                                                           v_img.data_ptr(), v_e.data_ptr(), ws.data_ptr(), nbytes,
-                                                          _stream(img_c.device)), "brush_exposure_backward")
+                                                          _lib.current_stream(img_c.device)), "brush_exposure_backward")
         return v_img, v_e.reshape(ctx.e_shape)
 
 
@@ -126,7 +120,7 @@ class ExposureTable:
         self._buffers(w, h)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().brush_exposure_forward(pred.data_ptr(), self.params.data_ptr() + 48 * i, w, h,
-                                                         self._out.data_ptr(), _stream(self.device)),
+                                                         self._out.data_ptr(), _lib.current_stream(self.device)),
                        "brush_exposure_forward")
         return self._out
 
@@ -146,7 +140,7 @@ class ExposureTable:
             _lib.check(_lib.lib().brush_exposure_backward_adam(
                 pred.data_ptr(), v_out.data_ptr(), C.byref(cfg), w, h, v_out.data_ptr(),
                 self.params.data_ptr() + 48 * i, self.moment1.data_ptr() + 48 * i, self.moment2.data_ptr() + 48 * i,
-                self.v_exposure.data_ptr(), self._ws.data_ptr(), self._ws_bytes, _stream(self.device)),
+                self.v_exposure.data_ptr(), self._ws.data_ptr(), self._ws_bytes, _lib.current_stream(self.device)),
                 "brush_exposure_backward_adam")
         return v_out
 

@@ -57,7 +57,7 @@ def relocation(raw_opacity: torch.Tensor, log_scales: torch.Tensor, ratio: torch
     with torch.cuda.device(raw_opacity.device):
         _lib.check(_lib.lib().brush_mcmc_relocation(raw_opacity.data_ptr(), log_scales.data_ptr(), ratio.data_ptr(), m,
                                                     float(min_opacity), new_raw.data_ptr(), new_scales.data_ptr(),
-                                                    torch.cuda.current_stream().cuda_stream), "brush_mcmc_relocation")
+                                                    _lib.current_stream()), "brush_mcmc_relocation")
     return new_raw, new_scales
 
 

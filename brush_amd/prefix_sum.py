@@ -1,7 +1,6 @@
 """prefix_sum — mirror of crates/brush-prefix-sum/src/lib.rs:17 over the HIP C ABI."""
 from __future__ import annotations
 
-import ctypes as C
 
 import torch
 
@@ -18,11 +17,10 @@ def prefix_sum(input: torch.Tensor) -> torch.Tensor:
     if n == 0:
         return out
     l = _lib.lib()
-    nbytes = C.c_size_t()
-    _lib.check(l.brush_inclusive_scan_workspace_size(n, C.byref(nbytes)), "brush_inclusive_scan_workspace_size")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=x.device)
+    nbytes = _lib.size_query("brush_inclusive_scan_workspace_size", n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(l.brush_inclusive_scan_u32(x.data_ptr(), out.data_ptr(), n, ws.data_ptr(), nbytes.value, stream),
+        stream = _lib.current_stream()
+        _lib.check(l.brush_inclusive_scan_u32(x.data_ptr(), out.data_ptr(), n, ws.data_ptr(), nbytes, stream),
                    "brush_inclusive_scan_u32")
     return out

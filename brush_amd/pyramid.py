@@ -68,7 +68,7 @@ def area_resize(image: torch.Tensor, size: Optional[Tuple[int, int]] = None, *,
     out = torch.empty((oh, ow, c), dtype=torch.uint8, device=image.device)
     with torch.cuda.device(image.device):
         _lib.check(_lib.lib().brush_area_resize_u8(image.data_ptr(), w, h, c, out.data_ptr(), ow, oh,
-                                                   torch.cuda.current_stream(image.device).cuda_stream),
+                                                   _lib.current_stream(image.device)),
                    "brush_area_resize_u8")
     return out
 
@@ -87,6 +87,6 @@ def nearest_resize(t: torch.Tensor, size: Optional[Tuple[int, int]] = None, *,
     out = torch.empty((oh, ow), dtype=t.dtype, device=t.device)
     with torch.cuda.device(t.device):
         _lib.check(_lib.lib().brush_nearest_resize(t.data_ptr(), t.element_size(), w, h, out.data_ptr(), ow, oh,
-                                                   torch.cuda.current_stream(t.device).cuda_stream),
+                                                   _lib.current_stream(t.device)),
                    "brush_nearest_resize")
     return out

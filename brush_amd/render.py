@@ -227,35 +227,32 @@ def _forward_impl(cam: Camera, img_size, means, log_scales, quats, sh_coeffs, ra
     if expect_backward is None:
         expect_backward = not render_u32
     if expect_backward and not det and not render_u32:
-        bbytes = C.c_size_t()
-        _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, sh_degree, cap, aux.workspace_flags, C.byref(bbytes)),
-                   "brush_bwd_workspace_size_flags")
-        aux.bwd_ws = _empty((max(bbytes.value, 1),), torch.uint8, dev)
+        bbytes = _lib.size_query("brush_bwd_workspace_size_flags", n, w, h, sh_degree, cap, aux.workspace_flags)
+        aux.bwd_ws = _empty((max(bbytes, 1),), torch.uint8, dev)
         aux.bwd_ws_zeroed = True
-    nbytes = C.c_size_t()
-    _lib.check(l.brush_fwd_workspace_size(n, w, h, sh_degree, cap, C.byref(nbytes)), "brush_fwd_workspace_size")
-    ws = _empty((max(nbytes.value, 1),), torch.uint8, dev)
+    nbytes = _lib.size_query("brush_fwd_workspace_size", n, w, h, sh_degree, cap)
+    ws = _empty((max(nbytes, 1),), torch.uint8, dev)
     means, log_scales, quats = means.contiguous(), log_scales.contiguous(), quats.contiguous()
     sh_coeffs, raw_opacity = sh_coeffs.contiguous(), raw_opacity.contiguous()
     s = aux._as_struct()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = _lib.current_stream()
         if depth is not None:
             assert not render_u32 and row_pitch is None
             _lib.check(l.brush_render_forward_depth(C.byref(u), means.data_ptr(), log_scales.data_ptr(),
                                                     quats.data_ptr(), sh_coeffs.data_ptr(), raw_opacity.data_ptr(), n,
                                                     out.data_ptr(), depth[0].data_ptr(), depth[1].data_ptr(),
-                                                    C.byref(s), ws.data_ptr(), nbytes.value, stream),
+                                                    C.byref(s), ws.data_ptr(), nbytes, stream),
                        "brush_render_forward_depth")
         elif row_pitch is not None:
             _lib.check(l.brush_render_forward_rgba8(C.byref(u), means.data_ptr(), log_scales.data_ptr(),
                                                     quats.data_ptr(), sh_coeffs.data_ptr(), raw_opacity.data_ptr(), n,
                                                     out.data_ptr(), int(row_pitch), C.byref(s), ws.data_ptr(),
-                                                    nbytes.value, stream), "brush_render_forward_rgba8")
+                                                    nbytes, stream), "brush_render_forward_rgba8")
         else:
             _lib.check(l.brush_render_forward(C.byref(u), means.data_ptr(), log_scales.data_ptr(), quats.data_ptr(),
                                               sh_coeffs.data_ptr(), raw_opacity.data_ptr(), n, 1 if render_u32 else 0,
-                                              out.data_ptr(), C.byref(s), ws.data_ptr(), nbytes.value, stream),
+                                              out.data_ptr(), C.byref(s), ws.data_ptr(), nbytes, stream),
                        "brush_render_forward")
     return out, aux, u
 
@@ -299,13 +296,12 @@ def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, nco
         "v_means": seg("v_means", (n, 3)), "v_scales": seg("v_scales", (n, 3)), "v_quats": seg("v_quats", (n, 4)),
         "v_opac": seg("v_opac", (n,)), "v_sh": seg("v_sh", (n, ncoef, 3)), "v_xy": seg("v_xy", (n, 2)),
     }
-    nbytes = C.c_size_t()
-    _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, int(u.sh_degree), int(aux.max_intersects),
-                                                aux.workspace_flags, C.byref(nbytes)), "brush_bwd_workspace_size_flags")
+    nbytes = _lib.size_query("brush_bwd_workspace_size_flags", n, w, h, int(u.sh_degree), int(aux.max_intersects),
+                             aux.workspace_flags)
     v_out = v_out.contiguous()
-    ws, s = aux.backward_workspace(nbytes.value, dev)
+    ws, s = aux.backward_workspace(nbytes, dev)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = _lib.current_stream()
         if pose is not None:
             compact_depth, v_depth = (None, None) if depth is None else (depth[0], depth[1].contiguous())
             _lib.check(l.brush_render_backward_pose(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
@@ -316,7 +312,7 @@ def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, nco
                                                     g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
                                                     g["v_scales"].data_ptr(), g["v_quats"].data_ptr(),
                                                     g["v_sh"].data_ptr(), g["v_opac"].data_ptr(), ws.data_ptr(),
-                                                    nbytes.value, pose[0].data_ptr(), pose[1].data_ptr(),
+                                                    nbytes, pose[0].data_ptr(), pose[1].data_ptr(),
                                                     pose[1].numel(), stream), "brush_render_backward_pose")
         elif depth is not None:
             compact_depth, v_depth = depth[0], depth[1].contiguous()
@@ -326,13 +322,13 @@ def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, nco
                                                      g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
                                                      g["v_scales"].data_ptr(), g["v_quats"].data_ptr(),
                                                      g["v_sh"].data_ptr(), g["v_opac"].data_ptr(), ws.data_ptr(),
-                                                     nbytes.value, stream), "brush_render_backward_depth")
+                                                     nbytes, stream), "brush_render_backward_depth")
         else:
             _lib.check(l.brush_render_backward(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
                                                quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
                                                v_out.data_ptr(), g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
                                                g["v_scales"].data_ptr(), g["v_quats"].data_ptr(), g["v_sh"].data_ptr(),
-                                               g["v_opac"].data_ptr(), ws.data_ptr(), nbytes.value, stream),
+                                               g["v_opac"].data_ptr(), ws.data_ptr(), nbytes, stream),
                        "brush_render_backward")
     return g, block
 
@@ -458,10 +454,9 @@ def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dumm
 
 def pose_buffers(n: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """(v_viewmat [12] f32, scratch of brush_pose_grad_workspace_size(n) bytes) for one pose backward."""
-    nbytes = C.c_size_t()
-    _lib.check(_lib.lib().brush_pose_grad_workspace_size(int(n), C.byref(nbytes)), "brush_pose_grad_workspace_size")
+    nbytes = _lib.size_query("brush_pose_grad_workspace_size", int(n))
     return (_empty((12,), torch.float32, device),
-            _empty((max(nbytes.value, 8) // 8,), torch.float64, device).view(torch.uint8))
+            _empty((max(nbytes, 8) // 8,), torch.float64, device).view(torch.uint8))
 
 
 def _check_viewmat(viewmat) -> torch.Tensor:

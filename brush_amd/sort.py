@@ -1,7 +1,6 @@
 """radix_argsort — mirror of crates/brush-sort/src/lib.rs:32-37 over the HIP C ABI."""
 from __future__ import annotations
 
-import ctypes as C
 
 import torch
 
@@ -27,12 +26,11 @@ def radix_argsort(input_keys: torch.Tensor, input_values: torch.Tensor, n_sort: 
     out_k = torch.empty_like(keys)
     out_v = torch.empty_like(vals)
     l = _lib.lib()
-    nbytes = C.c_size_t()
-    _lib.check(l.brush_radix_argsort_workspace_size(max_n, C.byref(nbytes)), "brush_radix_argsort_workspace_size")
-    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=keys.device)
+    nbytes = _lib.size_query("brush_radix_argsort_workspace_size", max_n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=keys.device)
     with torch.cuda.device(keys.device):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = _lib.current_stream()
         _lib.check(l.brush_radix_argsort_u32(keys.data_ptr(), vals.data_ptr(), out_k.data_ptr(), out_v.data_ptr(),
                                              n_sort.data_ptr(), max_n, int(sorting_bits), ws.data_ptr(),
-                                             nbytes.value, stream), "brush_radix_argsort_u32")
+                                             nbytes, stream), "brush_radix_argsort_u32")
     return out_k, out_v

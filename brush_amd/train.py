@@ -177,22 +177,21 @@ def l1_ssim_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_weight: float, windo
     u8 = gt.dtype == torch.uint8
     pred, gt = pred.contiguous().float(), (gt.contiguous() if u8 else gt.contiguous().float())
     l = _lib.lib()
-    nbytes = C.c_size_t()
-    _lib.check(l.brush_loss_workspace_size(w, h, C.byref(nbytes)), "brush_loss_workspace_size")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=pred.device)
+    nbytes = _lib.size_query("brush_loss_workspace_size", w, h)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     loss = torch.empty(1, dtype=torch.float32, device=pred.device) if out is None else out
     v_pred = torch.empty_like(pred)
     with torch.cuda.device(pred.device):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = _lib.current_stream()
         if u8:
             _lib.check(l.brush_l1_ssim_loss_gt(pred.data_ptr(), gt.data_ptr(), _lib.EVAL_GT_U8, w, h, int(gt.shape[2]),
                                                float(ssim_weight), int(window), float(grad_scale), loss.data_ptr(),
-                                               v_pred.data_ptr(), ws.data_ptr(), nbytes.value, stream),
+                                               v_pred.data_ptr(), ws.data_ptr(), nbytes, stream),
                        "brush_l1_ssim_loss_gt")
         else:
             _lib.check(l.brush_l1_ssim_loss(pred.data_ptr(), gt.data_ptr(), w, h, int(gt.shape[2]), float(ssim_weight),
                                             int(window), float(grad_scale), loss.data_ptr(), v_pred.data_ptr(),
-                                            ws.data_ptr(), nbytes.value, stream),
+                                            ws.data_ptr(), nbytes, stream),
                        "brush_l1_ssim_loss")
     return loss, v_pred
 
@@ -280,7 +279,7 @@ class SplatTrainer:
         z.now = self.opt_time
         with torch.cuda.device(sh.device):
             _lib.check(_lib.lib().brush_lazy_sh_flush(C.byref(z), sh.data_ptr(), n, R.sh_degree_from_coeffs(ncoef),
-                                                      torch.cuda.current_stream(sh.device).cuda_stream),
+                                                      _lib.current_stream(sh.device)),
                        "brush_lazy_sh_flush")
         self._lazy_pending = False
 
@@ -429,7 +428,7 @@ class SplatTrainer:
         for t in (means, log_scales, quats, sh, raw_opac):
             assert t.is_contiguous() and t.dtype == torch.float32
         l = _lib.lib()
-        stream = torch.cuda.current_stream(means.device).cuda_stream
+        stream = _lib.current_stream(means.device)
         # Splats::render feeds rotation / |rotation| (gaussian_splats.rs:174-175).  The fused backward of the
         # previous step already wrote it for the updated rotation; recompute when anyone else touched it.
         key = (quats.data_ptr(), n, splats.rotation._version)
@@ -499,18 +498,16 @@ class SplatTrainer:
                 self._norm_rot_owner = splats.rotation
             elif fused:
                 # single view: gradients go straight through the optimizer inside the backward kernel
-                nbytes = C.c_size_t()
-                _lib.check(l.brush_bwd_workspace_size_flags(n, w, h, int(u.sh_degree), int(aux.max_intersects),
-                                                            aux.workspace_flags, C.byref(nbytes)),
-                           "brush_bwd_workspace_size_flags")
-                ws, s_aux = aux.backward_workspace(nbytes.value, means.device)
+                nbytes = _lib.size_query("brush_bwd_workspace_size_flags", n, w, h, int(u.sh_degree),
+                                         int(aux.max_intersects), aux.workspace_flags)
+                ws, s_aux = aux.backward_workspace(nbytes, means.device)
                 v_xy = torch.empty((max(n, 1), 2), dtype=torch.float32, device=means.device)
                 next_rot = torch.empty_like(quats)
                 args = (C.byref(u), C.byref(s_aux), C.byref(cfg), means.data_ptr(), log_scales.data_ptr(),
                         norm_rot.data_ptr(), quats.data_ptr(), raw_opac.data_ptr(), sh.data_ptr(), n, pred.data_ptr(),
                         v_pred.data_ptr(), v_xy.data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
                         next_rot.data_ptr(), self.grad_2d_accum.data_ptr() if want_stats else None,
-                        self.xy_grad_counts.data_ptr() if want_stats else None, ws.data_ptr(), nbytes.value)
+                        self.xy_grad_counts.data_ptr() if want_stats else None, ws.data_ptr(), nbytes)
                 if pose is None:
                     _lib.check(l.brush_render_backward_adam(*args, stream), "brush_render_backward_adam")
                 else:

@@ -175,7 +175,7 @@ def remap_image(image: torch.Tensor, m, size: Tuple[int, int], return_valid: boo
     with torch.cuda.device(image.device):
         _lib.check(_lib.lib().brush_undistort_u8(image.data_ptr(), w, h, c, out.data_ptr(), ow, oh,
                                                  valid.data_ptr() if return_valid else None, m,
-                                                 torch.cuda.current_stream(image.device).cuda_stream),
+                                                 _lib.current_stream(image.device)),
                    "brush_undistort_u8")
     return (out, valid) if return_valid else out
 
@@ -191,7 +191,7 @@ def remap_depth(t: torch.Tensor, m, size: Tuple[int, int]) -> torch.Tensor:
     out = torch.empty((oh, ow), dtype=t.dtype, device=t.device)
     with torch.cuda.device(t.device):
         _lib.check(_lib.lib().brush_undistort_nearest(t.data_ptr(), t.element_size(), w, h, out.data_ptr(), ow, oh, m,
-                                                      torch.cuda.current_stream(t.device).cuda_stream),
+                                                      _lib.current_stream(t.device)),
                    "brush_undistort_nearest")
     return out
 

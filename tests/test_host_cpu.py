@@ -199,6 +199,37 @@ def test_per_splat_forward_kernels_static_lds_and_spills(lib):
     assert sorted(seen_other) == sorted(set(want_lds) - {"k_project_cull"})
 
 
+def test_fixed_sum_kernels_static_lds_and_spills(lib):
+    """The kernels that reduce through fixed_sum.hpp (pose gradient, exposure, depth loss, eval finalize): the static
+    LDS of every instantiation is the staging of its wave sums and nothing else (4 waves x 12 doubles = 384 bytes;
+    4 doubles + 4 uint32 = 48; 4 x 2 doubles = 64), every instantiation is present, and none spills or uses scratch."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("kernel_diff", os.path.join(ROOT, "tools", "kernel_diff.py"))
+    kd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kd)
+    from brush_amd import _lib
+
+    assert lib is not None
+    res = kd.resources(_lib.LIB_PATH, r"k_view_grad|k_exposure_|k_depth_loss|k_eval_finalize")
+    flags, modes_types = ("Lb0E", "Lb1E"), tuple(f"Lj{m}E{t}" for m in (0, 1) for t in "ft")  # t: uint16_t
+    want = {("k_view_grad", f): 384 for f in flags}
+    want.update({("k_exposure_finalize", f): 384 for f in flags})
+    want.update({("k_depth_loss", mt): 48 for mt in modes_types})
+    want.update({("k_view_grad_finalize", None): 384, ("k_exposure_backward", None): 384,
+                 ("k_exposure_forward", None): 0, ("k_depth_loss_finalize", None): 64, ("k_eval_finalize", None): 64})
+    seen = []
+    for name, r in res.items():
+        m = re.search(r"N_1\d+(k_[a-z_]+)(?:I((?:L[bj]\d+E)[ft]?)EEv|E)", name)
+        assert m, name
+        key = (m.group(1), m.group(2))
+        assert key in want, name
+        assert (r["vgpr_spill_count"], r["sgpr_spill_count"], r["private_segment_fixed_size"]) == (0, 0, 0), name
+        assert r["group_segment_fixed_size"] == want[key], name
+        seen.append(key)
+    assert sorted(seen, key=str) == sorted(want, key=str)
+
+
 def test_product_and_bench_do_not_import_the_oracle():
     """The oracle is test infrastructure: importing the package, or bench.py up to its timed path
     (synthetic inputs included), must not load it; only bench.py's cpu_baseline leg and the tests do."""

@@ -28,6 +28,11 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 views with lens distortion (SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) resampled on the
                                 device into the pinhole camera the rasterizer assumes (brush_amd/undistort.py; build
                                 extension, COLMAP's image_undistorter is the model; both command lines apply it)
+  splat_contributions / Contributions / prune_mask / contributions_from_aux  <- per-splat rendered contribution
+                                over a set of views (max and summed blending weight, hit and stop counts) from a
+                                replay of the compositing walk, and pruning by it (brush_amd/contribution.py; build
+                                extension, RadSplat and LightGaussian are the models; also `python -m brush_amd.prune`,
+                                Splats.select, TrainConfig.contribution_prune_at)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -58,6 +63,8 @@ _TRAIN_LOOP_NAMES = ("train_scene", "TrainLog", "TrainLoop")
 # brush_amd.pose is imported on first use too: a run without pose refinement never loads it.
 _POSE_NAMES = ("se3_exp", "apply_delta", "PoseTable")
 _EXPOSURE_NAMES = ("apply_exposure", "ExposureTable")
+_CONTRIBUTION_NAMES = ("Contributions", "ContributionBuffers", "contributions_from_aux", "splat_contributions",
+                       "prune_mask")
 
 
 def __getattr__(name):
@@ -73,6 +80,9 @@ def __getattr__(name):
     if name in _EXPOSURE_NAMES:
         from . import exposure as _exposure
         return getattr(_exposure, name)
+    if name in _CONTRIBUTION_NAMES:
+        from . import contribution as _contribution
+        return getattr(_contribution, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

@@ -207,6 +207,8 @@ _SYMBOLS = [
      [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(BrushUndistort), _P]),
     ("brush_undistort_nearest", C.c_int,
      [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.POINTER(BrushUndistort), _P]),
+    ("brush_render_contributions", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

@@ -108,6 +108,28 @@ class Splats(torch.nn.Module):
     def num_splats(self) -> int:
         return self.means.shape[0]
 
+    @torch.no_grad()
+    def select(self, keep) -> "Splats":
+        """A new Splats holding the rows `keep` of every parameter, on this one's device (any device).  `keep`: a boolean
+        [N] tensor (the rows that are True, in order) or an integer index tensor (those rows, in its order).  Pending
+        SH optimizer steps are applied first (sync); the new object belongs to no trainer."""
+        self.sync()
+        keep = torch.as_tensor(keep, device=self.means.device)
+        n = self.num_splats()
+        if keep.dtype == torch.bool:
+            if tuple(keep.shape) != (n,):
+                raise ValueError(f"a boolean `keep` must have shape ({n},), got {tuple(keep.shape)}")
+            keep = torch.nonzero(keep).squeeze(1)
+        elif keep.dtype in (torch.int32, torch.int64) and keep.dim() == 1:
+            keep = keep.to(torch.int64)
+            if keep.numel() and (int(keep.min()) < 0 or int(keep.max()) >= n):
+                raise ValueError(f"`keep` holds an index outside [0, {n})")
+        else:
+            raise ValueError(f"`keep` must be a boolean [N] or a 1-D integer index tensor, got {keep.dtype} "
+                             f"{tuple(keep.shape)}")
+        return Splats(self.means.detach()[keep], self.sh_coeffs.detach()[keep], self.rotation.detach()[keep],
+                      self.raw_opacity.detach()[keep], self.log_scales.detach()[keep])
+
     def render(self, camera: Camera, img_size, render_u32_buffer: bool = False, max_intersects=None,
                antialiased: bool = False):
         """gaussian_splats.rs:167-188; `antialiased`: render.render_splats."""

@@ -1,0 +1,119 @@
+"""Prune a splat file by rendered contribution (brush_amd/contribution.py).
+
+    python -m brush_amd.prune SPLATS DATASET [--min-contribution 0.01 | --keep-fraction F [--by max|sum]]
+                              [--views train|eval|all] [--antialiased] [--export OUT.ply] [--json OUT.json]
+                              [--format auto|nerf|colmap] [--eval-split-every K] [--max-resolution R] [--no-undistort]
+
+Measures every splat's contribution over the chosen views (default: the training views), drops the splats whose
+largest blending weight stays below --min-contribution (RadSplat's rule; 0 drops only splats that are never composited
+and never stop a pixel, which changes no bit of those views) or keeps the --keep-fraction largest by max or summed
+weight (LightGaussian's ranking), and prints the splat count and, when the dataset has eval views, their mean PSNR and
+SSIM (eval_stats) before and after.  --json holds the same numbers plus the histogram of `max` in decades.
+"""
+from __future__ import annotations
+
+
+def parser():
+    import argparse
+
+    p = argparse.ArgumentParser(prog="python -m brush_amd.prune",
+                                description="prune splats by their rendered contribution to a dataset's views")
+    p.add_argument("splats", help=".ply or .safetensors splat file")
+    p.add_argument("dataset", help="dataset directory or .zip (NeRF-synthetic or COLMAP)")
+    p.add_argument("--min-contribution", type=float, default=None, metavar="T",
+                   help="prune splats whose largest blending weight over the views is below T (default 0.01; 0: only "
+                        "splats that are never composited and never stop a pixel)")
+    p.add_argument("--keep-fraction", type=float, default=None, metavar="F",
+                   help="instead: keep the ceil(F N) splats that rank highest by --by")
+    p.add_argument("--by", choices=("max", "sum"), default="max", help="--keep-fraction: the ranking key")
+    p.add_argument("--views", choices=("train", "eval", "all"), default="train",
+                   help="the views the contribution is measured over")
+    p.add_argument("--antialiased", action="store_true", help="render in the antialiased mode")
+    p.add_argument("--export", default=None, metavar="OUT.ply", help="write the kept splats to this .ply")
+    p.add_argument("--json", default=None, metavar="OUT.json", help="also write the results to this file")
+    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
+    p.add_argument("--eval-split-every", type=int, default=None)
+    p.add_argument("--max-resolution", type=int, default=None)
+    p.add_argument("--no-undistort", action="store_true",
+                   help="use views with lens distortion as loaded, as if they were pinhole")
+    return p
+
+
+def rule_from_args(args) -> dict:
+    """The keyword arguments of prune_mask the command line asks for; ValueError when both rules are given or a value
+    is out of range."""
+    if args.min_contribution is not None and args.keep_fraction is not None:
+        raise ValueError("--min-contribution and --keep-fraction are two rules: give one of them")
+    if args.keep_fraction is not None:
+        if not 0.0 <= args.keep_fraction <= 1.0:
+            raise ValueError(f"--keep-fraction must be in [0, 1], got {args.keep_fraction}")
+        return {"keep_fraction": float(args.keep_fraction), "by": args.by}
+    t = 0.01 if args.min_contribution is None else float(args.min_contribution)
+    if not 0.0 <= t <= 1.0:
+        raise ValueError(f"--min-contribution must be in [0, 1], got {t}")
+    return {"min_max": t}
+
+
+def main(argv=None) -> int:
+    import json
+    import os
+    import sys
+
+    p = parser()
+    args = p.parse_args(argv)
+    try:
+        rule = rule_from_args(args)
+    except ValueError as e:
+        p.error(str(e))
+    import torch
+
+    from .contribution import max_histogram, prune_mask, splat_contributions
+    from .eval import _load_dataset, eval_stats
+    from .gaussian_splats import Splats
+    from .undistort import undistort_for_cli
+
+    data = _load_dataset(args)  # before any GPU work
+    has_eval = data.eval is not None and bool(data.eval.views)
+
+    def chosen(d):
+        ev = list(d.eval.views) if has_eval else []
+        return {"train": list(d.train.views), "eval": ev, "all": list(d.train.views) + ev}[args.views]
+
+    if not chosen(data):
+        print(f"{args.dataset}: the dataset has no {args.views} views", file=sys.stderr)
+        return 2
+    dev = torch.device("cuda", torch.cuda.current_device())
+    data = undistort_for_cli(data, not args.no_undistort, dev)
+    views = chosen(data)  # distorted views have become pinhole views
+    splats = (Splats.from_safetensors if args.splats.endswith(".safetensors") else Splats.from_ply)(args.splats, dev)
+
+    def score(s):
+        if not has_eval:
+            return None
+        st = eval_stats(s, data.eval, antialiased=args.antialiased)
+        return {"psnr": st.mean_psnr(), "ssim": st.mean_ssim(), "views": len(st.samples)}
+
+    c = splat_contributions(splats, views, antialiased=args.antialiased)
+    mask = prune_mask(c, **rule)
+    kept = splats.select((~mask).to(dev))
+    before, after = score(splats), score(kept)
+    n0, n1 = splats.num_splats(), kept.num_splats()
+    print(f"splats\tbefore {n0}\tafter {n1}\t({len(views)} {args.views} views)")
+    if has_eval:
+        print(f"eval ({before['views']} views)\tpsnr {before['psnr']:.4f} -> {after['psnr']:.4f}\t"
+              f"ssim {before['ssim']:.6f} -> {after['ssim']:.6f}")
+    if args.export:
+        with open(args.export, "wb") as f:
+            f.write(kept.to_ply())
+    if args.json:
+        res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "rule": rule,
+               "views": args.views, "num_views": len(views), "antialiased": bool(args.antialiased),
+               "splats_before": n0, "splats_after": n1, "eval_before": before, "eval_after": after,
+               "max_histogram": max_histogram(c)}
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -107,6 +107,36 @@ class TrainConfig:
     # takes its size from the target, so nothing else changes; () (the default) is the run without the option, bit for
     # bit.  DESIGN §8 row 13.
     downscale_schedule: Tuple[Tuple[int, int], ...] = ()
+    # Build extension: pruning by rendered contribution (brush_amd/contribution.py; RadSplat is the model).  Steps,
+    # non-negative and strictly increasing: after the optimizer update of a listed step the training loop measures every
+    # splat's contribution over all training views and drops the splats whose largest blending weight stays below
+    # contribution_prune_min (0.01 is RadSplat's value: a hyper-parameter default, not a measured number; 0.0 is the
+    # exact rule, "never added and never stopped a pixel", which changes no bit of any training view).  The optimizer
+    # state and the refinement statistics are reset as after a refinement.  Driven by train_loop.TrainLoop, not by
+    # SplatTrainer.step; not with strategy "mcmc" (a fixed budget relocates instead) nor with a multi-rank exchange.
+    # () (the default) is the run without the option, bit for bit.  DESIGN §8 row 15.
+    contribution_prune_at: Tuple[int, ...] = ()
+    contribution_prune_min: float = 0.01
+
+    def check_contribution_prune(self) -> Tuple[int, ...]:
+        """contribution_prune_at as a tuple of ints, or a ValueError naming what is wrong with the two fields."""
+        steps = []
+        at = self.contribution_prune_at
+        if not isinstance(at, (tuple, list)):
+            raise ValueError(f"TrainConfig.contribution_prune_at holds a tuple of steps, got {at!r}")
+        for x in at:
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or int(x) != x:
+                raise ValueError(f"TrainConfig.contribution_prune_at holds integer steps, got {x!r}")
+            if int(x) < 0:
+                raise ValueError(f"TrainConfig.contribution_prune_at: steps must be >= 0, got {int(x)}")
+            if steps and int(x) <= steps[-1]:
+                raise ValueError(f"TrainConfig.contribution_prune_at: steps must be strictly increasing, got {int(x)} "
+                                 f"after {steps[-1]}")
+            steps.append(int(x))
+        t = self.contribution_prune_min
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0.0 <= float(t) <= 1.0:
+            raise ValueError(f"TrainConfig.contribution_prune_min must be in [0, 1], got {t!r}")
+        return tuple(steps)
 
     def check_downscale_schedule(self) -> Tuple[Tuple[int, int], ...]:
         """The schedule as a tuple of (int step, int factor), or a ValueError naming what is wrong with it."""
@@ -206,6 +236,7 @@ class SplatTrainer:
         if self.config.depth_weight < 0 or (self.config.depth_weight_final or 0.0) < 0:
             raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
         self.config.check_downscale_schedule()
+        self.config.check_contribution_prune()
         dev = splats.means.device
         assert dev.type == "cuda", "brush_amd has no CPU path: the splats must live on the GPU"
         self.iter = 0
@@ -350,6 +381,22 @@ class SplatTrainer:
         splats.xys_dummy = torch.zeros((n, 2), dtype=torch.float32, device=dev, requires_grad=True)
         self._reset(n, int(splats.sh_coeffs.shape[1]), dev)
         return RefineStats(ns, int(clone_inds.numel()), alpha_pruned, scale_pruned)
+
+    @torch.no_grad()
+    def keep_splats(self, splats: Splats, keep: torch.Tensor) -> int:
+        """Rebuilds `splats` in place from its rows `keep` (a 1-D index tensor on the splats' device) and resets the
+        optimizer state and the refinement statistics, exactly as refine_splats does after a count change.  Returns the
+        new count.  Call between steps, after sync()."""
+        self.sync(splats)
+        dev = splats.means.device
+        keep = keep.to(device=dev, dtype=torch.int64)
+        for name in ("means", "rotation", "sh_coeffs", "raw_opacity", "log_scales"):
+            setattr(splats, name, torch.nn.Parameter(getattr(splats, name).detach()[keep].contiguous()))
+        n = splats.means.shape[0]
+        splats.xys_dummy = torch.zeros((n, 2), dtype=torch.float32, device=dev, requires_grad=True)
+        self._reset(n, int(splats.sh_coeffs.shape[1]), dev)
+        self.invalidate_cached_rotation()
+        return n
 
     def _lr_mean(self, scene_extent: float) -> float:
         c = self.config

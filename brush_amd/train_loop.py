@@ -17,6 +17,11 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--strategy default|mcmc] [--cap-max 1000000] [--exposure-opt] [--export-exposures EXP.json]
         [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
         [--downscale-schedule STEP:FACTOR,...] [--num-downscales K] [--resolution-schedule S]
+        [--contribution-prune-at STEP,...] [--contribution-prune-min 0.01]
+
+--contribution-prune-at 16000,24000 drops, after each listed step, the splats whose largest blending weight over all
+training views stays below --contribution-prune-min (TrainConfig.contribution_prune_at, brush_amd/contribution.py); the
+log's `prunes` holds (step, splats before, after).
 
 --downscale-schedule 0:4,3000:2,6000:1 trains coarse to fine (TrainConfig.downscale_schedule, brush_amd/pyramid.py): from
 each STEP on, the training targets are the resident images at 1 / FACTOR of their stored size, area-filtered on the device
@@ -82,12 +87,14 @@ class TrainLog:
     exposure_opt: bool = False
     exposures: Optional[List[List[float]]] = None    # exposure_opt: the 3x4 map (12 floats, row-major) of every view
     downscales: List[Tuple[int, int]] = field(default_factory=list)  # (step, factor): the level switches that happened
+    prunes: List[Tuple[int, int, int]] = field(default_factory=list)  # (step, splats before, after): contribution prunes
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
                 "image_bytes": self.image_bytes, "num_splats": self.num_splats, "pose_opt": self.pose_opt,
                 "pose_deltas": self.pose_deltas, "exposure_opt": self.exposure_opt, "exposures": self.exposures,
                 "downscales": [[int(s), int(f)] for s, f in self.downscales],
+                "prunes": [[int(s), int(b), int(a)] for s, b, a in self.prunes],
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -123,14 +130,31 @@ def random_init_bounds(scene) -> Tuple[np.ndarray, np.ndarray]:
     return scene.bounds(e * 0.25, e)
 
 
+def check_contribution_prune(config: TrainConfig, exchange=None) -> Tuple[int, ...]:
+    """The validated TrainConfig.contribution_prune_at of a run; a ValueError when the run cannot prune by contribution:
+    strategy "mcmc" (a fixed budget relocates dead splats instead of dropping them) or a multi-rank `exchange` (a
+    dist.ViewExchange of more than one rank: every rank would have to measure every view)."""
+    steps = config.check_contribution_prune()
+    if steps and config.strategy == "mcmc":
+        raise ValueError("TrainConfig.contribution_prune_at cannot be combined with strategy='mcmc': a fixed budget "
+                         "relocates splats instead of pruning them")
+    if steps and exchange is not None and int(getattr(exchange, "world", 1)) > 1:
+        raise ValueError("TrainConfig.contribution_prune_at cannot be combined with a multi-rank exchange: pruning by "
+                         "contribution is single-GPU")
+    return steps
+
+
 class TrainLoop:
     """The state of one run: splats, trainer, resident views and the device loss log.  `train_scene` drives it; tests
     and tools may call step() / evaluate() themselves (from one thread, on the current stream)."""
 
     def __init__(self, dataset: Dataset, config: Optional[TrainConfig] = None, *, steps: int, init=None,
-                 init_count: int = 10000, sh_degree: int = 3, seed: int = 42, device=None):
+                 init_count: int = 10000, sh_degree: int = 3, seed: int = 42, device=None, exchange=None):
+        """exchange: the dist.ViewExchange of a data-parallel driver, looked at only to refuse what a multi-rank run
+        cannot do (check_contribution_prune); the loop itself trains single-view."""
         if steps < 0:
             raise ValueError(f"steps must be >= 0, got {steps}")
+        self._prune_at = frozenset(check_contribution_prune(config or TrainConfig(), exchange))
         self.dataset = dataset
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         # the mean learning rate decays over the run; the refinement RNG takes the run's seed (train_loop.rs:44-46)
@@ -190,7 +214,25 @@ class TrainLoop:
                               poses=self.poses, exposures=self.exposures, gt_depth=depth,
                               depth_scale=getattr(view, "depth_scale", 1.0),
                               depth_offset=getattr(view, "depth_offset", 0.0))
+        if self.done in self._prune_at:
+            self.prune_by_contribution()
         self.done += 1
+
+    def prune_by_contribution(self) -> Tuple[int, int]:
+        """Measures every splat's contribution over all training views, at the current downscale factor and in the
+        config's antialiased mode, keeps the splats prune_mask(min_max=contribution_prune_min) leaves, rebuilds the
+        parameters and resets the optimizer state and refinement statistics (SplatTrainer.keep_splats).  Appends
+        (step, before, after) to the log's `prunes` and returns (before, after).  Synchronises (one read-back)."""
+        from .contribution import prune_mask, splat_contributions
+
+        self.trainer.sync(self.splats)
+        before = self.splats.num_splats()
+        c = splat_contributions(self.splats, self.dataset.train.views, antialiased=self.config.antialiased,
+                                downscale=self.loader.downscale)
+        keep = torch.nonzero(~prune_mask(c, min_max=self.config.contribution_prune_min)).squeeze(1)
+        after = self.trainer.keep_splats(self.splats, keep) if int(keep.numel()) < before else before
+        self.log.prunes.append((self.done, before, after))
+        return before, after
 
     def train_viewmats(self) -> List[Tuple[str, np.ndarray]]:
         """(name, row-major 4x4 float32 world-to-camera matrix) of every training view as the run holds it now: the
@@ -313,6 +355,14 @@ def downscale_schedule_from_args(args) -> Tuple[Tuple[int, int], ...]:
     return TrainConfig(downscale_schedule=pairs).check_downscale_schedule()
 
 
+def parse_prune_steps(text: str) -> Tuple[int, ...]:
+    """'16000,24000' -> (16000, 24000); the steps are validated by TrainConfig."""
+    try:
+        return tuple(int(x) for x in text.split(","))
+    except ValueError:
+        raise ValueError(f"--contribution-prune-at takes steps separated by commas, got {text!r}") from None
+
+
 def parser():
     import argparse
 
@@ -357,6 +407,12 @@ def parser():
                    help="nerfstudio's spelling: start at 1 / 2^K and double the resolution every --resolution-schedule steps")
     p.add_argument("--resolution-schedule", type=int, default=None, metavar="S",
                    help="--num-downscales: steps between two doublings (default 3000)")
+    p.add_argument("--contribution-prune-at", default=None, metavar="STEP,...",
+                   help="after each of these steps, drop the splats whose largest blending weight over all training "
+                        "views stays below --contribution-prune-min (e.g. 16000,24000)")
+    p.add_argument("--contribution-prune-min", type=float, default=TrainConfig.contribution_prune_min, metavar="T",
+                   help="--contribution-prune-at: the threshold on the largest blending weight (0: only splats that "
+                        "are never composited and never stop a pixel)")
     p.add_argument("--no-undistort", action="store_true",
                    help="train on views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
                         "loaded, as if they were pinhole, instead of undistorting them first")
@@ -372,6 +428,9 @@ def main(argv=None) -> int:
     args = p.parse_args(argv)
     try:
         schedule = downscale_schedule_from_args(args)
+        prune_at = () if args.contribution_prune_at is None else parse_prune_steps(args.contribution_prune_at)
+        check_contribution_prune(TrainConfig(strategy=args.strategy, contribution_prune_at=prune_at,
+                                             contribution_prune_min=args.contribution_prune_min))
     except ValueError as e:
         p.error(str(e))
     if not os.path.exists(args.dataset):
@@ -420,7 +479,8 @@ def main(argv=None) -> int:
     config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
                          mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt, depth_weight=args.depth_weight,
                          depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
-                         downscale_schedule=schedule)
+                         downscale_schedule=schedule, contribution_prune_at=prune_at,
+                         contribution_prune_min=args.contribution_prune_min)
     splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,

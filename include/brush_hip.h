@@ -628,6 +628,39 @@ int brush_undistort_u8(const uint8_t *src, uint32_t w, uint32_t h, uint32_t chan
 int brush_undistort_nearest(const void *src, uint32_t elem_bytes, uint32_t w, uint32_t h, void *dst, uint32_t ow,
                             uint32_t oh, const BrushUndistort *map, brush_stream_t stream);
 
+/* ---- rendered contribution of every splat (build extension; RadSplat's max blending weight, LightGaussian's summed
+ *      weight) -------------------------------------------------------------------------------------------------- */
+/* Replays the compositing walk of a FINISHED brush_render_forward / _depth / _rgba8 over the tile lists it left in the
+ * aux (projected_splats, tile_bins, compact_gid_from_isect, global_from_compact_gid, num_visible; final_index with the
+ * self-check) and accumulates, for every splat the walk meets, into the row of its GLOBAL id g:
+ *   max_bits[g]   the bits of max over pixels of fac = alpha T, the weight the forward added the splat's colour with
+ *                 (alpha after the 0.999 clamp, T the transmittance in front of it); a non-negative float, so the
+ *                 integer max of the bits is the float max;
+ *   counts[g][0]  sum_q24: the sum over pixels of (uint32) rint(fac 2^24), ties to even, as an exact integer;
+ *                 sum_q24 / 2^24 is the summed weight to half a unit of 2^-24 per added pixel;
+ *   counts[g][1]  hits: the number of pixels the forward added the splat to;
+ *   counts[g][2]  stops: the number of pixels the splat ENDED without being added.
+ * The stop quirk: an entry that passes `sigma >= 0 && alpha >= 1/255` and would take T to 1e-4 or below ends the pixel
+ * and is not composited (rasterize.wgsl:88-91).  Such a splat has fac = 0 there, yet removing it changes the image (the
+ * entries behind it would be tested against the same T), so it is counted on its own: a splat with hits == 0 and
+ * stops == 0 in every view can be removed without changing one bit of any of those views.
+ * Per pixel the walk repeats the forward's float operations, in both BRUSH_AUX_DETERMINISTIC settings and with
+ * BRUSH_AUX_ANTIALIASED (word 8 of a projected row already holds the compensated opacity).  The entry only
+ * ACCUMULATES: the caller zeroes max_bits [N] and counts [N][3] once and may keep them across views (max of maxima,
+ * sums of sums).  All four outputs are order-independent integers: the same views give the same bits on every run.
+ * Rows of splats the walk never meets (culled, or behind a stack that stopped every pixel of their quadrants first)
+ * are not touched.
+ * Self-check: out_img ([h,w,4] f32, the image of that forward) and mismatch ([1] u32) are both NULL or both given; with
+ * them every pixel compares the bits of its replayed 1 - T with out_img[..., 3] and its last added entry with
+ * final_index, and mismatch[0] += the number of pixels that differ (0 for a faithful replay; also accumulated).
+ * A NULL required pointer, a misaligned one (out_img: 16 bytes, counts: 8) or tile_bounds that do not belong to img_size
+ * return BRUSH_ERR_INVALID_ARG before any device work; n == 0 returns BRUSH_OK and launches nothing.  No workspace, no
+ * allocation, no synchronisation: graph-capturable. */
+int brush_render_contributions(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                               const float *out_img /* [h,w,4] or NULL */,
+                               uint32_t *max_bits /* [N] */, uint64_t *counts /* [N,3]: sum_q24, hits, stops */,
+                               uint32_t *mismatch /* [1] or NULL */, uint32_t n, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

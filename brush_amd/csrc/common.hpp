@@ -138,5 +138,12 @@ size_t sort_workspace_bytes(uint32_t max_n);
 hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
                        uint32_t *vals_out, const uint32_t *d_n, uint32_t max_n, uint32_t bits,
                        void *ws, hipStream_t s, uint32_t *edges = nullptr, uint32_t edge_keys = 0);
+// The depth sort: all 32 bits of the keys, same outputs and workspace as sort_launch.  Clouds of up to 2^20 splats
+// (depth_sort_uses_buckets, chosen from max_n like the launch shapes) are partitioned by ONE count + scatter pair into
+// 256 key-range buckets around splitters from a sorted sample, and a third launch finishes every bucket inside one
+// workgroup; larger ones run sort_launch.
+bool depth_sort_uses_buckets(uint32_t max_n);
+hipError_t depth_sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
+                             const uint32_t *d_n, uint32_t max_n, void *ws, hipStream_t s);
 
 }  // namespace brush

@@ -24,6 +24,8 @@
 //     512-thread scatter workgroups whose 76 KiB of LDS let two of them share a CU (one's loads and stores overlap the
 //     other's ranking): the 18 M-key tile sort of the 4K / 20 M-splat frame 326 -> 246 us (37 % of the HBM peak);
 //     256-thread / 4096-key workgroups (four per CU) measured slower (278 us: shorter digit runs, twice the tiles).
+// The depth sort of clouds up to 2^20 splats does not run these passes: depth_sort_launch (below) scatters once into 256
+// key-range buckets and finishes every bucket inside one workgroup, 3 launches instead of 8.
 // The element count stays on the device (*d_n): grids are sized for max_n and surplus blocks exit on
 // their first instruction.  Stability: tiles, wave chunks, rounds and lanes are all ranked in index order.
 // Traffic per pass: 4 B/key (upsweep) + 16 B/pair (downsweep).  Roofline: HBM at large n, kernel
@@ -71,11 +73,66 @@ inline bool sort_is_fused(uint32_t max_n) {
     return (uint32_t)(((uint64_t)max_n + kMaxTileKeys - 1) / kMaxTileKeys) <= kFusedMaxTiles;
 }
 
-template <bool FUSED>
+// ---- depth sort by key-range buckets (depth_sort_launch) ----
+// Clouds of up to kBucketMaxN splats: ONE count + scatter pair partitions the keys into kRadix key-range buckets (the
+// digit of that pass is "bucket of key": a binary search over 255 splitters picked from a sorted fixed-stride sample),
+// then one workgroup per bucket finishes its bucket in LDS, where a pass costs a barrier and not a kernel boundary.
+constexpr uint32_t kBucketMaxN = 1u << 20;
+constexpr uint32_t kSampleKeys = kSortThreads;  // one sampled key per thread of a count workgroup
+constexpr uint32_t kBucketLdsKeys = 8192;       // pairs a finish workgroup sorts in LDS; larger buckets: global passes
+static_assert(kBucketMaxN / kRadix <= kBucketLdsKeys / 2, "evenly spread keys fill a bucket's LDS at most half");
+static_assert(kBucketMaxN <= kSortThreads * 8 * kSortTargetTiles, "bucket scatter: at most 8 keys per lane");
+
+// Every thread of a 1024-thread workgroup: sorts a fixed-stride sample of the keys (all of them below kSampleKeys,
+// padded with the largest key) with a bitonic network, steps inside a wave by lane exchange and the rest through `xch`,
+// and leaves every (kSampleKeys / kRadix)-th of it in spl[1 .. 255] (spl[0] is never read).  Ends with a barrier.
+__device__ __forceinline__ void select_splitters(const uint32_t *__restrict__ keys, uint32_t n, uint32_t *spl,
+                                                 uint32_t (*xch)[kSampleKeys]) {
+    const uint32_t t = threadIdx.x;
+    uint32_t k = 0xFFFFFFFFu;
+    if (n >= kSampleKeys) k = keys[(uint32_t)(((uint64_t)t * n) / kSampleKeys)];
+    else if (t < n) k = keys[t];
+    uint32_t buf = 0;
+#pragma unroll
+    for (uint32_t size = 2; size <= kSampleKeys; size <<= 1) {
+#pragma unroll
+        for (uint32_t j = size >> 1; j > 0; j >>= 1) {
+            uint32_t other;
+            if (j < kWave) {
+                other = (uint32_t)__shfl_xor((int)k, (int)j, (int)kWave);
+            } else {
+                // two buffers in turn: a slot is rewritten two exchanges later, behind the barrier of the one between
+                xch[buf][t] = k;
+                __syncthreads();
+                other = xch[buf][t ^ j];
+                buf ^= 1u;
+            }
+            const bool ascending = (t & size) == 0, lower = (t & j) == 0;
+            k = lower == ascending ? min(k, other) : max(k, other);
+        }
+    }
+    constexpr uint32_t kPer = kSampleKeys / kRadix;
+    if (t % kPer == 0) spl[t / kPer] = k;
+    __syncthreads();
+}
+
+// Bucket of a key = number of splitters spl[1 .. 255] (ascending) that are <= key: equal keys share a bucket and the
+// buckets are ordered like the keys.
+__device__ __forceinline__ uint32_t bucket_of(const uint32_t *spl, uint32_t k) {
+    uint32_t b = 0;
+#pragma unroll
+    for (uint32_t step = kRadix / 2; step; step >>= 1) b += spl[b + step] <= k ? step : 0u;
+    return b;
+}
+
+// BUCKET: the digit is the key's bucket; every workgroup selects the same splitters from the same sample (cheaper than
+// a launch of its own and its boundary) and tile 0 publishes them for the scatter kernel.
+template <bool FUSED, bool BUCKET = false>
 __global__ __launch_bounds__(kSortThreads) void k_sort_upsweep(const uint32_t *__restrict__ keys,
                                                               const uint32_t *__restrict__ d_n, uint32_t max_n,
                                                               uint32_t shift, uint32_t mask,
-                                                              uint32_t *__restrict__ counts, uint32_t max_tiles) {
+                                                              uint32_t *__restrict__ counts, uint32_t max_tiles,
+                                                              uint32_t *__restrict__ splitters) {
     BRUSH_KTRACE(kTrSortUp, shift | (((shift >> 3) + (max_n > (1u << 21) ? 4u : 0u)) << 24));
     const uint32_t n = min(*d_n, max_n);
     BRUSH_KTRACE_MARK(1, n);
@@ -85,6 +142,13 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_upsweep(const uint32_t *_
     if ((uint64_t)tile * tile_keys >= n) return;
     __shared__ uint32_t hist[kSortWaves][kRadix];
     for (uint32_t i = threadIdx.x; i < kSortWaves * kRadix; i += kSortThreads) (&hist[0][0])[i] = 0;
+    const uint32_t *spl = nullptr;
+    if constexpr (BUCKET) {
+        __shared__ uint32_t spl_s[kRadix], xch[2][kSampleKeys];
+        select_splitters(keys, n, spl_s, xch);
+        if (tile == 0 && threadIdx.x < kRadix) splitters[threadIdx.x] = spl_s[threadIdx.x];  // [0]: unused
+        spl = spl_s;
+    }
     __syncthreads();
     const uint32_t wid = threadIdx.x / kWave;
     const uint32_t base = tile * tile_keys;
@@ -93,7 +157,7 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_upsweep(const uint32_t *_
         if (idx < n) {
             const uint32_t k = keys[idx];
             if (i == 0) BRUSH_KTRACE_MARK(2, k);
-            atomicAdd(&hist[wid][(k >> shift) & mask], 1u);
+            atomicAdd(&hist[wid][BUCKET ? bucket_of(spl, k) : (k >> shift) & mask], 1u);
         }
     }
     __syncthreads();
@@ -218,7 +282,9 @@ __device__ __forceinline__ void table_sums_to_lds(const uint32_t (&spec)[kSpecRo
     L.part_all()[g8][2 * dp] = ps.all[0], L.part_all()[g8][2 * dp + 1] = ps.all[1];
 }
 
-template <bool FUSED, uint32_t ITEMS, uint32_t THREADS, typename LDS>
+// BUCKET (depth_sort_launch): the digit of a key is its bucket (bucket_of over `spl`, 256 splitters in LDS that are
+// visible from barrier A on), kept packed four to a register; tile 0 also publishes the 257 bucket offsets.
+template <bool FUSED, uint32_t ITEMS, uint32_t THREADS, typename LDS, bool BUCKET = false>
 __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys_in,
                                                const uint32_t *__restrict__ vals_in,
                                                uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
@@ -226,8 +292,10 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
                                                const uint32_t *__restrict__ counts,
                                                const uint32_t *__restrict__ totals, uint32_t max_tiles,
                                                uint32_t *__restrict__ edges, uint32_t edge_keys, LDS &L,
-                                               const uint32_t (&spec)[kSpecRows], KTraceRef trace = KTraceRef{}) {
+                                               const uint32_t (&spec)[kSpecRows], KTraceRef trace = KTraceRef{},
+                                               const uint32_t *spl = nullptr, uint32_t *__restrict__ bucket_off = nullptr) {
     static_assert(!FUSED || THREADS == kSortThreads, "the fused table sums assume 8 groups of 128 threads");
+    static_assert(!BUCKET || (FUSED && ITEMS <= 8), "bucket scatter: the fused shape below kBucketMaxN");
     constexpr uint32_t kTileKeys = THREADS * ITEMS;
     constexpr uint32_t kWaves = THREADS / kWave;
     // small sorts: the scatter is a few hundred KB, not worth two barriers — unless the pass also finds the run
@@ -264,6 +332,15 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     }
     __syncthreads();  // A: wave_hist zeroed, partial column sums published
     BRUSH_KTRACE_MARK_VIA(trace, 3, key[0]);
+    uint32_t bucket4[BUCKET ? (ITEMS + 3) / 4 : 1] = {};
+    if constexpr (BUCKET) {
+#pragma unroll
+        for (uint32_t i = 0; i < ITEMS; i++) bucket4[i / 4] |= bucket_of(spl, key[i]) << ((i & 3u) * 8u);
+    }
+    auto digit_of = [&](uint32_t i) -> uint32_t {
+        if constexpr (BUCKET) return (bucket4[i / 4] >> ((i & 3u) * 8u)) & 0xFFu;
+        else return (key[i] >> shift) & mask;
+    };
 
     // rank of a key among the keys of its digit inside its wave's chunk: < 64 * ITEMS <= 1024.  The large-tile variants
     // are register-bound and keep two ranks per register.
@@ -282,7 +359,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     for (uint32_t i = 0; i < ITEMS; i++) {
         const uint32_t idx = chunk + i * kWave + lane;
         const bool valid = idx < n;
-        const uint32_t digit = (key[i] >> shift) & mask;
+        const uint32_t digit = digit_of(i);
         uint64_t peers = __ballot(valid);
 #pragma unroll
         for (uint32_t b = 0; b < 8; b++) {
@@ -327,6 +404,12 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     if (threadIdx.x < kRadix) {
         L.digit_base[threadIdx.x] = smaller + glob_base;
         L.tile_start[threadIdx.x] = run_start;
+        if constexpr (BUCKET) {
+            if (tile == 0) {  // it exists whenever n > 0
+                bucket_off[threadIdx.x] = smaller;
+                if (threadIdx.x == kRadix - 1) bucket_off[kRadix] = n;
+            }
+        }
     }
     __syncthreads();  // C
     BRUSH_KTRACE_MARK_VIA(trace, 4, smaller);
@@ -335,7 +418,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
         for (uint32_t i = 0; i < ITEMS; i++) {
             const uint32_t idx = chunk + i * kWave + lane;
             if (idx < n) {
-                const uint32_t digit = (key[i] >> shift) & mask;
+                const uint32_t digit = digit_of(i);
                 const uint32_t pos = L.digit_base[digit] + L.wave_hist[wid][digit] + rank_of(i);
                 if (keys_out) keys_out[pos] = key[i];
                 vals_out[pos] = kLateVals ? (vals_in ? vals_in[idx] : idx) : val[kLateVals ? 0 : i];
@@ -361,7 +444,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
             for (uint32_t u = 0; u < kValBatch; u++) {
                 const uint32_t i = i0 + u, idx = chunk + i * kWave + lane;
                 if (idx < n) {
-                    const uint32_t digit = (key[i] >> shift) & mask;
+                    const uint32_t digit = digit_of(i);
                     const uint32_t lp = L.tile_start[digit] + L.wave_hist[wid][digit] + rank_of(i);
                     L.keys[lp] = key[i];
                     L.vals[lp] = v[u];
@@ -373,7 +456,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
         for (uint32_t i = 0; i < ITEMS; i++) {
             const uint32_t idx = chunk + i * kWave + lane;
             if (idx < n) {
-                const uint32_t digit = (key[i] >> shift) & mask;
+                const uint32_t digit = digit_of(i);
                 const uint32_t lp = L.tile_start[digit] + L.wave_hist[wid][digit] + rank_of(i);
                 L.keys[lp] = key[i];
                 L.vals[lp] = val[i];
@@ -393,7 +476,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
         const uint32_t lp = i * THREADS + threadIdx.x;
         if (lp < tile_n) {
             const uint32_t k = L.keys[lp];
-            const uint32_t digit = (k >> shift) & mask;
+            const uint32_t digit = BUCKET ? bucket_of(spl, k) : (k >> shift) & mask;
             const uint32_t ts = L.tile_start[digit];
             const uint32_t pos = L.digit_base[digit] + (lp - ts);
             if (keys_out) keys_out[pos] = k;  // nullptr: nobody reads the sorted keys (the run edges are found right here)
@@ -404,7 +487,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
             // [pos, pos + 1) as (start, end); so do the first and the last key of the run, whose outer neighbours belong
             // to other workgroups.  edges[2k] = max ~start, edges[2k+1] = max end over all proposals (zero-initialised
             // by the caller): proposals from the inside of a bin lose against the true edges.
-            if (edges && k < edge_keys) {
+            if (!BUCKET && edges && k < edge_keys) {
                 const bool first = lp == ts;
                 const bool last = lp + 1 == tile_n || ((L.keys[lp + 1] >> shift) & mask) != digit;
                 if (first || L.keys[lp - 1] != k) atomicMax(&edges[2 * k], ~pos);
@@ -414,12 +497,13 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     }
 }
 
-template <bool FUSED>
+template <bool FUSED, bool BUCKET = false>
 __global__ __launch_bounds__(kSortThreads) void k_sort_downsweep(
     const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
     uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ d_n,
     uint32_t max_n, uint32_t shift, uint32_t mask, const uint32_t *__restrict__ counts,
-    const uint32_t *__restrict__ totals, uint32_t max_tiles, uint32_t *__restrict__ edges, uint32_t edge_keys) {
+    const uint32_t *__restrict__ totals, uint32_t max_tiles, uint32_t *__restrict__ edges, uint32_t edge_keys,
+    const uint32_t *__restrict__ splitters, uint32_t *__restrict__ bucket_off) {
     BRUSH_KTRACE(kTrSortDown, shift | (((shift >> 3) + (max_n > (1u << 21) ? 4u : 0u)) << 24));
     // The first 128 rows of the [tile][digit] count table (every row a sort of up to 2 M keys has) are requested before
     // the element count is known: the table sum used to start only when *d_n had arrived and took two dependent batches
@@ -432,6 +516,12 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_downsweep(
         for (uint32_t j = 0; j < kSpecRows; j++)
             spec[j] = FUSED ? counts[(size_t)(g8 + kTableGroups * j) * (kRadix / 2) + dp] : 0u;
     }
+    const uint32_t *spl = nullptr;
+    if constexpr (BUCKET) {
+        __shared__ uint32_t spl_s[kRadix];  // read behind the body's barrier A
+        if (threadIdx.x < kRadix) spl_s[threadIdx.x] = splitters[threadIdx.x];
+        spl = spl_s;
+    }
     const uint32_t n = min(*d_n, max_n);
     BRUSH_KTRACE_MARK(1, n);
     const uint32_t items = sort_items(n);
@@ -439,15 +529,16 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_downsweep(
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     DownLds &L = *reinterpret_cast<DownLds *>(lds_raw);
 #define BRUSH_DOWN(K, SPEC)                                                                                       \
-    downsweep_body<FUSED, K, kSortThreads>(keys_in, vals_in, keys_out, vals_out, n, shift, mask, counts, totals, \
-                                           max_tiles, edges, edge_keys, L, SPEC, BRUSH_KTRACE_REF)
+    downsweep_body<FUSED, K, kSortThreads, DownLds, BUCKET>(keys_in, vals_in, keys_out, vals_out, n, shift, mask,  \
+                                                            counts, totals, max_tiles, edges, edge_keys, L, SPEC, \
+                                                            BRUSH_KTRACE_REF, spl, bucket_off)
     if (items >= 8) {  // block-uniform
         // large tiles are register-bound: the table sums are formed here, before their 8 / 16 keys per lane are live
         table_sums_to_lds(spec, counts, blockIdx.x, (n + kSortThreads * items - 1) / (kSortThreads * items), L,
                           BRUSH_KTRACE_REF);
         const uint32_t none[kSpecRows] = {};
-        if (items == 8) BRUSH_DOWN(8, none);
-        else BRUSH_DOWN(16, none);
+        if (BUCKET || items == 8) BRUSH_DOWN(8, none);  // BUCKET: n <= kBucketMaxN never selects 16
+        else if constexpr (!BUCKET) BRUSH_DOWN(16, none);
         return;
     }
     switch (items) {
@@ -486,6 +577,136 @@ __global__ void k_sort_copy(const uint32_t *__restrict__ keys_in, const uint32_t
     }
 }
 
+// ---- bucket finish: one workgroup per bucket ----
+struct FinishLds {
+    uint32_t keys[2][kBucketLdsKeys];
+    uint32_t vals[2][kBucketLdsKeys];
+    uint32_t wave_hist[kSortWaves][kRadix];
+    uint32_t wave_tot2[4][2];
+    uint32_t or_and[kSortWaves][2];
+};
+static_assert(sizeof(FinishLds) <= 160 * 1024, "one finish workgroup per CU");
+
+// One stable counting pass of the whole workgroup over `cnt` pairs, src -> dst (LDS or this bucket's own range of a
+// global buffer) by the digit (key >> shift) & mask.  Every wave owns a contiguous chunk: it counts its digits, the
+// counts are scanned in (digit, wave) order, then it walks the chunk again in index order and ranks 64 keys at a time
+// with match-any ballots, so nothing per key stays in registers and every loop is bounded by cnt.  Ends with a barrier
+// (workgroup-scope release / acquire: the next pass reads what this one wrote, also in global memory).
+__device__ __forceinline__ void bucket_pass(const uint32_t *sk, const uint32_t *sv, uint32_t *dk, uint32_t *dv,
+                                            uint32_t cnt, uint32_t shift, uint32_t mask, FinishLds &L) {
+    const uint32_t wid = threadIdx.x / kWave, lane = lane_id();
+    for (uint32_t i = threadIdx.x; i < kSortWaves * kRadix; i += kSortThreads) (&L.wave_hist[0][0])[i] = 0;
+    __syncthreads();
+    const uint32_t per_wave = ceil_div(cnt, kSortThreads) * kWave;  // cnt <= kBucketMaxN
+    const uint32_t beg = min(cnt, wid * per_wave), end = min(cnt, beg + per_wave);
+    for (uint32_t i = beg + lane; i < end; i += kWave) atomicAdd(&L.wave_hist[wid][(sk[i] >> shift) & mask], 1u);
+    __syncthreads();
+    uint32_t tot = 0, unused = 0;
+    if (threadIdx.x < kRadix) {
+#pragma unroll
+        for (uint32_t w = 0; w < kSortWaves; w++) {
+            const uint32_t t = L.wave_hist[w][threadIdx.x];
+            L.wave_hist[w][threadIdx.x] = tot;
+            tot += t;
+        }
+    }
+    block_excl_scan256_pair(tot, unused, L.wave_tot2);  // tot: pairs of a smaller digit
+    if (threadIdx.x < kRadix) {
+#pragma unroll
+        for (uint32_t w = 0; w < kSortWaves; w++) L.wave_hist[w][threadIdx.x] += tot;
+    }
+    __syncthreads();
+    const uint64_t lt = lanemask_lt();
+    for (uint32_t i0 = beg; i0 < end; i0 += kWave) {  // wave-uniform
+        const uint32_t i = i0 + lane;
+        const bool valid = i < end;
+        const uint32_t k = valid ? sk[i] : 0u, v = valid ? sv[i] : 0u;
+        const uint32_t digit = (k >> shift) & mask;
+        uint64_t peers = __ballot(valid);
+#pragma unroll
+        for (uint32_t b = 0; b < 8; b++) {
+            const bool bit = (digit >> b) & 1u;
+            const uint64_t vote = __ballot(valid && bit);
+            peers &= bit ? vote : ~vote;
+        }
+        const uint32_t below = __popcll(peers & lt);
+        const int leader = valid ? (__ffsll((long long)peers) - 1) : 0;
+        uint32_t old = 0;
+        if (valid && (int)lane == leader) {
+            old = L.wave_hist[wid][digit];
+            L.wave_hist[wid][digit] = old + __popcll(peers);
+        }
+        old = __shfl(old, leader, 64);
+        if (valid) {
+            dk[old + below] = k;
+            dv[old + below] = v;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+}
+
+// Workgroup b sorts bucket b = pairs [off[b], off[b + 1]) of the scatter's output (tmp) by key, stable, into the same
+// range of the final buffers.  The bucket's keys agree in every bit above the highest one in which any two of them
+// differ (OR ^ AND over the bucket), so only the bits below it are sorted, split evenly over ceil(bits / 8) passes.
+//   * up to kBucketLdsKeys pairs: loaded once, passes between two LDS images, the last one writes the result;
+//   * more (long runs of equal keys, a spike the sample missed): the same passes between the bucket's range of tmp
+//     and of out, an odd number of them so that the last one lands in out.  Slow, and alone in its own range.
+// No workgroup waits for another one.
+__global__ __launch_bounds__(kSortThreads) void k_sort_bucket_finish(uint32_t *tmp_keys, uint32_t *tmp_vals,
+                                                                    uint32_t *keys_out, uint32_t *vals_out,
+                                                                    const uint32_t *__restrict__ d_n, uint32_t max_n,
+                                                                    const uint32_t *__restrict__ bucket_off) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    FinishLds &L = *reinterpret_cast<FinishLds *>(lds_raw);
+    const uint32_t off0 = bucket_off[blockIdx.x], off1 = bucket_off[blockIdx.x + 1];
+    const uint32_t n = min(*d_n, max_n);
+    if (n == 0) return;  // no scatter workgroup ran: the offsets are leftovers
+    const uint32_t start = min(off0, n), stop = min(off1, n);
+    if (stop <= start) return;
+    const uint32_t cnt = stop - start;
+    const bool in_lds = cnt <= kBucketLdsKeys;  // block-uniform
+    tmp_keys += start, tmp_vals += start, keys_out += start, vals_out += start;
+    uint32_t k_or = 0, k_and = 0xFFFFFFFFu;
+    for (uint32_t i = threadIdx.x; i < cnt; i += kSortThreads) {
+        const uint32_t k = tmp_keys[i];
+        k_or |= k, k_and &= k;
+        if (in_lds) L.keys[0][i] = k, L.vals[0][i] = tmp_vals[i];
+    }
+#pragma unroll
+    for (uint32_t m = kWave / 2; m; m >>= 1) {
+        k_or |= (uint32_t)__shfl_xor((int)k_or, (int)m, (int)kWave);
+        k_and &= (uint32_t)__shfl_xor((int)k_and, (int)m, (int)kWave);
+    }
+    if (lane_id() == 0) L.or_and[threadIdx.x / kWave][0] = k_or, L.or_and[threadIdx.x / kWave][1] = k_and;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t w = 0; w < kSortWaves; w++) k_or |= L.or_and[w][0], k_and &= L.or_and[w][1];
+    const uint32_t differ = k_or ^ k_and;
+    const uint32_t bits = differ ? 32u - (uint32_t)__clz((int)differ) : 0u;
+    uint32_t passes = (bits + 7u) / 8u;
+    if (in_lds) {
+        if (passes == 0) {  // one key value: the scatter's order is the result
+            for (uint32_t i = threadIdx.x; i < cnt; i += kSortThreads) keys_out[i] = L.keys[0][i], vals_out[i] = L.vals[0][i];
+            return;
+        }
+        const uint32_t width = (bits + passes - 1u) / passes, mask = (1u << width) - 1u;
+        uint32_t p = 0;
+        for (; p + 1 < passes; p++)
+            bucket_pass(L.keys[p & 1u], L.vals[p & 1u], L.keys[(p + 1u) & 1u], L.vals[(p + 1u) & 1u], cnt, p * width,
+                        mask, L);
+        bucket_pass(L.keys[p & 1u], L.vals[p & 1u], keys_out, vals_out, cnt, p * width, mask, L);
+        return;
+    }
+    passes |= 1u;  // 1, 3 or 5: tmp -> out -> tmp ... -> out (a pass over bits that agree is a stable copy)
+    const uint32_t width = (bits + passes - 1u) / passes, mask = (1u << width) - 1u;  // <= 8; 5 passes: 7 bits, shifts <= 28
+    for (uint32_t p = 0; p < passes; p++) {
+        const bool to_out = (p & 1u) == 0;
+        bucket_pass(to_out ? tmp_keys : keys_out, to_out ? tmp_vals : vals_out, to_out ? keys_out : tmp_keys,
+                    to_out ? vals_out : tmp_vals, cnt, p * width, mask, L);
+    }
+}
+
 struct SortWs {
     uint32_t *tmp_keys, *tmp_vals, *counts, *totals;
     uint32_t max_tiles;
@@ -515,6 +736,12 @@ hipError_t enable_big_lds() {
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sort_downsweep_big),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DownLdsBig));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sort_downsweep<true, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DownLds));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sort_bucket_finish),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FinishLds));
     if (e == hipSuccess) done[dev].store(1, std::memory_order_release);
     return e;
 }
@@ -561,13 +788,13 @@ hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_
         uint32_t *pass_edges = p + 1 == passes ? edges : nullptr;
         if (fused) {
             hipLaunchKernelGGL(k_sort_upsweep<true>, dim3(w.max_tiles), dim3(kSortThreads), 0, s, src_k, d_n, max_n,
-                               shift, mask, w.counts, w.max_tiles);
+                               shift, mask, w.counts, w.max_tiles, nullptr);
             hipLaunchKernelGGL(k_sort_downsweep<true>, dim3(w.max_tiles), dim3(kSortThreads), sizeof(DownLds), s, src_k,
                                src_v, dst_k, dst_v, d_n, max_n, shift, mask, w.counts, w.totals, w.max_tiles, pass_edges,
-                               edge_keys);
+                               edge_keys, nullptr, nullptr);
         } else {
             hipLaunchKernelGGL(k_sort_upsweep<false>, dim3(w.max_tiles), dim3(kSortThreads), 0, s, src_k, d_n, max_n,
-                               shift, mask, w.counts, w.max_tiles);
+                               shift, mask, w.counts, w.max_tiles, nullptr);
             hipLaunchKernelGGL(k_sort_scan, dim3(kRadix), dim3(256), 0, s, w.counts, d_n, max_n, w.max_tiles, w.totals);
             hipLaunchKernelGGL(k_sort_downsweep_big, dim3(w.max_tiles), dim3(kBigThreads), sizeof(DownLdsBig), s,
                                src_k, src_v, dst_k, dst_v, d_n, max_n, shift, mask, w.counts, w.totals, w.max_tiles,
@@ -576,6 +803,30 @@ hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_
         src_k = dst_k;
         src_v = dst_v;
     }
+    return hipGetLastError();
+}
+
+bool depth_sort_uses_buckets(uint32_t max_n) { return max_n <= kBucketMaxN; }
+
+hipError_t depth_sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
+                             const uint32_t *d_n, uint32_t max_n, void *ws, hipStream_t s) {
+    if (!depth_sort_uses_buckets(max_n)) return sort_launch(keys_in, vals_in, keys_out, vals_out, d_n, max_n, 32, ws, s);
+    if (max_n == 0) return hipSuccess;
+    if (!keys_out) return hipErrorInvalidValue;
+    const SortWs w = carve_sort(ws, max_n);
+    const hipError_t lds = enable_big_lds();
+    if (lds != hipSuccess) return lds;
+    // The fused shape leaves two pieces of its workspace unused: `totals` (here: the splitters) and the upper half of
+    // the count table, whose rows are 16-bit (here: the kRadix + 1 bucket offsets).
+    static_assert(kRadix + 1 <= (kRadix / 2) * kSortTargetTiles, "the offsets fit in the unused half");
+    uint32_t *splitters = w.totals, *bucket_off = w.counts + (size_t)(kRadix / 2) * w.max_tiles;
+    hipLaunchKernelGGL((k_sort_upsweep<true, true>), dim3(w.max_tiles), dim3(kSortThreads), 0, s, keys_in, d_n, max_n, 0u,
+                       kRadix - 1u, w.counts, w.max_tiles, splitters);
+    hipLaunchKernelGGL((k_sort_downsweep<true, true>), dim3(w.max_tiles), dim3(kSortThreads), sizeof(DownLds), s, keys_in,
+                       vals_in, w.tmp_keys, w.tmp_vals, d_n, max_n, 0u, kRadix - 1u, w.counts, w.totals, w.max_tiles,
+                       (uint32_t *)nullptr, 0u, (const uint32_t *)splitters, bucket_off);
+    hipLaunchKernelGGL(k_sort_bucket_finish, dim3(kRadix), dim3(kSortThreads), sizeof(FinishLds), s, w.tmp_keys,
+                       w.tmp_vals, keys_out, vals_out, d_n, max_n, (const uint32_t *)bucket_off);
     return hipGetLastError();
 }
 

@@ -244,9 +244,9 @@ static int render_forward_impl(const BrushUniforms *h_uniforms, const float *mea
     // DepthSort: keys = f32 depth bits, all 32 bits (render.rs:151-156).  With a depth output the sorted keys go to
     // the caller's compact_depth: camera-space z of every visible splat in compact order, read by the compositing
     // kernels of the forward and of the backward.
-    BRUSH_HIP_CHECK(sort_launch(ws.pre_keys, ws.pre_gids,
-                                compact_depth ? reinterpret_cast<uint32_t *>(compact_depth) : ws.sorted_keys,
-                                aux.global_from_compact_gid, aux.num_visible, n, 32, ws.sort_ws, s));
+    BRUSH_HIP_CHECK(depth_sort_launch(ws.pre_keys, ws.pre_gids,
+                                      compact_depth ? reinterpret_cast<uint32_t *>(compact_depth) : ws.sorted_keys,
+                                      aux.global_from_compact_gid, aux.num_visible, n, ws.sort_ws, s));
     mark_fwd(s, 1 + BRUSH_STAGE_DEPTH_SORT);
     if (stop_behind(BRUSH_STAGE_DEPTH_SORT)) return BRUSH_OK;
     // ProjectVisible (render.rs:161-184)

@@ -51,6 +51,7 @@ from . import dataset  # noqa: F401
 # (imported eagerly and after the submodule: the package attribute `depth_loss` is the function, the module stays
 # reachable as `from brush_amd.depth_loss import ...`)
 from .depth_loss import depth_loss, depth_loss_into  # noqa: F401
+from .compose import as_background, compose, compose_backward, compose_forward  # noqa: F401  (as depth_loss above)
 from .pyramid import area_resize, downscaled_size, nearest_resize  # noqa: F401
 from .undistort import (Distortion, fit_scale, undistort_dataset, undistort_depth, undistort_image,  # noqa: F401
                         undistorted_camera)

@@ -198,6 +198,8 @@ _SYMBOLS = [
     ("brush_exposure_backward", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
     ("brush_exposure_backward_adam", C.c_int,
      [_P, _P, C.POINTER(BrushExposureAdam), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_compose_forward", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    ("brush_compose_backward", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     ("brush_depth_loss_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     ("brush_depth_loss", C.c_int,
      [_P, _P, _P, C.POINTER(BrushDepthLoss), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_size_t, _P]),

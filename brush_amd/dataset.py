@@ -86,6 +86,10 @@ class SceneView:
     # Build extension (brush_amd/undistort.py): the lens distortion `camera` leaves out (a COLMAP camera with non-zero
     # distortion coefficients), or None for a pinhole view; undistort_dataset resamples such a view and clears it.
     distortion: Optional["Distortion"] = None  # noqa: F821
+    # Build extension (brush_amd/compose.py): the view's loss mask at the image's final size, uint8 [h,w], the first
+    # channel of whatever the mask file decodes to; nonzero = keep the pixel (COLMAP's and nerfstudio's convention), or
+    # None.
+    mask: Optional[np.ndarray] = None
 
     def image_f32(self) -> np.ndarray:
         """The trainer's target tensor: u8 / 255, alpha kept when present (brush-train/src/image.rs)."""
@@ -192,6 +196,35 @@ def _fit_depth(depth: np.ndarray, orig_hw, final_hw, view_name: str) -> np.ndarr
                                                       if tuple(orig_hw) != tuple(final_hw) else ""))
 
 
+# ---------------------------------------------------------------------------- loss masks (build extension)
+def _decode_mask(data: bytes) -> np.ndarray:
+    """A mask file as uint8 [h,w]: the first channel of whatever it decodes to (a palette is expanded first; wider
+    integers are reduced to "nonzero"); nonzero = keep."""
+    from PIL import Image
+
+    img = Image.open(io.BytesIO(data))
+    if img.mode == "P":
+        img = img.convert("RGBA" if "transparency" in img.info else "RGB")
+    a = np.asarray(img)
+    if a.ndim == 3:
+        a = a[..., 0]
+    if a.dtype != np.uint8:
+        a = (a != 0).astype(np.uint8) * np.uint8(255)
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _fit_mask(mask: np.ndarray, orig_hw, final_hw, view_name: str) -> np.ndarray:
+    """The mask at the image's final size, as _fit_depth treats a depth map (nearest neighbour: a mask is never
+    blended); a mask of any other size is an error naming the view."""
+    if tuple(mask.shape) == tuple(final_hw):
+        return mask
+    if tuple(mask.shape) == tuple(orig_hw):
+        return resize_nearest(mask, final_hw)
+    raise ValueError(f"{view_name}: the mask is {mask.shape[1]}x{mask.shape[0]}, the image "
+                     f"{orig_hw[1]}x{orig_hw[0]}" + (f" (loaded at {final_hw[1]}x{final_hw[0]})"
+                                                      if tuple(orig_hw) != tuple(final_hw) else ""))
+
+
 # ---------------------------------------------------------------------------- small glam equivalents
 def _quat_from_mat3(m: np.ndarray) -> np.ndarray:
     """Unit quaternion (x, y, z, w) of a rotation matrix (columns = rotated axes)."""
@@ -260,6 +293,9 @@ def _read_transforms(files: DatasetFiles, name: str, max_frames, max_resolution)
             view.depth = _fit_depth(depth, orig_hw, img.shape[:2], path)
             view.depth_scale = float(unit) if unit is not None else (U16_DEPTH_SCALE if depth.dtype == np.uint16
                                                                       else 1.0)
+        if frame.get("mask_path"):  # nerfstudio's per-frame loss mask
+            mpath = DatasetFiles.join(base, frame["mask_path"])
+            view.mask = _fit_mask(_decode_mask(files.read_bytes(mpath)), orig_hw, img.shape[:2], path)
         views.append(view)
     return views
 
@@ -472,7 +508,8 @@ def read_colmap(root: str, max_frames: Optional[int] = None, max_resolution: Opt
     uint16, millimetres) or depths/<stem>.npy (float32, scene units) when there is one; an optional
     sparse/0/depth_params.json {stem: {"scale": s, "offset": o}} replaces that view's scale and offset.  A view whose
     camera has non-zero distortion coefficients carries them as `distortion` (brush_amd/undistort.py); camera and image
-    are the ones of the pinhole reading either way."""
+    are the ones of the pinhole reading either way.  A view whose image is images/<name> takes the loss mask
+    masks/<name>.png (COLMAP's own convention, e.g. masks/0001.jpg.png), else masks/<stem>.png, when there is one."""
     from .undistort import Distortion
 
     files = DatasetFiles(root)
@@ -506,6 +543,11 @@ def read_colmap(root: str, max_frames: Optional[int] = None, max_resolution: Opt
                 view.depth_scale = float(depth_params[stem]["scale"])
                 view.depth_offset = float(depth_params[stem].get("offset", 0.0))
             break
+        for mpath in (f"masks/{info.name}.png", f"masks/{stem}.png") if load_images else ():
+            mpath = DatasetFiles.join(base, mpath)
+            if files.exists(mpath):
+                view.mask = _fit_mask(_decode_mask(files.read_bytes(mpath)), orig_hw, img.shape[:2], path)
+                break
         (evals if eval_split_every is not None and i % eval_split_every == 0 else train).append(view)
     return Dataset.from_views(train, evals)
 

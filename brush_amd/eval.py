@@ -9,6 +9,11 @@ Command line (prints one line per view, then the means):
     python -m brush_amd.eval SPLATS DATASET [--format auto|nerf|colmap] [--eval-split-every K]
                              [--max-resolution R] [--num-frames K] [--seed S] [--window 11] [--json OUT]
                              [--depth-metrics] [--depth-mode depth|disparity] [--downscale 1,2,4,8]
+                             [--background white|black|R,G,B] [--no-masks]
+
+--background white scores over a white background (the protocol of the NeRF-synthetic numbers in the literature): the
+render and the image's straight RGBA are composed over the colour first (brush_amd/compose.py).  A view's loss mask
+(nerfstudio's mask_path, COLMAP's masks/<image name>.png) leaves its zero pixels out of the PSNR unless --no-masks.
 
 --downscale 1,2,4,8 is Mip-Splatting's multi-scale protocol: the views are scored once per scale, rendered at 1 / scale
 of their size against the image area-filtered to that size on the device (brush_amd/pyramid.py); one block of lines per
@@ -69,6 +74,8 @@ class EvalView:
     psnr: float
     ssim: float
     aux: object = None
+    # Build extension (loss masks): kept pixels / all pixels of the view's mask at the evaluated level; 1.0 without one.
+    valid_fraction: float = 1.0
 
 
 @dataclass
@@ -99,7 +106,8 @@ def select_views(num_views: int, num_frames: Optional[int] = None,
 
 
 def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np.random.Generator] = None,
-               window: int = 11, keep_aux: bool = False, antialiased: bool = False, downscale: int = 1) -> EvalStats:
+               window: int = 11, keep_aux: bool = False, antialiased: bool = False, downscale: int = 1,
+               background=None, use_masks: bool = True) -> EvalStats:
     """eval.rs:27-77: render each selected view of `scene` (a dataset.Scene, e.g. Dataset.eval) at its image's size
     through Splats.render under no_grad and score it against the image's RGB, uploaded as uint8, with eval_metrics.
     The metrics of all views go into one [V,3] device tensor that is read back once, after the last view.
@@ -112,13 +120,26 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
 
     Trainer state: rendering goes through Splats.render, which applies the SH optimizer steps a SplatTrainer has
     deferred (Splats.sync), exactly as any render or trainer.sync() does; nothing else of the trainer changes.  Call it
-    from the trainer's thread and stream, between step() calls."""
+    from the trainer's thread and stream, between step() calls.
+
+    `background` (None, "white", "black", an (r, g, b) tuple or a float32 [3] device tensor) and the views' loss masks
+    (SceneView.mask, honoured when `use_masks`): with a background or a masked view among the selected ones, each view
+    goes through compose.compose_forward first (render and straight-alpha image composed over the colour, both zeroed
+    where the mask is 0; a mask follows `downscale` through pyramid.nearest_resize) and eval_metrics scores the float32
+    result.  A masked view's `valid_fraction` f is an exact count of the mask's nonzero pixels at the evaluated level,
+    read back with the metrics (at most one more read-back, after the last view), and its psnr is 10 log10(f / mse),
+    computed on the host in float64 from the read-back mse, the PSNR over the kept pixels (nan when f == 0).  Its ssim
+    is the mean SSIM of the masked images as they are, zeroed pixels included: the blur mixes pixels across the mask's
+    edge, so there is no exact per-pixel restriction of it.  With neither option in play the call is the one without
+    them, launch for launch."""
     from .pyramid import area_resize, check_factor
 
     downscale = check_factor(downscale)
     views = scene.views
     idx = select_views(len(views), num_frames, rng)
     dev = splats.means.device
+    if background is not None or (use_masks and any(getattr(views[i], "mask", None) is not None for i in idx)):
+        return _eval_stats_composed(splats, views, idx, window, keep_aux, antialiased, downscale, background, use_masks)
     metrics = torch.empty((len(idx), 3), dtype=torch.float32, device=dev)
     rendered = []
     with torch.no_grad():
@@ -138,6 +159,68 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
     host = metrics.cpu().numpy()  # the one readback
     return EvalStats([EvalView(views[i], r, float(host[k, 1]), float(host[k, 2]), a)
                       for k, (i, (r, a)) in enumerate(zip(idx, rendered))])
+
+
+def _eval_stats_composed(splats, views, idx, window, keep_aux, antialiased, downscale, background, use_masks):
+    """eval_stats with a background and / or masked views (its docstring has the definition)."""
+    import math
+
+    from .compose import as_background, compose_forward
+    from .pyramid import area_resize, nearest_resize
+
+    dev = splats.means.device
+    if isinstance(background, str) and background == "random":
+        raise ValueError("an eval has no 'random' background: score over a fixed colour")
+    bg = as_background(background, dev)
+    metrics = torch.empty((len(idx), 3), dtype=torch.float32, device=dev)
+    masked = use_masks and any(getattr(views[i], "mask", None) is not None for i in idx)
+    kept = torch.zeros(len(idx), dtype=torch.int64, device=dev) if masked else None  # nonzero mask pixels per view
+    pixels = [0] * len(idx)                                                          # mask pixels per view; 0: no mask
+    rendered = []
+    with torch.no_grad():
+        for row, i in enumerate(idx):
+            v = views[i]
+            img = np.require(v.image, requirements=["C", "W"])
+            if img.ndim != 3 or img.dtype != np.uint8 or img.shape[2] not in (3, 4):
+                raise ValueError(f"{v.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
+            gt = torch.from_numpy(img).to(dev)
+            mask = getattr(v, "mask", None) if use_masks else None
+            if mask is not None:
+                if mask.dtype != np.uint8 or tuple(mask.shape) != tuple(img.shape[:2]):
+                    raise ValueError(f"{v.name}: the view's mask must be uint8 [h,w] = {tuple(img.shape[:2])}, got "
+                                     f"{mask.dtype} {mask.shape}")
+                mask = torch.from_numpy(np.array(mask, copy=True, order="C")).to(dev)
+            if downscale > 1:
+                gt = area_resize(gt, factor=downscale)
+                if mask is not None:
+                    mask = nearest_resize(mask.to(torch.int16).view(torch.uint16),
+                                          factor=downscale).view(torch.int16).to(torch.uint8)
+            h, w = int(gt.shape[0]), int(gt.shape[1])
+            pred, aux = splats.render(v.camera, (w, h), False, antialiased=antialiased)
+            if bg is None and mask is None:  # a plain view among masked ones
+                eval_metrics(pred, gt, window, out=metrics[row])
+                shown = pred
+            else:
+                shown, target = compose_forward(pred, gt, background=bg, mask=mask)
+                eval_metrics(shown, target, window, out=metrics[row])
+            if mask is not None:
+                kept[row] = torch.count_nonzero(mask)
+                pixels[row] = h * w
+            rendered.append((shown[..., :3], aux if keep_aux else None))
+    host = metrics.cpu().numpy()  # the read-back of the metrics
+    host_kept = kept.cpu().numpy() if masked else None  # the one further read-back
+    samples = []
+    for k, (i, (r, a)) in enumerate(zip(idx, rendered)):
+        psnr, f = float(host[k, 1]), 1.0
+        if pixels[k] > 0:
+            f = float(host_kept[k]) / float(pixels[k])
+            mse = float(host[k, 0])
+            if f == 0.0:
+                psnr = float("nan")
+            else:
+                psnr = 10.0 * math.log10(f / mse) if mse > 0.0 else float("inf")
+        samples.append(EvalView(views[i], r, psnr, float(host[k, 2]), a, f))
+    return EvalStats(samples)
 
 
 @dataclass
@@ -251,6 +334,11 @@ def parser():
     p.add_argument("--downscale", default=None, metavar="F,...",
                    help="multi-scale eval: score once per factor (1..16, e.g. 1,2,4,8), rendering at 1 / F of each "
                         "view's size against the area-filtered image")
+    p.add_argument("--background", default=None, metavar="white|black|R,G,B",
+                   help="score over this background colour: the render and the image's straight RGBA are composed "
+                        "over it first (white: the protocol of the NeRF-synthetic numbers in the literature)")
+    p.add_argument("--no-masks", action="store_true",
+                   help="ignore the dataset's loss masks (nerfstudio's mask_path, COLMAP's masks/<image name>.png)")
     p.add_argument("--no-undistort", action="store_true",
                    help="score views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
                         "loaded, as if they were pinhole, instead of undistorting them first")
@@ -280,6 +368,17 @@ def main(argv=None) -> int:
             scales = parse_scales(args.downscale)
         except ValueError as e:
             p.error(str(e))
+    background = None
+    if args.background is not None:
+        from .compose import parse_background
+
+        try:
+            background = parse_background(args.background)
+            if background == "random":
+                raise ValueError("--background random is a training option: an eval scores over a fixed colour")
+        except ValueError as e:
+            p.error(str(e))
+    compose_args = {"background": background, "use_masks": not args.no_masks}
 
     data = _load_dataset(args)  # before any GPU work
     if data.eval is None or not data.eval.views:
@@ -298,7 +397,8 @@ def main(argv=None) -> int:
     rng = np.random.default_rng(args.seed)
     scale_rows = None
     if scales is None:
-        stats = eval_stats(splats, data.eval, args.num_frames, rng, args.window, antialiased=args.antialiased)
+        stats = eval_stats(splats, data.eval, args.num_frames, rng, args.window, antialiased=args.antialiased,
+                           **compose_args)
         for s in stats.samples:
             print(f"{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
         print(f"mean ({len(stats.samples)} views)\tpsnr {stats.mean_psnr():.4f}\tssim {stats.mean_ssim():.6f}")
@@ -309,7 +409,8 @@ def main(argv=None) -> int:
         chosen = Scene([data.eval.views[i] for i in select_views(len(data.eval.views), args.num_frames, rng)])
         scale_rows, stats = [], None
         for f in scales:
-            st = eval_stats(splats, chosen, None, None, args.window, antialiased=args.antialiased, downscale=f)
+            st = eval_stats(splats, chosen, None, None, args.window, antialiased=args.antialiased, downscale=f,
+                            **compose_args)
             stats = st if stats is None or f == 1 else stats  # the top-level rows: scale 1 when asked for, else the first
             for s in st.samples:
                 print(f"scale 1/{f}\t{s.view.name}\tpsnr {s.psnr:.4f}\tssim {s.ssim:.6f}")
@@ -329,6 +430,8 @@ def main(argv=None) -> int:
     if args.json:
         res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "window": args.window,
                "antialiased": bool(args.antialiased),
+               "background": list(background) if isinstance(background, tuple) else background,
+               "use_masks": not args.no_masks,
                "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in stats.samples],
                "mean_psnr": stats.mean_psnr(), "mean_ssim": stats.mean_ssim()}
         if scale_rows is not None:

@@ -117,6 +117,18 @@ class TrainConfig:
     # () (the default) is the run without the option, bit for bit.  DESIGN §8 row 15.
     contribution_prune_at: Tuple[int, ...] = ()
     contribution_prune_min: float = 0.01
+    # Build extension: background colour and loss masks (brush_amd/compose.py; gsplat's backgrounds / masks and
+    # nerfstudio's mask_path are the models).  background: None (the render is compared as it is, premultiplied, against
+    # the image's straight RGB(A)), "white", "black", an (r, g, b) tuple, or "random": the render and the target are
+    # composed over that colour in front of the loss, the target then being opaque RGB; "random" draws torch.rand(3) per
+    # step from a device generator seeded from `seed` (no upload, no synchronisation; evaluates over black), the usual
+    # way to keep splats of an RGBA object capture from hiding behind a black background.  use_masks: the training loop
+    # hands a view's mask (SceneView.mask, nonzero = keep) to the step, which zeroes the other pixels of both images and
+    # of the gradient; the resident depth maps are zeroed under the masks at load, so the depth term skips them too.
+    # None with no masked view is the run without the option, launch for launch and bit for bit.  Works on every
+    # optimizer path.  DESIGN §8 row 16.
+    background: object = None
+    use_masks: bool = True
 
     def check_contribution_prune(self) -> Tuple[int, ...]:
         """contribution_prune_at as a tuple of ints, or a ValueError naming what is wrong with the two fields."""
@@ -237,6 +249,9 @@ class SplatTrainer:
             raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
         self.config.check_downscale_schedule()
         self.config.check_contribution_prune()
+        from .compose import check_background
+        check_background(self.config.background)
+        self._bg_rng, self._bg_fixed = None, {}  # "random"'s device generator; the fixed colours' device tensors
         dev = splats.means.device
         assert dev.type == "cuda", "brush_amd has no CPU path: the splats must live on the GPU"
         self.iter = 0
@@ -403,6 +418,24 @@ class SplatTrainer:
         gamma = c.lr_mean_decay ** (1.0 / c.total_steps)
         return c.lr_mean * gamma ** self.iter * scene_extent
 
+    def _background(self, background, dev) -> Optional[torch.Tensor]:
+        """step's `background` as the float32 [3] device tensor brush_compose_* reads: a tensor is taken as it is, a
+        fixed colour is uploaded once and kept, "random" is drawn on the device from a generator seeded from
+        config.seed."""
+        from .compose import as_background, check_background
+
+        if background is None or isinstance(background, torch.Tensor):
+            return as_background(background, dev)
+        background = check_background(background)
+        if background == "random":
+            if self._bg_rng is None:
+                self._bg_rng = torch.Generator(device=dev)
+                self._bg_rng.manual_seed(self.config.seed)
+            return as_background("random", dev, self._bg_rng)
+        if background not in self._bg_fixed:
+            self._bg_fixed[background] = as_background(background, dev)
+        return self._bg_fixed[background]
+
     def _lr_exposure(self) -> float:
         c = self.config
         gamma = c.lr_exposure_decay ** (1.0 / c.total_steps)
@@ -419,7 +452,7 @@ class SplatTrainer:
              batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None,
              loss_out: Optional[torch.Tensor] = None, view_index: Optional[int] = None, poses=None,
              exposures=None, gt_depth: Optional[torch.Tensor] = None, depth_scale: float = 1.0,
-             depth_offset: float = 0.0):
+             depth_offset: float = 0.0, background=None, gt_mask: Optional[torch.Tensor] = None):
         """One reference training iteration on one view (batch size is 1 in the reference,
         train.rs:216-219).  `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the
         same bits as its float32 twin; brush_amd.scene_loader keeps the training images on the device in this form).
@@ -443,7 +476,13 @@ class SplatTrainer:
         is rendered with its depth output, brush_depth_loss adds the depth term's alpha gradient into the colour loss's
         gradient and the term itself into the step's loss, and the backward carries the depth gradient
         (brush_render_backward_depth); the step then takes the separate-call path whatever `fused_backward` says.  With
-        gt_depth None or a zero weight the step is the one without the option.  Not with `exchange` / `grad_sync`."""
+        gt_depth None or a zero weight the step is the one without the option.  Not with `exchange` / `grad_sync`.
+        `background` (None, "white", "black", "random", an (r, g, b) tuple or a float32 [3] device tensor) and `gt_mask`
+        (uint8 [h,w] on the device, nonzero = keep): the image the loss would see (the render, or its exposure-compensated
+        form) and the target go through brush_compose_forward first, and the loss's gradient through
+        brush_compose_backward, in place, before the exposure backward and every render backward path.  With a
+        background the loss compares opaque RGB.  The depth term is not masked here: scene_loader zeroes the depth maps
+        under the masks at load.  On every optimizer path; with both None the step is the one without the option."""
         c = self.config
         use_mcmc = c.strategy == "mcmc"
         if gt_depth is not None and (exchange is not None or grad_sync is not None):
@@ -503,7 +542,17 @@ class SplatTrainer:
                                        lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat, depth=depth_bufs)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
-        if exposures is None:
+        bg = None if background is None else self._background(background, means.device)
+        if bg is not None or gt_mask is not None:
+            from .compose import compose_backward, compose_forward
+            seen = pred if exposures is None else exposures.forward(view_index, pred)
+            seen, target = compose_forward(seen, gt_image, background=bg, mask=gt_mask)
+            loss, v_pred = l1_ssim_loss(seen, target, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views,
+                                        out=loss_out)
+            compose_backward(v_pred, background=bg, mask=gt_mask, out=v_pred)
+            if exposures is not None:
+                v_pred = exposures.backward_step(view_index, pred, v_pred, lr=self._lr_exposure())
+        elif exposures is None:
             loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views,
                                         out=loss_out)
         else:  # the loss sees the compensated image; the backward below sees the raw render and the gradient at it

@@ -18,6 +18,12 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
         [--downscale-schedule STEP:FACTOR,...] [--num-downscales K] [--resolution-schedule S]
         [--contribution-prune-at STEP,...] [--contribution-prune-min 0.01]
+        [--background white|black|random|R,G,B] [--no-masks]
+
+--background composes the render and the (straight-alpha) target over a colour in front of the loss and in the evals
+(TrainConfig.background, brush_amd/compose.py); random draws a colour per step on the device and evaluates over black.
+Loss masks (nerfstudio's mask_path; COLMAP's masks/<image name>.png) are honoured unless --no-masks is given: masked
+pixels are left out of the loss, the depth term and the eval's PSNR.
 
 --contribution-prune-at 16000,24000 drops, after each listed step, the splats whose largest blending weight over all
 training views stays below --contribution-prune-min (TrainConfig.contribution_prune_at, brush_amd/contribution.py); the
@@ -88,6 +94,8 @@ class TrainLog:
     exposures: Optional[List[List[float]]] = None    # exposure_opt: the 3x4 map (12 floats, row-major) of every view
     downscales: List[Tuple[int, int]] = field(default_factory=list)  # (step, factor): the level switches that happened
     prunes: List[Tuple[int, int, int]] = field(default_factory=list)  # (step, splats before, after): contribution prunes
+    background: object = None                     # TrainConfig.background as configured
+    masked_views: int = 0                         # training views whose loss mask the run used
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
@@ -95,6 +103,8 @@ class TrainLog:
                 "pose_deltas": self.pose_deltas, "exposure_opt": self.exposure_opt, "exposures": self.exposures,
                 "downscales": [[int(s), int(f)] for s, f in self.downscales],
                 "prunes": [[int(s), int(b), int(a)] for s, b, a in self.prunes],
+                "background": list(self.background) if isinstance(self.background, tuple) else self.background,
+                "masked_views": int(self.masked_views),
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -169,7 +179,7 @@ class TrainLoop:
         else:
             self.splats = Splats.from_random_config(init_count, sh_degree, random_init_bounds(dataset.train), self.rng,
                                                     self.device)
-        self.loader = SceneLoader(dataset.train, seed, self.device)
+        self.loader = SceneLoader(dataset.train, seed, self.device, use_masks=self.config.use_masks)
         self.trainer = SplatTrainer(self.splats, self.config)
         self.poses = None
         if self.config.pose_opt:
@@ -185,9 +195,14 @@ class TrainLoop:
                                            self.config.exposure_reg)
         # depth supervision: the drawn view's resident depth map goes with the step (views without one train as before)
         self._depth = self.config.depth_weight > 0.0 and any(d is not None for d in self.loader.depths)
+        # background colour and loss masks: the drawn view's resident mask and the configured colour go with the step
+        self._masks = any(m is not None for m in self.loader.masks)
+        self._compose = self.config.background is not None or self._masks
         self.losses = torch.zeros(self.steps, dtype=torch.float32, device=self.device)
         self.done = 0
-        self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes)
+        self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes,
+                            background=self.config.background,
+                            masked_views=sum(m is not None for m in self.loader.masks))
         self._t0 = time.perf_counter()
         self._eval_seconds = 0.0
         self._last = (0, 0.0)  # (step, training seconds) of the previous eval row
@@ -201,7 +216,7 @@ class TrainLoop:
         if factor != self.loader.downscale:  # a level switch: launches only (SceneLoader.set_downscale)
             self.loader.set_downscale(factor)
             self.log.downscales.append((self.done, factor))
-        if self.poses is None and self.exposures is None and not self._depth:
+        if self.poses is None and self.exposures is None and not self._depth and not self._compose:
             view, gt = self.loader.next_batch()
             self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
                               loss_out=self.losses[self.done:self.done + 1])
@@ -213,7 +228,8 @@ class TrainLoop:
                               view_index=i if (self.poses is not None or self.exposures is not None) else None,
                               poses=self.poses, exposures=self.exposures, gt_depth=depth,
                               depth_scale=getattr(view, "depth_scale", 1.0),
-                              depth_offset=getattr(view, "depth_offset", 0.0))
+                              depth_offset=getattr(view, "depth_offset", 0.0),
+                              background=self.config.background, gt_mask=self.loader.mask(i) if self._masks else None)
         if self.done in self._prune_at:
             self.prune_by_contribution()
         self.done += 1
@@ -255,8 +271,11 @@ class TrainLoop:
         torch.cuda.synchronize(self.device)  # the training time up to here is done
         t = time.perf_counter()
         train_s = t - self._t0 - self._eval_seconds
-        # evaluated in the mode the splats are trained in
-        stats = eval_stats(self.splats, self.dataset.eval, eval_views, self.rng, antialiased=self.config.antialiased)
+        # evaluated in the mode the splats are trained in; a random training background evaluates over black
+        # (with no background and no masked eval view eval_stats is the call without the options)
+        bg = "black" if self.config.background == "random" else self.config.background
+        stats = eval_stats(self.splats, self.dataset.eval, eval_views, self.rng, antialiased=self.config.antialiased,
+                           background=bg, use_masks=self.config.use_masks)
         loss = float(self.losses[self.done - 1].item()) if self.done > 0 else float("nan")
         dstep, dt = self.done - self._last[0], train_s - self._last[1]
         row = EvalRow(self.done, stats.mean_psnr(), stats.mean_ssim(), self.splats.num_splats(),
@@ -413,6 +432,11 @@ def parser():
     p.add_argument("--contribution-prune-min", type=float, default=TrainConfig.contribution_prune_min, metavar="T",
                    help="--contribution-prune-at: the threshold on the largest blending weight (0: only splats that "
                         "are never composited and never stop a pixel)")
+    p.add_argument("--background", default=None, metavar="white|black|random|R,G,B",
+                   help="compose the render and the target over this colour in front of the loss and in the evals; "
+                        "random draws a colour per step (and evaluates over black)")
+    p.add_argument("--no-masks", action="store_true",
+                   help="ignore the dataset's loss masks (nerfstudio's mask_path, COLMAP's masks/<image name>.png)")
     p.add_argument("--no-undistort", action="store_true",
                    help="train on views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
                         "loaded, as if they were pinhole, instead of undistorting them first")
@@ -431,6 +455,8 @@ def main(argv=None) -> int:
         prune_at = () if args.contribution_prune_at is None else parse_prune_steps(args.contribution_prune_at)
         check_contribution_prune(TrainConfig(strategy=args.strategy, contribution_prune_at=prune_at,
                                              contribution_prune_min=args.contribution_prune_min))
+        from .compose import parse_background
+        background = None if args.background is None else parse_background(args.background)
     except ValueError as e:
         p.error(str(e))
     if not os.path.exists(args.dataset):
@@ -480,7 +506,8 @@ def main(argv=None) -> int:
                          mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt, depth_weight=args.depth_weight,
                          depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
                          downscale_schedule=schedule, contribution_prune_at=prune_at,
-                         contribution_prune_min=args.contribution_prune_min)
+                         contribution_prune_min=args.contribution_prune_min, background=background,
+                         use_masks=not args.no_masks)
     splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,

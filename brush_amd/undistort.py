@@ -243,8 +243,9 @@ def dataset_distortions(dataset) -> list:
 
 
 def undistort_dataset(dataset, device=None, scale: Optional[float] = None):
-    """A new Dataset in which every view that has a `distortion` carries its image and depth map resampled on the
-    device (undistort_image / undistort_depth at `scale`, None: fit_scale per camera), the undistorted camera and
+    """A new Dataset in which every view that has a `distortion` carries its image, depth map and loss mask resampled
+    on the device (undistort_image / undistort_depth at `scale`, None: fit_scale per camera; the mask goes through the
+    depth maps' nearest remap, so a pixel whose source lies outside the frame is 0, not kept), the undistorted camera and
     `distortion=None`; the other views are shared unchanged.  Plans are kept per (Distortion, scale): COLMAP datasets
     usually share one camera.  The first view of each plan also fetches the validity mask, which is checked once:
     ValueError if any pixel is invalid (the distortion folds inside the frame, or `scale` is too small).
@@ -279,7 +280,12 @@ def undistort_dataset(dataset, device=None, scale: Optional[float] = None):
         if depth is not None:
             _check_source(depth.shape, d, f"{view.name}: the depth map")
             depth = remap_depth(torch.from_numpy(np.array(depth, copy=True, order="C")).to(dev), m, size).cpu().numpy()
-        return dataclasses.replace(view, image=out.cpu().numpy(), depth=depth,
+        mask = getattr(view, "mask", None)
+        if mask is not None:  # the nearest remap of the depth maps, on the mask as uint16: a pixel without a source is 0
+            _check_source(mask.shape, d, f"{view.name}: the mask")
+            wide = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint16)).to(dev)
+            mask = remap_depth(wide, m, size).cpu().numpy().astype(np.uint8)
+        return dataclasses.replace(view, image=out.cpu().numpy(), depth=depth, mask=mask,
                                    camera=undistorted_camera(view.camera, d, s), distortion=None)
 
     train = Scene([convert(v) for v in dataset.train.views])

@@ -535,6 +535,41 @@ int brush_exposure_backward_adam(const float *pred, const float *v_out, const Br
                                  uint32_t h, float *v_pred, float *exposure, float *moment1, float *moment2,
                                  float *v_exposure, void *workspace, size_t workspace_bytes, brush_stream_t stream);
 
+/* ---- background colour and loss masks (build extension; gsplat's backgrounds / masks, nerfstudio's mask_path) ----- */
+/* Two element-wise maps that sit directly in front of the colour loss and behind it.  The op renders a premultiplied
+ * image with no background; a trainer composes it, and the straight-alpha target, over a background colour b, and
+ * leaves out the pixels a mask rules out.
+ *   pred [h][w][4] f32: the premultiplied render, alpha = pred.w.
+ *   gt   [h][w][Cg], Cg = gt_channels = 3 or 4, STRAIGHT alpha: u8 (BRUSH_EVAL_GT_U8, read as (float)b / 255.0f with an
+ *        IEEE division) or f32 (BRUSH_EVAL_GT_F32, read as stored).
+ *   mask [h][w] u8 or NULL: a pixel is KEPT when mask == NULL or mask[p] != 0 (COLMAP's and nerfstudio's convention).
+ *   background: a DEVICE pointer to 3 f32, or NULL.  It lives on the device so that a colour drawn per step costs no
+ *        upload and no synchronisation, and the call stays graph-capturable.
+ * At least one of mask and background must be given.  Every operation below is one f32 operation rounded on its own
+ * (never contracted).  Forward, with a background (out_gt then has 3 channels):
+ *   t = 1.0f - alpha;   out_pred.c = pred.c + t * b_c  (c = 0..2);   out_pred.w = alpha
+ *   Cg == 4:  s = 1.0f - G_a;   out_gt.c = G_c * G_a + s * b_c            Cg == 3:  out_gt.c = G_c
+ * and without one (out_gt then has Cg channels): out_pred = pred, bits kept; out_gt.k = G_k.  A pixel that is not kept
+ * is +0.0f in every word of out_pred and out_gt, by selection and not by multiplication: a NaN under the mask does not
+ * leak.  The colour loss runs on (out_pred, out_gt); brush_compose_backward turns its v_out = d L / d out_pred into the
+ * gradient at pred:
+ *   kept:      v_pred.c = v_out.c;   v_pred.w = v_out.w - ((b_0 v_0 + b_1 v_1) + b_2 v_2)   (v_out.w without a background)
+ *   not kept:  +0.0f in all four words
+ * v_pred may alias v_out.  out_pred may not alias pred (the compositing backward needs the raw render), and out_gt may
+ * alias neither gt nor out_pred.
+ * Consequences: with a background the target is opaque RGB, so brush_l1_ssim_loss* then runs with gt_channels = 3 and
+ * alpha is not compared, as in gsplat.  The L1 mean stays over all w h pixels: masked pixels contribute 0 to L1 and a
+ * constant to SSIM, which is nerfstudio's (pred * mask, gt * mask) and the convention brush_depth_loss already has.
+ * All pointers are device pointers; the four images are 16-byte aligned, background 4-byte; w h in [1, 2^28).  A NULL
+ * required pointer, a misaligned one, both options NULL, any other gt_dtype / gt_channels or size returns
+ * BRUSH_ERR_INVALID_ARG, checked before any GPU call.  No workspace, no allocation, no synchronisation:
+ * graph-capturable; the same inputs give the same bits on every call. */
+int brush_compose_forward(const float *pred, const void *gt, uint32_t gt_dtype, uint32_t gt_channels,
+                          const uint8_t *mask, const float *background, uint32_t w, uint32_t h,
+                          float *out_pred, float *out_gt, brush_stream_t stream);
+int brush_compose_backward(const float *v_out, const uint8_t *mask, const float *background,
+                           uint32_t w, uint32_t h, float *v_pred, brush_stream_t stream);
+
 /* ---- depth supervision (build extension; the 3DGS trainer's depth regulariser, gsplat's depth_loss) ------------- */
 /* An L1 loss between the rendered expected depth and a per-view depth map, and both of its gradients, in one pass.
  * Per pixel p: a = pred[p].w, the alpha of the raw render pred [h][w][4] f32 (brush_render_forward_depth's image);

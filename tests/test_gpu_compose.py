@@ -1,0 +1,560 @@
+"""Background colour and loss masks on the GPU: the kernels of brush_amd/csrc/compose.hip against the float32
+restatement of tests/compose_ref.py bit for bit, repeatability and graph replay, the autograd function, the trainer on
+both optimizer paths, the loader, the eval and one scene trained end to end over a random background.
+
+The kernels run one lane per pixel over the whole grid: no stride loop, no grid cap, no vector tail, no
+alignment-dependent path.  The only boundaries are the wave (64) and the workgroup (256), which SHAPES straddles.
+The end-to-end threshold comes from a run on the MI355X and is recorded in profiles/compose_margins.json
+(BRUSH_COMPOSE_MARGINS=path makes a run write its own figures there)."""
+import dataclasses
+import json
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import compose_ref as R
+from tests import eval_data as E
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [(1, 1), (3, 1), (5, 1), (7, 5), (63, 1), (64, 1), (65, 3), (33, 31), (255, 1), (257, 1), (129, 127)]
+BG = (0.25, 0.5, 1.0)
+MARGINS = {}
+PARAMS = ("means", "log_scales", "rotation", "raw_opacity", "sh_coeffs")
+
+# End to end (test 7): white-background eval PSNR after E2E_STEPS steps over a random background minus that of the
+# initial splats, measured on the MI355X; the gate is half of it.
+E2E_STEPS = 300
+E2E_GAIN_MEASURED_DB = 5.465
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import brush_amd  # noqa: F401
+
+    yield torch.device("cuda:0")
+    path = os.environ.get("BRUSH_COMPOSE_MARGINS")
+    if MARGINS and path:
+        with open(path, "w") as f:
+            json.dump(MARGINS, f, indent=1, sort_keys=True)
+
+
+@pytest.fixture
+def deterministic():
+    from brush_amd import render as RD
+
+    old = RD.DETERMINISTIC
+    RD.DETERMINISTIC = True
+    yield
+    RD.DETERMINISTIC = old
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _bits(a):
+    a = _np(a) if not isinstance(a, np.ndarray) else a
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _up(a, dev):
+    import torch
+
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _bg(dev, colour=BG):
+    import torch
+
+    return torch.tensor(colour, dtype=torch.float32).to(dev)
+
+
+# ---------------------------------------------------------------------------- 1. kernels against the restatement
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_kernels_match_the_f32_restatement_bitwise(dev, w, h):
+    import torch
+
+    from brush_amd import compose_backward, compose_forward
+
+    bg_t = _bg(dev)
+    n = 0
+    for gt_dtype in (np.uint8, np.float32):
+        for cg in (3, 4):
+            for mask_kind in (None, "random", "zero", "full"):
+                pred, gt, mask, v_out = R.case(w, h, cg, gt_dtype, mask_kind, seed=1000 * w + 10 * h + cg)
+                t_pred, t_gt, t_mask, t_v = (_up(a, dev) for a in (pred, gt, mask, v_out))
+                for bg in (None, BG):
+                    if bg is None and mask is None:
+                        continue
+                    tag = (w, h, gt_dtype.__name__, cg, mask_kind, bg)
+                    want_out, want_gt = R.forward32(pred, gt, bg, mask)
+                    want_v = R.backward32(v_out, bg, mask)
+                    b = None if bg is None else bg_t
+                    out, target = compose_forward(t_pred, t_gt, background=b, mask=t_mask)
+                    assert tuple(target.shape) == (h, w, 3 if bg is not None else cg), tag   # out_gt channel count
+                    assert tuple(out.shape) == (h, w, 4) and out.dtype == target.dtype == torch.float32
+                    assert np.array_equal(_bits(out), _bits(want_out)), tag
+                    assert np.array_equal(_bits(target), _bits(want_gt)), tag
+                    v_pred = compose_backward(t_v, background=b, mask=t_mask)
+                    assert np.array_equal(_bits(v_pred), _bits(want_v)), tag
+                    assert np.array_equal(_bits(t_v), _bits(v_out)), tag                     # the input is untouched
+                    alias = t_v.clone()                                                      # backward in place
+                    assert compose_backward(alias, background=b, mask=t_mask, out=alias) is alias
+                    assert np.array_equal(_bits(alias), _bits(want_v)), tag
+                    n += 1
+    assert n == 2 * 2 * (4 * 2 - 1)
+
+
+def test_wrappers_out_buffers_and_errors(dev):
+    import torch
+
+    from brush_amd import compose_backward, compose_forward
+
+    w, h = 33, 31
+    pred, gt, mask, v_out = R.case(w, h, 4, np.uint8, "random", 3)
+    pred[2, 3], v_out[2, 3], mask[2, 3] = np.nan, np.nan, 0    # a NaN under the mask does not leak
+    t_pred, t_gt, t_mask, t_v = (_up(a, dev) for a in (pred, gt, mask, v_out))
+    bg = _bg(dev)
+    bufs = (torch.full((h, w, 4), 7.0, device=dev), torch.full((h, w, 3), 7.0, device=dev))
+    out, target = compose_forward(t_pred, t_gt, background=bg, mask=t_mask, out=bufs)
+    assert out is bufs[0] and target is bufs[1]
+    want_out, want_gt = R.forward32(pred, gt, BG, mask)
+    assert np.array_equal(_bits(out), _bits(want_out)) and np.array_equal(_bits(target), _bits(want_gt))
+    assert np.isfinite(_np(out)).all() and np.isfinite(_np(compose_backward(t_v, background=bg, mask=t_mask))).all()
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt)                                            # neither option
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt, background=bg, out=(bufs[0], bufs[0]))     # out_gt's shape
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt, mask=t_mask, out=bufs)                     # without a background: 4 channels
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt, background=bg, out=(t_pred, bufs[1]))      # out_pred is pred
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt.to(torch.int16), background=bg)             # dtype
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt[:, :, :2], background=bg)                   # channels
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt, mask=t_mask[:, :-1])                       # mask shape
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt, mask=t_mask.float())                       # mask dtype
+    with pytest.raises(ValueError):
+        compose_forward(t_pred, t_gt, background=bg.cpu())                       # device
+    with pytest.raises(ValueError):
+        compose_forward(t_pred[..., :3], t_gt, background=bg)
+    with pytest.raises(ValueError):
+        compose_backward(t_v, background=torch.zeros(4, device=dev))
+    with pytest.raises(ValueError):
+        compose_backward(t_v.double(), mask=t_mask)
+
+
+# ---------------------------------------------------------------------------- 2. repeatability and graph replay
+def test_repeatable_and_graph_replay(dev):
+    import torch
+
+    from brush_amd import compose_backward, compose_forward
+
+    w, h = 129, 127
+    pred, gt, mask, v_out = R.case(w, h, 4, np.uint8, "random", 21)
+    t_pred, t_gt, t_mask, t_v = (_up(a, dev) for a in (pred, gt, mask, v_out))
+    bg = _bg(dev)
+
+    def run(bufs=None, v_buf=None):
+        out, target = compose_forward(t_pred, t_gt, background=bg, mask=t_mask, out=bufs)
+        return out, target, compose_backward(t_v, background=bg, mask=t_mask, out=v_buf)
+
+    first, again = run(), run()
+    torch.cuda.synchronize()
+    for a, b in zip(first, again):
+        assert np.array_equal(_bits(a), _bits(b))
+    bufs = (torch.zeros((h, w, 4), device=dev), torch.zeros((h, w, 3), device=dev))
+    v_buf = torch.zeros((h, w, 4), device=dev)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # warm-up off the default stream, as torch's capture recipe asks
+        run(bufs, v_buf)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        run(bufs, v_buf)
+    for colour in (BG, (0.75, 0.125, 0.5)):  # the background is read from the device at replay
+        bg.copy_(_bg(dev, colour))
+        want = run()
+        for t in bufs + (v_buf,):
+            t.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        for a, b in zip(want, bufs + (v_buf,)):
+            assert np.array_equal(_bits(a), _bits(b))
+    assert not np.array_equal(_bits(want[0]), _bits(first[0]))
+
+
+# ---------------------------------------------------------------------------- 3. autograd
+@pytest.mark.parametrize("use_bg,use_mask", [(True, True), (True, False), (False, True)])
+def test_compose_autograd_equals_the_backward_wrapper(dev, use_bg, use_mask):
+    import torch
+
+    from brush_amd import compose, compose_backward, compose_forward
+
+    w, h = 65, 3
+    pred, gt, mask, v_out = R.case(w, h, 4, np.uint8, "random", 8)
+    t_pred, t_gt, t_mask, t_v = (_up(a, dev) for a in (pred, gt, mask, v_out))
+    bg, m = (_bg(dev) if use_bg else None), (t_mask if use_mask else None)
+    img = t_pred.clone().requires_grad_(True)
+    out, target = compose(img, t_gt, background=bg, mask=m)
+    assert not target.requires_grad
+    (g_img,) = torch.autograd.grad((out * t_v).sum(), [img])
+    want_out, want_target = compose_forward(t_pred, t_gt, background=bg, mask=m)
+    want_v = compose_backward(t_v, background=bg, mask=m)
+    assert np.array_equal(_bits(out), _bits(want_out)) and np.array_equal(_bits(target), _bits(want_target))
+    assert np.array_equal(_bits(g_img), _bits(want_v))
+    if use_bg:  # the alpha term is there
+        kept = np.ones((h, w), bool) if not use_mask else mask != 0
+        assert (_np(g_img)[..., 3][kept] != v_out[..., 3][kept]).any()
+        assert np.array_equal(_bits(g_img), _bits(R.backward32(v_out, BG, mask if use_mask else None)))
+
+
+# ---------------------------------------------------------------------------- 4. trainer, deterministic mode
+def _ring(n, w, h):
+    from tests import test_gpu_train_loop as TL
+
+    return [cam for _, cam in TL._ring_cameras(n, w, h)]
+
+
+def _trajectory(dev, cams, gts, fused, masks=None, background=None, steps=6):
+    """The parameters' bits after `steps` trainer steps on views 0..3 in turn."""
+    from brush_amd import Splats, SplatTrainer, TrainConfig
+
+    splats = Splats.from_random_config(1024, 3, (np.full(3, -1.0), np.full(3, 1.0)), np.random.default_rng(3), dev)
+    tr = SplatTrainer(splats, TrainConfig(deferred_sh_adam=fused))
+    tr.fused_backward = fused
+    for i in range(steps):
+        k = i % len(cams)
+        tr.step(splats, cams[k], gts[k], 1.0, background=background, gt_mask=None if masks is None else masks[k])
+    tr.sync(splats)
+    return {k: _bits(getattr(splats, k)) for k in PARAMS}
+
+
+def _same(a, b):
+    return all(np.array_equal(a[k], b[k]) for k in PARAMS)
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused_deferred", "separate_calls"])
+def test_trainer_trajectories_are_exact(dev, deterministic, fused):
+    import torch
+
+    w = h = 64
+    cams = _ring(4, w, h)
+    rgb = [E.noise_image(w, h, 3, 50 + i) for i in range(4)]
+    rgba = [E.noise_image(w, h, 4, 60 + i) for i in range(4)]
+    up = lambda imgs: [_up(im, dev) for im in imgs]
+    full = [torch.full((h, w), 255, dtype=torch.uint8, device=dev)] * 4
+    base_rgb = _trajectory(dev, cams, up(rgb), fused)
+    base_rgba = _trajectory(dev, cams, up(rgba), fused)
+    assert not _same(base_rgb, base_rgba)
+    # (a) an all-255 mask is the run without a mask
+    assert _same(_trajectory(dev, cams, up(rgb), fused, masks=full), base_rgb)
+    assert _same(_trajectory(dev, cams, up(rgba), fused, masks=full), base_rgba)
+    # (b) two targets that differ only under a mask covering a quarter of each view
+    mask = np.full((h, w), 255, dtype=np.uint8)
+    mask[: h // 2, w // 2:] = 0
+    other = [im.copy() for im in rgb]
+    for k, im in enumerate(other):
+        im[mask == 0] = E.noise_image(w, h, 3, 90 + k)[mask == 0]
+    masks = [_up(mask, dev)] * 4
+    with_a = _trajectory(dev, cams, up(rgb), fused, masks=masks)
+    with_b = _trajectory(dev, cams, up(other), fused, masks=masks)
+    assert _same(with_a, with_b)
+    assert not _same(with_a, base_rgb)                                      # the mask does something
+    assert not _same(_trajectory(dev, cams, up(other), fused), base_rgb)    # withheld: the targets do differ
+    # (c) black behind an RGB target is the run without a background
+    assert _same(_trajectory(dev, cams, up(rgb), fused, background="black"), base_rgb)
+    assert not _same(_trajectory(dev, cams, up(rgba), fused, background="white"), base_rgba)
+
+
+def test_step_with_background_and_mask_does_not_synchronise(dev):
+    import torch
+
+    from brush_amd import Splats, SplatTrainer, TrainConfig
+
+    w = h = 64
+    cams = _ring(4, w, h)
+    gts = [_up(E.noise_image(w, h, 4, 70 + i), dev) for i in range(4)]
+    mask = _up(R.case(w, h, 3, np.uint8, "random", 1)[2], dev)
+    splats = Splats.from_random_config(1024, 3, (np.full(3, -1.0), np.full(3, 1.0)), np.random.default_rng(3), dev)
+    tr = SplatTrainer(splats, TrainConfig())
+    for bg in ("random", BG):   # the first step fills the deferred-SH table; each fixed colour is uploaded once
+        tr.step(splats, cams[0], gts[0], 1.0, background=bg, gt_mask=mask)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        with pytest.raises(RuntimeError):
+            torch.tensor(BG).to(dev)  # the mode sees an upload
+        losses = [tr.step(splats, cams[i % 4], gts[i % 4], 1.0, background=bg, gt_mask=mask)[0]
+                  for i, bg in enumerate(("random", BG, "random", BG))]
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    assert all(np.isfinite(float(l)) for l in losses)
+    # "random" is reproducible: the same seed draws the same colours
+    a, b = SplatTrainer(splats, TrainConfig(seed=9)), SplatTrainer(splats, TrainConfig(seed=9))
+    draws = [[_np(t._background("random", dev)) for _ in range(3)] for t in (a, b)]
+    assert np.array_equal(np.stack(draws[0]), np.stack(draws[1])) and not np.array_equal(draws[0][0], draws[0][1])
+    want = torch.rand(3, generator=torch.Generator(device=dev).manual_seed(9), device=dev)
+    assert np.array_equal(draws[0][0], _np(want))
+
+
+# ---------------------------------------------------------------------------- 5. loader
+def _masked_scene(w, h, n=3):
+    from brush_amd.dataset import Scene, SceneView
+
+    cams = _ring(n, w, h)
+    views = []
+    for i in range(n):
+        _, _, mask, _ = R.case(w, h, 3, np.uint8, "random", 40 + i)
+        depth = np.random.default_rng(i).integers(1, 60000, (h, w)).astype(np.uint16 if i % 2 == 0 else np.float32)
+        views.append(SceneView(f"v{i}", cams[i], E.noise_image(w, h, 3, i), depth=depth if i < 2 else None,
+                               mask=mask if i != 1 else None))
+    return Scene(views)
+
+
+def test_loader_masks_levels_and_depth(dev):
+    from brush_amd.dataset import resize_nearest
+    from brush_amd.pyramid import downscaled_size
+    from brush_amd.scene_loader import SceneLoader
+
+    w, h = 50, 37
+    scene = _masked_scene(w, h)
+    loader = SceneLoader(scene, 1, dev)
+    assert loader.mask(1) is None and len(loader.masks) == 3
+    for i in (0, 2):
+        assert np.array_equal(_np(loader.mask(i)), scene.views[i].mask)
+    plain = w * h * 3 * 3 + w * h * (2 + 4)
+    assert loader.total_bytes == plain + 2 * w * h
+    # depth is zeroed under the mask at load (view 0 has both); a view without a mask keeps its map
+    d0 = _np(loader.depth(0))
+    gone = scene.views[0].mask == 0
+    assert gone.any() and (d0[gone] == 0).all() and np.array_equal(d0[~gone], scene.views[0].depth[~gone])
+    assert scene.views[0].depth[gone].all()                       # the host copy is untouched
+    assert np.array_equal(_np(loader.depth(1)), scene.views[1].depth)
+    for factor in (2, 3):
+        loader.set_downscale(factor)
+        ow, oh = downscaled_size(w, h, factor)
+        for i in (0, 2):
+            got = loader.mask(i)
+            assert got.dtype == __import__("torch").uint8
+            assert np.array_equal(_np(got), resize_nearest(scene.views[i].mask, (oh, ow))), (factor, i)
+        assert loader.mask(1) is None
+        assert loader.level_bytes == 3 * ow * oh * 3 + ow * oh * (2 + 4) + 2 * ow * oh
+    loader.set_downscale(1)
+    assert loader.level_bytes == 0 and loader.mask(0) is loader.masks[0]
+    off = SceneLoader(scene, 1, dev, use_masks=False)
+    assert off.mask(0) is None and off.total_bytes == plain
+    assert np.array_equal(_np(off.depth(0)), scene.views[0].depth)
+
+
+def test_undistort_dataset_carries_the_mask(dev):
+    import torch
+
+    from brush_amd.dataset import Dataset, Scene, SceneView
+    from brush_amd.undistort import Distortion, fit_scale, remap_depth, undistort_dataset, undistort_map
+
+    w, h = 48, 40
+    d = Distortion("SIMPLE_RADIAL", w, h, 40.0, 40.0, 24.5, 19.5, k1=0.12)
+    _, _, mask, _ = R.case(w, h, 3, np.uint8, "random", 77)
+    view = SceneView("v0", _ring(1, w, h)[0], E.noise_image(w, h, 3, 4), mask=mask, distortion=d)
+    out = undistort_dataset(Dataset(Scene([view]))).train.views[0]
+    assert out.distortion is None and out.mask.dtype == np.uint8 and out.mask.shape == (h, w)
+    want = remap_depth(torch.from_numpy(mask.astype(np.uint16)).to(dev), undistort_map(d, fit_scale(d)), (w, h))
+    assert np.array_equal(out.mask, _np(want).astype(np.uint8))
+    assert not np.array_equal(out.mask, mask) and np.array_equal(view.mask, mask)
+    # at a scale that leaves border pixels without a source, those come out 0 (not kept) from an all-255 mask
+    full = torch.full((h, w), 255, dtype=torch.uint16, device=dev)
+    wide = _np(remap_depth(full, undistort_map(d, 0.5), (w, h)))
+    assert (wide == 0).any() and (wide[h // 2, w // 2] == 255) and set(np.unique(wide)) == {0, 255}
+
+
+# ---------------------------------------------------------------------------- 6. eval
+def _cloud_splats(dev, n=4000, seed=2):
+    from brush_amd import Splats
+
+    s = Splats.from_random_config(n, 1, (np.full(3, -0.8), np.full(3, 0.8)), np.random.default_rng(seed), dev)
+    import torch
+
+    with torch.no_grad():
+        s.log_scales.fill_(math.log(0.08))
+        s.raw_opacity.fill_(math.log(0.6 / 0.4))
+    return s
+
+
+@pytest.fixture(scope="module")
+def nerf_scene(tmp_path_factory):
+    """A NeRF-synthetic tree at 64x48: 4 val views, RGB and RGBA in turn; train frame 1 has a mask_path."""
+    root = str(tmp_path_factory.mktemp("compose_nerf"))
+    E.write_nerf(root, 64, 48, n_train=2, n_val=4)
+    _, _, mask, _ = R.case(64, 48, 3, np.uint8, "random", 5)
+    os.makedirs(os.path.join(root, "masks"))
+    with open(os.path.join(root, "masks", "t1.png"), "wb") as f:
+        f.write(E.png_bytes(mask))
+    path = os.path.join(root, "transforms_train.json")
+    with open(path) as f:
+        scene = json.load(f)
+    scene["frames"][1]["mask_path"] = "masks/t1.png"
+    with open(path, "w") as f:
+        json.dump(scene, f)
+    return root
+
+
+def test_eval_over_white_and_with_masks(dev, deterministic, nerf_scene):
+    import torch
+
+    from brush_amd import dataset as D
+    from brush_amd import eval_metrics, eval_stats
+    from brush_amd.pyramid import downscaled_size
+
+    data = D.read_nerf_synthetic(nerf_scene)
+    views = data.eval.views
+    assert sorted({v.image.shape[2] for v in views}) == [3, 4]
+    splats = _cloud_splats(dev)
+    w, h = 64, 48
+
+    def restated(v, bg, mask):
+        with torch.no_grad():
+            pred, _ = splats.render(v.camera, (w, h), False)
+        out, target = R.forward32(_np(pred), v.image, bg, mask)
+        return out, _np(eval_metrics(_up(out, dev), _up(target, dev)))
+
+    plain = eval_stats(splats, data.eval)
+    white = eval_stats(splats, data.eval, background="white")
+    assert [s.valid_fraction for s in white.samples] == [1.0] * 4
+    for s, p, v in zip(white.samples, plain.samples, views):
+        out, m = restated(v, (1.0, 1.0, 1.0), None)
+        assert np.float32(s.psnr).view(np.uint32) == m[1].view(np.uint32)
+        assert np.float32(s.ssim).view(np.uint32) == m[2].view(np.uint32)
+        assert np.array_equal(_bits(s.rendered), _bits(out[..., :3]))
+        assert s.psnr != p.psnr
+    # masks: view 0 (RGB) and view 1 (RGBA) get one, view 2 an all-zero one, view 3 none
+    masks = [R.case(w, h, 3, np.uint8, "random", 30)[2], R.case(w, h, 3, np.uint8, "random", 31)[2],
+             np.zeros((h, w), np.uint8), None]
+    scene = D.Scene([dataclasses.replace(v, mask=m) for v, m in zip(views, masks)])
+    for bg_name, bg in ((None, None), ("white", (1.0, 1.0, 1.0))):
+        stats = eval_stats(splats, scene, background=bg_name)
+        for s, p, v, m in zip(stats.samples, (plain if bg is None else white).samples, views, masks):
+            if m is None:
+                assert s.valid_fraction == 1.0 and s.psnr == p.psnr and s.ssim == p.ssim
+                continue
+            f = float(np.count_nonzero(m)) / float(w * h)
+            assert s.valid_fraction == f                                     # exact
+            _, met = restated(v, bg, m)
+            if f == 0.0:
+                assert math.isnan(s.psnr)
+            else:
+                assert s.psnr == 10.0 * math.log10(f / float(met[0]))        # PSNR over the kept pixels
+                assert s.psnr < 10.0 * math.log10(1.0 / float(met[0]))
+            assert np.float32(s.ssim).view(np.uint32) == met[2].view(np.uint32)  # the masked images as they are
+    # use_masks=False and no background: today's call
+    off = eval_stats(splats, scene, use_masks=False)
+    assert [(s.psnr, s.ssim, s.valid_fraction) for s in off.samples] == [(p.psnr, p.ssim, 1.0) for p in plain.samples]
+    # a mask follows `downscale` through the nearest resize
+    half = eval_stats(splats, scene, downscale=2)
+    ow, oh = downscaled_size(w, h, 2)
+    assert half.samples[0].valid_fraction == np.count_nonzero(D.resize_nearest(masks[0], (oh, ow))) / float(ow * oh)
+    with pytest.raises(ValueError, match="random"):
+        eval_stats(splats, scene, background="random")
+
+
+def test_command_lines_accept_the_flags(dev, nerf_scene, tmp_path):
+    from brush_amd import dataset as D
+    from brush_amd import eval_stats
+
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    splats = _cloud_splats(dev)
+    ply, out = tmp_path / "cloud.ply", tmp_path / "eval.json"
+    ply.write_bytes(splats.to_ply())
+    r = subprocess.run([sys.executable, "-m", "brush_amd.eval", str(ply), nerf_scene, "--background", "white",
+                        "--no-masks", "--json", str(out)], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    res = json.loads(out.read_text())
+    from brush_amd import Splats
+
+    stats = eval_stats(Splats.from_ply(str(ply), dev), D.read_nerf_synthetic(nerf_scene).eval, background="white")
+    assert len(res["views"]) == 4
+    for v, s in zip(res["views"], stats.samples):
+        assert abs(v["psnr"] - s.psnr) <= 1e-3 and abs(v["ssim"] - s.ssim) <= 1e-5   # atomics: the render's last bits
+    log = tmp_path / "log.json"
+    r = subprocess.run([sys.executable, "-m", "brush_amd.train_loop", nerf_scene, "--steps", "12", "--init-count",
+                        "500", "--background", "random", "--eval-every", "12", "--json", str(log)], cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    res = json.loads(log.read_text())
+    assert res["background"] == "random" and res["masked_views"] == 1 and len(res["losses"]) == 12
+    assert [e["step"] for e in res["evals"]] == [0, 12] and all(np.isfinite(res["losses"]))
+    r = subprocess.run([sys.executable, "-m", "brush_amd.eval", str(ply), nerf_scene, "--background", "random"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 2 and "random" in r.stderr   # refused by the parser, before any GPU work
+
+
+# ---------------------------------------------------------------------------- 7. end to end
+def _write_rgba_scene(root, dev, w=64, h=64, n_train=16, n_val=4):
+    """test_gpu_train_loop._write_scene's cloud and cameras as an RGBA object capture: straight colour, alpha kept."""
+    import torch
+
+    from tests import test_gpu_exposure as TX
+    from tests import test_gpu_train_loop as TL
+
+    known = TX._known_cloud(dev)
+    fovx = 0.6911112070083618
+    for split, n, off in (("train", n_train, 0.1), ("val", n_val, 0.5)):
+        os.makedirs(os.path.join(root, split), exist_ok=True)
+        frames = []
+        for i, (c2w, cam) in enumerate(TL._ring_cameras(n, w, h, 4.0, 1.0, off)):
+            with torch.no_grad():
+                pred, _ = known.render(cam, (w, h), False)
+            p = pred.cpu().numpy().astype(np.float64)
+            a = np.clip(p[..., 3:4], 0.0, 1.0)
+            straight = np.where(a > 0, p[..., :3] / np.maximum(a, 1e-12), 0.0)
+            img = np.clip(np.round(np.concatenate([straight, a], 2) * 255.0), 0, 255).astype(np.uint8)
+            with open(os.path.join(root, split, f"r_{i}.png"), "wb") as f:
+                f.write(E.png_bytes(img))
+            frames.append({"file_path": f"./{split}/r_{i}", "rotation": 0.0, "transform_matrix": c2w.tolist()})
+        with open(os.path.join(root, f"transforms_{split}.json"), "w") as f:
+            json.dump({"camera_angle_x": fovx, "frames": frames}, f)
+    return root
+
+
+def test_rgba_object_trains_over_a_random_background(dev, tmp_path):
+    """300 steps over a random background from random splats; scored over white before and after.
+    Measured on the MI355X: 12.852 -> 18.317 dB, a gain of 5.465 dB (E2E_GAIN_MEASURED_DB; 11 042 splats, 18.296 dB over
+    black); a second run gave 12.852 -> 18.552 dB (the default render mode's float atomics make runs differ in the last
+    bits).  The gate is half of the first figure, 2.73 dB (profiles/compose_margins.json: e2e)."""
+    from brush_amd import TrainConfig, eval_stats
+    from brush_amd.train_loop import TrainLoop, load_dataset
+
+    data, _ = load_dataset(_write_rgba_scene(str(tmp_path / "rgba"), dev))
+    assert all(v.image.shape[2] == 4 for v in data.train.views + data.eval.views)
+    loop = TrainLoop(data, TrainConfig(warmup_steps=50, refine_every=50, background="random"), steps=E2E_STEPS,
+                     init_count=2000, sh_degree=3, seed=5)
+    before = eval_stats(loop.splats, data.eval, background="white").mean_psnr()
+    for _ in range(E2E_STEPS):
+        loop.step()
+    row, _ = loop.evaluate()       # "random" evaluates over black
+    splats, log = loop.finish()
+    after = eval_stats(splats, data.eval, background="white").mean_psnr()
+    gain = after - before
+    print(f"compose e2e: white-background psnr {before:.3f} -> {after:.3f} dB (gain {gain:.3f}); over black "
+          f"{row.psnr:.3f} dB; {log.num_splats} splats; last-50 loss {float(np.mean(log.losses[-50:])):.6f}")
+    MARGINS["e2e"] = dict(steps=E2E_STEPS, psnr_white_before=before, psnr_white_after=after, gain_db=gain,
+                          psnr_black_after=row.psnr, splats=log.num_splats, gain_measured_db=E2E_GAIN_MEASURED_DB,
+                          threshold_db=0.5 * E2E_GAIN_MEASURED_DB)
+    assert log.background == "random" and log.masked_views == 0 and np.isfinite(log.losses).all()
+    assert after > before
+    assert gain >= 0.5 * E2E_GAIN_MEASURED_DB

@@ -33,6 +33,10 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 replay of the compositing walk, and pruning by it (brush_amd/contribution.py; build
                                 extension, RadSplat and LightGaussian are the models; also `python -m brush_amd.prune`,
                                 Splats.select, TrainConfig.contribution_prune_at)
+  filter3d_rates / apply_filter3d / Splats.bake_filter3d  <- the 3D smoothing filter of Mip-Splatting: per-splat
+                                filter lengths from the training views' sampling rates, and the map of log-scales and
+                                raw opacity that applies them (brush_amd/filter3d.py; build extension;
+                                TrainConfig.filter3d, `python -m brush_amd.train_loop --filter3d`)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -53,6 +57,7 @@ from . import dataset  # noqa: F401
 from .depth_loss import depth_loss, depth_loss_into  # noqa: F401
 from .compose import as_background, compose, compose_backward, compose_forward  # noqa: F401  (as depth_loss above)
 from .pyramid import area_resize, downscaled_size, nearest_resize  # noqa: F401
+from .filter3d import apply_filter3d, filter3d_rates  # noqa: F401
 from .undistort import (Distortion, fit_scale, undistort_dataset, undistort_depth, undistort_image,  # noqa: F401
                         undistorted_camera)
 

@@ -111,6 +111,16 @@ class BrushUndistort(C.Structure):
                                                "k4", "k5", "k6", "p1", "p2")]
 
 
+class BrushFilterView(C.Structure):
+    """One pinhole view of brush_filter3d_rates (include/brush_hip.h: BrushFilterView), 96 bytes."""
+    _fields_ = [
+        ("viewmat", C.c_float * 16),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("padding", C.c_uint32 * 2),
+    ]
+
+
 class BrushError(RuntimeError):
     pass
 
@@ -211,6 +221,11 @@ _SYMBOLS = [
      [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.POINTER(BrushUndistort), _P]),
     ("brush_render_contributions", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P]),
+    ("brush_filter3d_view_chunk", C.c_uint32, []),
+    ("brush_filter3d_rates", C.c_int,
+     [_P, C.c_uint32, _P, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),
+    ("brush_filter3d_apply", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P]),
+    ("brush_filter3d_backward", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

@@ -282,6 +282,46 @@ def write_depth_maps(splats, views, out_dir: str):
     return paths
 
 
+def zoomed_camera(camera, img_size, zoom: float):
+    """`camera` with `zoom` times its focal lengths on an image of the same size and the same principal point: the
+    central 1 / zoom of the view, magnified (a zoom-in no training view sampled, which is what the 3D smoothing filter
+    of brush_amd/filter3d.py is for)."""
+    from .camera import Camera, focal_to_fov
+
+    w, h = int(img_size[0]), int(img_size[1])
+    fx, fy = camera.focal((w, h))
+    return Camera(camera.position, camera.rotation, focal_to_fov(float(fx) * zoom, w), focal_to_fov(float(fy) * zoom, h),
+                  camera.center_uv)
+
+
+def write_zoomed_renders(splats, views, zoom: float, out_dir: str, antialiased: bool = False, background=None):
+    """For each view: <stem>_zoom<zoom>.png, the view rendered through zoomed_camera at its own size, composed over
+    `background` (an (r, g, b) tuple, "white" or "black"; None: black) and written as 8-bit RGB.  There is no ground
+    truth for a zoom-in, so nothing is scored: the images are for inspection.  Returns the written paths."""
+    import os
+
+    from PIL import Image
+
+    from .compose import check_background
+
+    bg = check_background(background)
+    rgb = {None: (0.0, 0.0, 0.0), "black": (0.0, 0.0, 0.0), "white": (1.0, 1.0, 1.0)}.get(bg, bg)
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    with torch.no_grad():
+        for v in views:
+            h, w = int(v.image.shape[0]), int(v.image.shape[1])
+            img, _ = splats.render(zoomed_camera(v.camera, (w, h), zoom), (w, h), antialiased=antialiased)
+            colour = torch.tensor(rgb, dtype=torch.float32, device=img.device)
+            out = img[..., :3] + (1.0 - img[..., 3:4]) * colour
+            u8 = torch.clamp(torch.round(out * 255.0), 0, 255).to(torch.uint8).cpu().numpy()
+            stem = os.path.splitext(os.path.basename(v.name))[0]
+            path = os.path.join(out_dir, f"{stem}_zoom{zoom:g}.png")
+            Image.fromarray(u8).save(path)
+            paths.append(path)
+    return paths
+
+
 # ---------------------------------------------------------------------------- command line
 def detect_format(dataset: str) -> str:
     """'nerf' when the directory / zip holds a transforms_*.json, else 'colmap'."""
@@ -339,6 +379,11 @@ def parser():
                         "over it first (white: the protocol of the NeRF-synthetic numbers in the literature)")
     p.add_argument("--no-masks", action="store_true",
                    help="ignore the dataset's loss masks (nerfstudio's mask_path, COLMAP's masks/<image name>.png)")
+    p.add_argument("--zoom", type=float, default=None, metavar="Z",
+                   help="with --image-dir: also render every scored view at Z times its focal length (same size and "
+                        "principal point) and write the images for inspection; a zoom-in has no ground truth, so "
+                        "nothing is scored (metrics across scales: --downscale)")
+    p.add_argument("--image-dir", default=None, metavar="DIR", help="--zoom: where the zoomed renders go")
     p.add_argument("--no-undistort", action="store_true",
                    help="score views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
                         "loaded, as if they were pinhole, instead of undistorting them first")
@@ -379,6 +424,10 @@ def main(argv=None) -> int:
         except ValueError as e:
             p.error(str(e))
     compose_args = {"background": background, "use_masks": not args.no_masks}
+    if (args.zoom is None) != (args.image_dir is None):
+        p.error("--zoom and --image-dir go together")
+    if args.zoom is not None and not (args.zoom > 0 and args.zoom < float("inf")):
+        p.error("--zoom must be a positive factor")
 
     data = _load_dataset(args)  # before any GPU work
     if data.eval is None or not data.eval.views:
@@ -420,6 +469,10 @@ def main(argv=None) -> int:
                                "mean_psnr": st.mean_psnr(), "mean_ssim": st.mean_ssim()})
     if args.depth_dir:
         write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir)
+    if args.zoom is not None:
+        for path in write_zoomed_renders(splats, [s.view for s in stats.samples], args.zoom, args.image_dir,
+                                         antialiased=args.antialiased, background=background):
+            print(f"zoom {args.zoom:g}\t{path}")
     depth_rows = None
     if args.depth_metrics:
         depth_rows = eval_depth(splats, data.eval, mode=args.depth_mode, antialiased=args.antialiased)

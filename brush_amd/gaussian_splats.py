@@ -130,6 +130,18 @@ class Splats(torch.nn.Module):
         return Splats(self.means.detach()[keep], self.sh_coeffs.detach()[keep], self.rotation.detach()[keep],
                       self.raw_opacity.detach()[keep], self.log_scales.detach()[keep])
 
+    @torch.no_grad()
+    def bake_filter3d(self, filter) -> "Splats":
+        """A new Splats holding the effective parameters under the 3D smoothing filter `filter` (float32 [N] lengths on
+        this one's device, filter3d.filter3d_rates): log-scales and raw opacities through filter3d.apply_filter3d, the
+        rest copied.  Mip-Splatting's "fused" export: a renderer or viewer that knows nothing of the filter shows the
+        result correctly.  Pending SH optimizer steps are applied first (sync); the new object belongs to no trainer."""
+        from .filter3d import apply_filter3d
+
+        self.sync()
+        log_scales, raw_opacity = apply_filter3d(self.log_scales.detach(), self.raw_opacity.detach(), filter)
+        return Splats(self.means.detach(), self.sh_coeffs.detach(), self.rotation.detach(), raw_opacity, log_scales)
+
     def render(self, camera: Camera, img_size, render_u32_buffer: bool = False, max_intersects=None,
                antialiased: bool = False):
         """gaussian_splats.rs:167-188; `antialiased`: render.render_splats."""

@@ -129,6 +129,31 @@ class TrainConfig:
     # optimizer path.  DESIGN §8 row 16.
     background: object = None
     use_masks: bool = True
+    # Build extension: the 3D smoothing filter of Mip-Splatting (brush_amd/filter3d.py), the world-space half of what
+    # `antialiased` is the screen-space half of.  Every splat carries a filter length (SplatTrainer.set_filter3d; the
+    # training loop computes it from the training views, brush_filter3d_rates, before the first step, after every step
+    # that changed the splat count and every filter3d_every steps); a step renders and backpropagates through the
+    # effective log-scales and opacities (brush_filter3d_apply / _backward around the existing forward and backward) and
+    # steps the raw parameters, on the separate-call optimizer path.  filter3d_variance: the filter's variance in
+    # squared sampling intervals (0.2 is Mip-Splatting's value: a hyper-parameter default, not a measured number).
+    # Refinement, the opacity reset and the prune thresholds keep reading the RAW parameters, as Mip-Splatting's
+    # densification does.  Combines with antialiased, background / masks, exposure, pose and depth; single-view
+    # training, not with strategy "mcmc".  False (the default) is the step without the option, launch for launch.
+    # DESIGN §8 row 17.
+    filter3d: bool = False
+    filter3d_every: int = 100
+    filter3d_variance: float = 0.2
+
+    def check_filter3d(self):
+        """A ValueError naming what is wrong with the filter3d fields or their combination with the strategy."""
+        e, v = self.filter3d_every, self.filter3d_variance
+        if isinstance(e, bool) or not isinstance(e, int) or e < 1:
+            raise ValueError(f"TrainConfig.filter3d_every must be an integer >= 1, got {e!r}")
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f"TrainConfig.filter3d_variance must be finite and >= 0, got {v!r}")
+        if self.filter3d and self.strategy == "mcmc":
+            raise ValueError("TrainConfig.filter3d cannot be combined with strategy='mcmc': relocation and the "
+                             "regularisers act on the raw scales and opacities")
 
     def check_contribution_prune(self) -> Tuple[int, ...]:
         """contribution_prune_at as a tuple of ints, or a ValueError naming what is wrong with the two fields."""
@@ -239,6 +264,8 @@ def l1_ssim_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_weight: float, windo
 
 
 class SplatTrainer:
+    filter3d: Optional[torch.Tensor] = None  # the 3D filter lengths [N] of set_filter3d, or None
+
     def __init__(self, splats: Splats, config: TrainConfig | None = None):
         self.config = config or TrainConfig()
         if self.config.strategy not in ("default", "mcmc"):
@@ -249,6 +276,8 @@ class SplatTrainer:
             raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
         self.config.check_downscale_schedule()
         self.config.check_contribution_prune()
+        self.config.check_filter3d()
+        self.filter3d = None
         from .compose import check_background
         check_background(self.config.background)
         self._bg_rng, self._bg_fixed = None, {}  # "random"'s device generator; the fixed colours' device tensors
@@ -281,6 +310,20 @@ class SplatTrainer:
         kernel): such writes do not bump the tensor version the cache key watches.  In-place ops on the
         Parameter itself, replacing the Parameter and refine_splats are detected without it."""
         self._norm_rot, self._norm_rot_key, self._norm_rot_owner = None, None, None
+
+    def set_filter3d(self, filter: Optional[torch.Tensor]):
+        """Sets (None: clears) the 3D smoothing filter the next steps train under: a contiguous float32 [N] device
+        tensor of filter lengths, one per splat (filter3d.filter3d_rates), kept by reference.  With a filter set a step
+        takes the separate-call path whatever `fused_backward` says.  The filter is not resized when refinement changes
+        the count: the next step then refuses to run until a filter of the new length is set."""
+        if filter is not None:
+            if self.config.strategy == "mcmc":
+                raise ValueError("the 3D filter cannot be combined with strategy='mcmc'")
+            if not isinstance(filter, torch.Tensor) or filter.dim() != 1 or filter.dtype != torch.float32 \
+                    or not filter.is_cuda or not filter.is_contiguous():
+                raise ValueError("the 3D filter must be a contiguous float32 [N] tensor on the GPU")
+            filter = filter.detach()
+        self.filter3d = filter
 
     LAZY_TABLE_ROWS = 2048
 
@@ -482,9 +525,20 @@ class SplatTrainer:
         form) and the target go through brush_compose_forward first, and the loss's gradient through
         brush_compose_backward, in place, before the exposure backward and every render backward path.  With a
         background the loss compares opaque RGB.  The depth term is not masked here: scene_loader zeroes the depth maps
-        under the masks at load.  On every optimizer path; with both None the step is the one without the option."""
+        under the masks at load.  On every optimizer path; with both None the step is the one without the option.
+        With a 3D filter set (set_filter3d; TrainConfig.filter3d demands one) the step takes the separate-call path
+        whatever `fused_backward` says: brush_filter3d_apply, the forward and the backward on the effective log-scales
+        and opacities, brush_filter3d_backward on the dense gradients, then the refinement statistics and
+        brush_adam_step on the raw parameters as without it.  A filter whose length is not the current splat count is
+        refused.  Not with `exchange` / `grad_sync`."""
         c = self.config
         use_mcmc = c.strategy == "mcmc"
+        filt = self.filter3d
+        if c.filter3d and filt is None:
+            raise ValueError("TrainConfig.filter3d is set but the trainer has no filter: call set_filter3d first "
+                             "(train_loop.TrainLoop does)")
+        if filt is not None and (exchange is not None or grad_sync is not None):
+            raise ValueError("the 3D filter is single-view: it cannot be combined with exchange / grad_sync")
         if gt_depth is not None and (exchange is not None or grad_sync is not None):
             raise ValueError("depth supervision is single-view: it cannot be combined with exchange / grad_sync")
         depth_w = self._depth_weight() if gt_depth is not None else 0.0
@@ -513,6 +567,12 @@ class SplatTrainer:
         sh, raw_opac = splats.sh_coeffs.detach(), splats.raw_opacity.detach()
         for t in (means, log_scales, quats, sh, raw_opac):
             assert t.is_contiguous() and t.dtype == torch.float32
+        if filt is not None:
+            from . import filter3d as F3
+            try:
+                F3.check_filter(filt, n, means.device)
+            except ValueError as e:
+                raise ValueError(f"stale 3D filter: {e}; set one for the current splats (set_filter3d)") from None
         l = _lib.lib()
         stream = _lib.current_stream(means.device)
         # Splats::render feeds rotation / |rotation| (gaussian_splats.rs:174-175).  The fused backward of the
@@ -527,7 +587,8 @@ class SplatTrainer:
         self.invalidate_cached_rotation()
         # the optimizer runs inside a kernel that sees which splats the step touches: the single-view fused backward, or
         # the data-parallel reduction of the views' records (both take BrushAdamConfig.lazy_sh)
-        fused = grad_sync is None and (exchange is not None or self.fused_backward) and not use_mcmc and not use_depth
+        fused = grad_sync is None and (exchange is not None or self.fused_backward) and not use_mcmc and not use_depth \
+            and filt is None
         lazy = self._lazy_state(splats, n, ncoef) if fused else None
         if lazy is None:
             self.sync(splats)  # this step reads / steps every SH block: nothing may stay pending
@@ -538,7 +599,12 @@ class SplatTrainer:
             viewmat = poses.viewmat(view_index, camera).numpy()
             pose = R.pose_buffers(n, means.device)
         depth_bufs = R._depth_buffers(n, (w, h), means.device) if use_depth else None  # (depth map, compact depth)
-        pred, aux, u = R._forward_impl(camera, (w, h), means, log_scales, norm_rot, sh, raw_opac, False, None,
+        # the renderer sees the effective log-scales and opacities; everything else keeps reading the raw ones
+        eff_scales, eff_opac = log_scales, raw_opac
+        if filt is not None:
+            with torch.cuda.device(means.device):
+                eff_scales, eff_opac = F3.apply_into(log_scales, raw_opac, filt, n, stream)
+        pred, aux, u = R._forward_impl(camera, (w, h), means, eff_scales, norm_rot, sh, eff_opac, False, None,
                                        lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat, depth=depth_bufs)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
@@ -613,8 +679,10 @@ class SplatTrainer:
                 self._norm_rot, self._norm_rot_key = next_rot, (quats.data_ptr(), n, splats.rotation._version)
                 self._norm_rot_owner = splats.rotation
             else:
-                grads, block = R._backward_impl(u, aux, means, log_scales, norm_rot, raw_opac, ncoef, pred, v_pred,
+                grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
                                                 depth=depth_grad, pose=pose)
+                if filt is not None:  # gradients at the effective parameters -> at the raw ones, in place
+                    F3.backward_into(log_scales, raw_opac, filt, n, grads["v_scales"], grads["v_opac"], stream)
                 if grad_sync is not None:  # view-sharded data parallelism: sum the per-view gradients
                     grad_sync(block, aux)
                 if want_stats:

@@ -18,7 +18,12 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
         [--downscale-schedule STEP:FACTOR,...] [--num-downscales K] [--resolution-schedule S]
         [--contribution-prune-at STEP,...] [--contribution-prune-min 0.01]
-        [--background white|black|random|R,G,B] [--no-masks]
+        [--background white|black|random|R,G,B] [--no-masks] [--filter3d] [--filter3d-every 100]
+
+--filter3d trains under Mip-Splatting's 3D smoothing filter (TrainConfig.filter3d, brush_amd/filter3d.py): every splat
+is low-passed at the highest rate any training view sampled it, recomputed every --filter3d-every steps and whenever the
+splat count changed.  Evals, contribution prunes and --export then work on the baked splats (Splats.bake_filter3d), which
+any viewer shows correctly; the JSON log records the mode.
 
 --background composes the render and the (straight-alpha) target over a colour in front of the loss and in the evals
 (TrainConfig.background, brush_amd/compose.py); random draws a colour per step on the device and evaluates over black.
@@ -96,6 +101,8 @@ class TrainLog:
     prunes: List[Tuple[int, int, int]] = field(default_factory=list)  # (step, splats before, after): contribution prunes
     background: object = None                     # TrainConfig.background as configured
     masked_views: int = 0                         # training views whose loss mask the run used
+    filter3d: bool = False                        # TrainConfig.filter3d: trained under the 3D smoothing filter
+    filter3d_refreshes: List[int] = field(default_factory=list)  # the steps in front of which the filter was recomputed
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
@@ -104,7 +111,8 @@ class TrainLog:
                 "downscales": [[int(s), int(f)] for s, f in self.downscales],
                 "prunes": [[int(s), int(b), int(a)] for s, b, a in self.prunes],
                 "background": list(self.background) if isinstance(self.background, tuple) else self.background,
-                "masked_views": int(self.masked_views),
+                "masked_views": int(self.masked_views), "filter3d": bool(self.filter3d),
+                "filter3d_refreshes": [int(s) for s in self.filter3d_refreshes],
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -154,6 +162,15 @@ def check_contribution_prune(config: TrainConfig, exchange=None) -> Tuple[int, .
     return steps
 
 
+def check_filter3d(config: TrainConfig, exchange=None):
+    """A ValueError when the run cannot train under the 3D filter: bad TrainConfig.filter3d fields, strategy "mcmc", or
+    a multi-rank `exchange` (a dist.ViewExchange of more than one rank: the filter's step is single-view)."""
+    config.check_filter3d()
+    if config.filter3d and exchange is not None and int(getattr(exchange, "world", 1)) > 1:
+        raise ValueError("TrainConfig.filter3d cannot be combined with a multi-rank exchange: the 3D filter is "
+                         "single-GPU")
+
+
 class TrainLoop:
     """The state of one run: splats, trainer, resident views and the device loss log.  `train_scene` drives it; tests
     and tools may call step() / evaluate() themselves (from one thread, on the current stream)."""
@@ -165,6 +182,7 @@ class TrainLoop:
         if steps < 0:
             raise ValueError(f"steps must be >= 0, got {steps}")
         self._prune_at = frozenset(check_contribution_prune(config or TrainConfig(), exchange))
+        check_filter3d(config or TrainConfig(), exchange)
         self.dataset = dataset
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         # the mean learning rate decays over the run; the refinement RNG takes the run's seed (train_loop.rs:44-46)
@@ -198,20 +216,58 @@ class TrainLoop:
         # background colour and loss masks: the drawn view's resident mask and the configured colour go with the step
         self._masks = any(m is not None for m in self.loader.masks)
         self._compose = self.config.background is not None or self._masks
+        # 3D smoothing filter: the training views' records go to the device once, so that a refresh is launches only.
+        # Full-size intrinsics and the dataset's poses, whatever level the downscale schedule trains at and whatever
+        # pose_opt has moved: the filter bounds what the stored images can resolve.
+        self._filter_views = None
+        self._filter_stale, self._filter_at = True, -1  # (the step index the filter was last computed in front of)
+        if self.config.filter3d:
+            from .filter3d import view_records
+
+            self._filter_views = torch.from_numpy(view_records(dataset.train.views)).to(self.device)
         self.losses = torch.zeros(self.steps, dtype=torch.float32, device=self.device)
         self.done = 0
         self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes,
                             background=self.config.background,
-                            masked_views=sum(m is not None for m in self.loader.masks))
+                            masked_views=sum(m is not None for m in self.loader.masks),
+                            filter3d=bool(self.config.filter3d))
         self._t0 = time.perf_counter()
         self._eval_seconds = 0.0
         self._last = (0, 0.0)  # (step, training seconds) of the previous eval row
 
+    def refresh_filter3d(self):
+        """Recomputes the 3D filter lengths of the current splats from the dataset's training views (full-size
+        intrinsics, the dataset's poses: neither the downscale level nor pose_opt's corrections enter) and hands them to
+        the trainer.  Launches only: no upload, no read-back, no synchronisation."""
+        from .filter3d import filter3d_rates
+
+        self.trainer.set_filter3d(filter3d_rates(self.splats.means.detach(), self._filter_views,
+                                                 variance=self.config.filter3d_variance))
+        self._filter_stale, self._filter_at = False, self.done
+        self.log.filter3d_refreshes.append(self.done)
+
+    def baked_splats(self) -> Splats:
+        """What a renderer should be given: with TrainConfig.filter3d the splats with the current filter baked in
+        (Splats.bake_filter3d, a copy; the filter is refreshed first when the count changed since), else the splats
+        themselves."""
+        if not self.config.filter3d:
+            return self.splats
+        if self._filter_stale or self.trainer.filter3d is None \
+                or int(self.trainer.filter3d.shape[0]) != self.splats.num_splats():
+            self.refresh_filter3d()
+        return self.splats.bake_filter3d(self.trainer.filter3d)
+
     def step(self):
         """One training iteration on a random view, at the level TrainConfig.downscale_at gives for this step; its loss
-        lands in the device log."""
+        lands in the device log.  With TrainConfig.filter3d the 3D filter is recomputed in front of the step (from the
+        training views at full size and at the dataset's poses, refresh_filter3d) before the first step, after any step
+        that changed the splat count (refinement, contribution prune) and otherwise when the step index is a multiple
+        of filter3d_every; no step synchronises because of the filter."""
         if self.done >= self.steps:
             raise RuntimeError(f"the run has {self.steps} steps, all done")
+        if self.config.filter3d and (self._filter_stale or (self.done % self.config.filter3d_every == 0
+                                                            and self._filter_at != self.done)):
+            self.refresh_filter3d()
         factor = self.config.downscale_at(self.done)
         if factor != self.loader.downscale:  # a level switch: launches only (SceneLoader.set_downscale)
             self.loader.set_downscale(factor)
@@ -230,6 +286,8 @@ class TrainLoop:
                               depth_scale=getattr(view, "depth_scale", 1.0),
                               depth_offset=getattr(view, "depth_offset", 0.0),
                               background=self.config.background, gt_mask=self.loader.mask(i) if self._masks else None)
+        if self.trainer.last_refine is not None:
+            self._filter_stale = True  # refinement rebuilt the splats: the filter belongs to the old rows
         if self.done in self._prune_at:
             self.prune_by_contribution()
         self.done += 1
@@ -238,15 +296,18 @@ class TrainLoop:
         """Measures every splat's contribution over all training views, at the current downscale factor and in the
         config's antialiased mode, keeps the splats prune_mask(min_max=contribution_prune_min) leaves, rebuilds the
         parameters and resets the optimizer state and refinement statistics (SplatTrainer.keep_splats).  Appends
-        (step, before, after) to the log's `prunes` and returns (before, after).  Synchronises (one read-back)."""
+        (step, before, after) to the log's `prunes` and returns (before, after).  Synchronises (one read-back).  With
+        TrainConfig.filter3d the contributions are those of the baked splats (what the renderer draws); the rows kept
+        are taken from the raw ones."""
         from .contribution import prune_mask, splat_contributions
 
         self.trainer.sync(self.splats)
         before = self.splats.num_splats()
-        c = splat_contributions(self.splats, self.dataset.train.views, antialiased=self.config.antialiased,
+        c = splat_contributions(self.baked_splats(), self.dataset.train.views, antialiased=self.config.antialiased,
                                 downscale=self.loader.downscale)
         keep = torch.nonzero(~prune_mask(c, min_max=self.config.contribution_prune_min)).squeeze(1)
         after = self.trainer.keep_splats(self.splats, keep) if int(keep.numel()) < before else before
+        self._filter_stale = self._filter_stale or after != before
         self.log.prunes.append((self.done, before, after))
         return before, after
 
@@ -263,7 +324,8 @@ class TrainLoop:
     def evaluate(self, eval_views: Optional[int] = None) -> Tuple[EvalRow, object]:
         """eval_stats on the dataset's eval views, between steps, on this thread and stream (its docstring's rule);
         appends and returns the EvalRow (and the EvalStats).  Always at the eval views' full size, whatever level the
-        downscale schedule has the training at: the rows of one run stay comparable."""
+        downscale schedule has the training at: the rows of one run stay comparable.  With TrainConfig.filter3d the
+        baked splats are evaluated."""
         from .eval import eval_stats
 
         if self.dataset.eval is None or not self.dataset.eval.views:
@@ -274,8 +336,8 @@ class TrainLoop:
         # evaluated in the mode the splats are trained in; a random training background evaluates over black
         # (with no background and no masked eval view eval_stats is the call without the options)
         bg = "black" if self.config.background == "random" else self.config.background
-        stats = eval_stats(self.splats, self.dataset.eval, eval_views, self.rng, antialiased=self.config.antialiased,
-                           background=bg, use_masks=self.config.use_masks)
+        stats = eval_stats(self.baked_splats(), self.dataset.eval, eval_views, self.rng,
+                           antialiased=self.config.antialiased, background=bg, use_masks=self.config.use_masks)
         loss = float(self.losses[self.done - 1].item()) if self.done > 0 else float("nan")
         dstep, dt = self.done - self._last[0], train_s - self._last[1]
         row = EvalRow(self.done, stats.mean_psnr(), stats.mean_ssim(), self.splats.num_splats(),
@@ -287,7 +349,9 @@ class TrainLoop:
 
     def finish(self) -> Tuple[Splats, TrainLog]:
         """Applies the trainer's pending SH steps (the returned splats are current) and the pending pose updates, and
-        reads the loss log back."""
+        reads the loss log back.  With TrainConfig.filter3d the returned splats are the baked ones (Splats.bake_filter3d
+        under the current filter: what the evals rendered and what a viewer shows correctly); the raw parameters stay at
+        `loop.splats` and the filter at `loop.trainer.filter3d`."""
         self.trainer.sync(self.splats)
         self.log.pose_opt = self.poses is not None
         if self.poses is not None:
@@ -300,7 +364,7 @@ class TrainLoop:
         self.log.seconds = time.perf_counter() - self._t0
         self.log.train_seconds = self.log.seconds - self._eval_seconds
         self.log.num_splats = self.splats.num_splats()
-        return self.splats, self.log
+        return self.baked_splats(), self.log
 
 
 def train_scene(dataset: Dataset, config: Optional[TrainConfig] = None, *, steps: int, init=None,
@@ -437,6 +501,10 @@ def parser():
                         "random draws a colour per step (and evaluates over black)")
     p.add_argument("--no-masks", action="store_true",
                    help="ignore the dataset's loss masks (nerfstudio's mask_path, COLMAP's masks/<image name>.png)")
+    p.add_argument("--filter3d", action="store_true",
+                   help="train under Mip-Splatting's 3D smoothing filter; evals and --export use the baked splats")
+    p.add_argument("--filter3d-every", type=int, default=TrainConfig.filter3d_every, metavar="K",
+                   help="--filter3d: recompute the filter every K steps (and whenever the splat count changed)")
     p.add_argument("--no-undistort", action="store_true",
                    help="train on views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
                         "loaded, as if they were pinhole, instead of undistorting them first")
@@ -457,6 +525,7 @@ def main(argv=None) -> int:
                                              contribution_prune_min=args.contribution_prune_min))
         from .compose import parse_background
         background = None if args.background is None else parse_background(args.background)
+        check_filter3d(TrainConfig(strategy=args.strategy, filter3d=args.filter3d, filter3d_every=args.filter3d_every))
     except ValueError as e:
         p.error(str(e))
     if not os.path.exists(args.dataset):
@@ -507,7 +576,7 @@ def main(argv=None) -> int:
                          depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
                          downscale_schedule=schedule, contribution_prune_at=prune_at,
                          contribution_prune_min=args.contribution_prune_min, background=background,
-                         use_masks=not args.no_masks)
+                         use_masks=not args.no_masks, filter3d=args.filter3d, filter3d_every=args.filter3d_every)
     splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,

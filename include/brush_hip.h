@@ -696,6 +696,55 @@ int brush_render_contributions(const BrushUniforms *h_uniforms, const BrushAux *
                                uint32_t *max_bits /* [N] */, uint64_t *counts /* [N,3]: sum_q24, hits, stops */,
                                uint32_t *mismatch /* [1] or NULL */, uint32_t n, brush_stream_t stream);
 
+/* ---- 3D smoothing filter (build extension; Mip-Splatting, Yu et al. 2024, is the model) ------------------------- */
+/* The world-space half of Mip-Splatting: every splat is low-passed at the highest rate any training view sampled it.
+ * A splat carries a filter length f; the renderer sees the covariance Sigma + f^2 I and the opacity scaled by
+ * sqrt(det Sigma / det(Sigma + f^2 I)).  With Sigma = R diag(s^2) R^T that is a map of the log-scales and the raw opacity
+ * alone, so it sits in front of brush_render_forward and its transpose behind brush_render_backward; no other entry
+ * point knows of it.  All three entries take a stream, allocate nothing, never synchronise, use no atomics and no
+ * workspace and can be captured into a graph; n == 0 returns BRUSH_OK without touching the pointers; a NULL or
+ * misaligned (floats: 4 bytes, view records: 16) argument is BRUSH_ERR_INVALID_ARG, checked before any GPU call. */
+/* One pinhole view of brush_filter3d_rates, 96 bytes: the world-to-camera matrix column-major as BrushUniforms stores
+ * it, the intrinsics in pixels and the image size. */
+typedef struct BrushFilterView {
+    float viewmat[16];
+    float fx, fy, cx, cy;
+    uint32_t width, height;
+    uint32_t padding[2];
+} BrushFilterView;
+/* The number of view records brush_filter3d_rates stages in LDS at a time (tests straddle it). */
+uint32_t brush_filter3d_view_chunk(void);
+/* filter[i], the filter length of splat i from num_views views (a DEVICE array of records).  With p = W_v mean_i, rows
+ * summed left to right ((m0 x + m1 y) + m2 z) + t, the pair (i, v) is valid when
+ *   p.z > near_z,   -margin w <= (fx p.x) / p.z + cx <= (1 + margin) w,   -margin h <= (fy p.y) / p.z + cy <= (1 + margin) h
+ * (Mip-Splatting: near_z 0.2, margin 0.15); nu_i = max over valid v of fx_v / p.z and filter[i] = sqrt(variance) / nu_i
+ * (variance 0.2; the root is taken in float64 on the host and rounded once).  A splat no view sees takes the largest
+ * length among the seen ones; when none is seen, or num_views == 0 (views may then be NULL), every length is 0.  Max
+ * and min are float comparisons and nothing is summed across views: the result depends on neither the view order nor
+ * the launch shape.  near_z, margin and variance must be finite and >= 0.  Two launches: one lane per splat with the
+ * views staged through LDS, then one workgroup that finds the maximum and fills the unseen rows. */
+int brush_filter3d_rates(const float *means, uint32_t n, const BrushFilterView *views, uint32_t num_views, float near_z,
+                         float margin, float variance, float *filter, brush_stream_t stream);
+/* The forward map, per splat, with s2_k = exp(2 log_scale_k) and f = filter[i] (det_expf / det_logf throughout):
+ *   log_scales_out_k = 0.5 ln(s2_k + f^2)
+ *   c = prod_k sqrt(s2_k / (s2_k + f^2)),   E = exp(-o),   D = (1 - c) + E
+ *   raw_opacity_out = logit(sigmoid(o) c) = ln c - ln D
+ * A row with f * f == 0 is copied through bit for bit.  Where c underflows to 0 the result is floored at
+ * BRUSH_FILTER3D_MIN_RAW_OPACITY = ln 2^-126 (sigmoid of it is the smallest normal f32): a finite number, never NaN or
+ * -inf.  o is read clamped to [-87, 87], so every finite input with log_scale <= 44 gives finite outputs.  The outputs
+ * must not alias the inputs. */
+#define BRUSH_FILTER3D_MIN_RAW_OPACITY (-87.33654f)
+int brush_filter3d_apply(const float *log_scales, const float *raw_opacity, const float *filter, uint32_t n,
+                         float *log_scales_out, float *raw_opacity_out, brush_stream_t stream);
+/* The transpose, in place on the dense gradients brush_render_backward left for the effective parameters; log_scales
+ * and raw_opacity are the RAW parameters, from which c, E and D are recomputed by the forward's own function:
+ *   v_scales_k = v_scales_k * s2_k / (s2_k + f^2) + v_opac * (f^2 / (s2_k + f^2)) * (1 + E) / D     (1 / (1 - p) = (1 + E) / D)
+ *   v_opac     = v_opac * E / D                                                             ((1 - sigmoid(o)) / (1 - p))
+ * f carries no gradient.  Rows with f * f == 0 keep their bits.  Where the forward's floor acted the gradient is that of
+ * the unfloored map (finite: D >= exp(-87)), which keeps such a splat trainable. */
+int brush_filter3d_backward(const float *log_scales, const float *raw_opacity, const float *filter, uint32_t n,
+                            float *v_scales, float *v_opac, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

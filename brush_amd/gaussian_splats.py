@@ -14,14 +14,7 @@ from .render import render_splats, render_splats_depth, render_splats_pose
 class Splats(torch.nn.Module):
     def __init__(self, means, sh_coeffs, rotation, raw_opacity, log_scales):
         super().__init__()
-        self.means = torch.nn.Parameter(means.detach().clone())
-        self.sh_coeffs = torch.nn.Parameter(sh_coeffs.detach().clone())
-        self.rotation = torch.nn.Parameter(rotation.detach().clone())
-        self.raw_opacity = torch.nn.Parameter(raw_opacity.detach().clone())
-        self.log_scales = torch.nn.Parameter(log_scales.detach().clone())
-        # carries the screen-space xy gradient (gaussian_splats.rs:157)
-        self.xys_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device,
-                                     requires_grad=True)
+        self.replace_parameters(*(t.detach().clone() for t in (means, sh_coeffs, rotation, raw_opacity, log_scales)))
         # a SplatTrainer with deferred Adam of the SH block registers itself here; sync() applies what is pending
         self.lazy_sh_owner = None
 
@@ -109,6 +102,21 @@ class Splats(torch.nn.Module):
         return self.means.shape[0]
 
     @torch.no_grad()
+    def replace_parameters(self, means, sh_coeffs, rotation, raw_opacity, log_scales):
+        """Replaces the five parameters by the given tensors (the constructor's order; any row count, the same for
+        all): each is made contiguous and wrapped, not copied, in a fresh Parameter object, so that whoever keys a cache
+        on a Parameter's identity (the trainer's normalised rotation) sees the change; xys_dummy is sized to the new
+        count.  What the constructor (on copies of its arguments), refinement, pruning and the MCMC growth end in."""
+        self.means = torch.nn.Parameter(means.contiguous())
+        self.sh_coeffs = torch.nn.Parameter(sh_coeffs.contiguous())
+        self.rotation = torch.nn.Parameter(rotation.contiguous())
+        self.raw_opacity = torch.nn.Parameter(raw_opacity.contiguous())
+        self.log_scales = torch.nn.Parameter(log_scales.contiguous())
+        # carries the screen-space xy gradient (gaussian_splats.rs:157)
+        self.xys_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device,
+                                     requires_grad=True)
+
+    @torch.no_grad()
     def select(self, keep) -> "Splats":
         """A new Splats holding the rows `keep` of every parameter, on this one's device (any device).  `keep`: a boolean
         [N] tensor (the rows that are True, in order) or an integer index tensor (those rows, in its order).  Pending
@@ -142,21 +150,24 @@ class Splats(torch.nn.Module):
         log_scales, raw_opacity = apply_filter3d(self.log_scales.detach(), self.raw_opacity.detach(), filter)
         return Splats(self.means.detach(), self.sh_coeffs.detach(), self.rotation.detach(), raw_opacity, log_scales)
 
+    def _synced_norm_rotation(self) -> torch.Tensor:
+        """What every render starts with: sync(), then rotation / |rotation| (differentiable), which Splats::render
+        feeds the op instead of the stored rotation (gaussian_splats.rs:174-175)."""
+        self.sync()
+        rot = self.rotation
+        return rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
+
     def render(self, camera: Camera, img_size, render_u32_buffer: bool = False, max_intersects=None,
                antialiased: bool = False):
         """gaussian_splats.rs:167-188; `antialiased`: render.render_splats."""
-        self.sync()
-        rot = self.rotation
-        norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
+        norm_rot = self._synced_norm_rotation()
         return render_splats(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
                              self.sh_coeffs, self.raw_opacity, render_u32_buffer, max_intersects,
                              antialiased=antialiased)
 
     def render_depth(self, camera: Camera, img_size, max_intersects=None, antialiased: bool = False):
         """render() with the accumulated depth (render.render_splats_depth): (img [h,w,4], depth [h,w], aux)."""
-        self.sync()
-        rot = self.rotation
-        norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
+        norm_rot = self._synced_norm_rotation()
         return render_splats_depth(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
                                    self.sh_coeffs, self.raw_opacity, max_intersects, antialiased=antialiased)
 
@@ -164,9 +175,7 @@ class Splats(torch.nn.Module):
                     depth: bool = False):
         """render() / render_depth() through the explicit world-to-camera matrix `viewmat` (float32 [4,4] CPU tensor),
         differentiable with respect to it (render.render_splats_pose): (img, aux) or (img, depth, aux)."""
-        self.sync()
-        rot = self.rotation
-        norm_rot = rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
+        norm_rot = self._synced_norm_rotation()
         return render_splats_pose(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
                                   self.sh_coeffs, self.raw_opacity, viewmat, max_intersects=max_intersects,
                                   antialiased=antialiased, depth=depth)

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 
-PARAMS = ("means", "log_scales", "rotation", "raw_opacity", "sh_coeffs")  # the order of the moment segments
+PARAMS = ("means", "log_scales", "rotation", "raw_opacity", "sh_coeffs")  # Splats' names, in the moment segments' order
 
 
 @dataclass
@@ -99,8 +99,7 @@ def refine(trainer, splats) -> McmcRefineStats:
     """One MCMC refinement on the post-step parameters: relocate the dead splats, then grow towards the cap."""
     c = trainer.config
     dev = splats.means.device
-    p = {"means": splats.means.detach(), "log_scales": splats.log_scales.detach(), "rotation": splats.rotation.detach(),
-         "raw_opacity": splats.raw_opacity.detach(), "sh_coeffs": splats.sh_coeffs.detach()}
+    p = {k: getattr(splats, k).detach() for k in PARAMS}
     n, ncoef = int(p["means"].shape[0]), int(p["sh_coeffs"].shape[1])
     m1, m2 = moment_segments(trainer.moment1, n, ncoef), moment_segments(trainer.moment2, n, ncoef)
 
@@ -128,7 +127,7 @@ def refine(trainer, splats) -> McmcRefineStats:
         u = torch.rand(num_added, generator=trainer.rng, device=dev, dtype=torch.float64)
         src = sample_by_weight(torch.sigmoid(p["raw_opacity"]), u)
         _split(p, src, c.mcmc_min_opacity)
-        new = {k: torch.cat([p[k], p[k][src]], 0).contiguous() for k in PARAMS}
+        new = {k: torch.cat([p[k], p[k][src]], 0) for k in PARAMS}
         moments = []
         for segs in (m1, m2):
             parts = []
@@ -137,13 +136,7 @@ def refine(trainer, splats) -> McmcRefineStats:
                 parts += [seg.reshape(-1), torch.zeros(num_added * seg.shape[1], dtype=seg.dtype, device=dev)]
             moments.append(torch.cat(parts))
         trainer.moment1, trainer.moment2 = moments
-        splats.means = torch.nn.Parameter(new["means"])
-        splats.log_scales = torch.nn.Parameter(new["log_scales"])
-        splats.rotation = torch.nn.Parameter(new["rotation"])
-        splats.raw_opacity = torch.nn.Parameter(new["raw_opacity"])
-        splats.sh_coeffs = torch.nn.Parameter(new["sh_coeffs"])
-        splats.xys_dummy = torch.zeros((n_target, 2), dtype=torch.float32, device=dev, requires_grad=True)
-        trainer.grad_2d_accum = torch.zeros(n_target, device=dev)
-        trainer.xy_grad_counts = torch.zeros(n_target, device=dev)
+        splats.replace_parameters(**new)
+        trainer._reset_stats(n_target, dev)  # (the moments above are kept: no optimizer reset)
     trainer.invalidate_cached_rotation()
     return McmcRefineStats(num_relocated, num_added)

@@ -20,6 +20,8 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from . import _lib
+from . import filter3d as F3
+from . import mcmc
 from . import render as R
 from .camera import Camera
 from .dist import allreduce_densification_stats
@@ -50,19 +52,20 @@ class TrainConfig:
     densify_grad_thresh: float = 0.0002
     densify_size_thresh: float = 0.005
     seed: int = 42
-    # Build extension (not in the reference): deferred Adam of the SH block (include/brush_hip.h: BrushLazySh).  Same
-    # parameter values as the eager optimizer, bit for bit; SplatTrainer.sync() brings `splats.sh_coeffs` up to date
-    # for readers that do not go through the trainer (Splats.render / to_ply call it themselves).
+    # The build extensions below are not in the reference.  Which of them train on a single view only, and which make a
+    # step take the separate-call optimizer path, is said once, in SplatTrainer.step's docstring.
+    # Build extension: deferred Adam of the SH block (include/brush_hip.h: BrushLazySh).  Same parameter values as the
+    # eager optimizer, bit for bit; SplatTrainer.sync() brings `splats.sh_coeffs` up to date for readers that do not go
+    # through the trainer (Splats.render / to_ply call it themselves).
     deferred_sh_adam: bool = True
     # Build extension: render and backpropagate in the antialiased mode (BRUSH_AUX_ANTIALIASED: opacity compensation of
-    # the 2D blur).  Single-view training only: a step given an `exchange` raises.  Refinement still prunes on
-    # sigmoid(raw_opacity), as gsplat does.
+    # the 2D blur).  There is no antialiased record path (brush_render_backward_records), so a step given an `exchange`
+    # raises.  Refinement still prunes on sigmoid(raw_opacity), as gsplat does.
     antialiased: bool = False
     # Build extension: per-view camera-pose refinement (brush_amd/pose.py; gsplat's pose_opt is the model).  Each
     # training view carries a camera-frame twist, stepped by Adam from the view-matrix gradient of the render backward.
     # Learning rates in radians / world units per step; pose_reg pulls the twists back to the dataset's poses (and
-    # pins the gauge the scene shares with its cameras).  Single-view training only.  DESIGN §8 row 9 has the runs
-    # these defaults come from.
+    # pins the gauge the scene shares with its cameras).  DESIGN §8 row 9 has the runs these defaults come from.
     pose_opt: bool = False
     lr_pose_rot: float = 1e-3
     lr_pose_trans: float = 5e-4
@@ -71,8 +74,7 @@ class TrainConfig:
     # is the model, gsplat's app_opt covers the same ground).  Each training view carries a 3x4 affine colour map,
     # applied to the render before the loss and stepped by Adam on the device.  lr_exposure decays by the total factor
     # lr_exposure_decay over `total_steps` (formed like the mean rate); exposure_reg pulls the maps back to the identity
-    # (and pins the gain the scene shares with its exposures).  Single-view training only; eval views are rendered as
-    # given.  DESIGN §8 row 11.
+    # (and pins the gain the scene shares with its exposures).  Eval views are rendered as given.  DESIGN §8 row 11.
     exposure_opt: bool = False
     lr_exposure: float = 1e-2
     lr_exposure_decay: float = 0.1
@@ -82,7 +84,7 @@ class TrainConfig:
     # MCMCStrategy): dead splats (opacity <= mcmc_min_opacity) are relocated onto live ones, the count grows by
     # mcmc_growth per refinement up to mcmc_cap_max, every step adds noise of mcmc_noise_lr * lr_mean to the means and
     # the opacity / scale regularisers to the gradients; the optimizer state is kept and opacities are never reset.
-    # Same schedule (warmup_steps, refine_every, max_refine_step).  Single-view training, separate-call optimizer path.
+    # Same schedule (warmup_steps, refine_every, max_refine_step).
     strategy: str = "default"
     mcmc_cap_max: int = 1_000_000
     mcmc_noise_lr: float = 5e5
@@ -96,7 +98,7 @@ class TrainConfig:
     # inverse depths), over the pixels with a measurement and alpha >= depth_alpha_min ("mostly covered": a
     # hyper-parameter default, not a measured number).  The weight goes from depth_weight to depth_weight_final (None:
     # constant) exponentially over `total_steps`, formed like the exposure rate.  0 (the default) is the step without the
-    # option, bit for bit.  Single-view training, separate-call optimizer path.  DESIGN §8 row 12.
+    # option, bit for bit.  DESIGN §8 row 12.
     depth_weight: float = 0.0
     depth_weight_final: Optional[float] = None
     depth_mode: str = "depth"
@@ -134,15 +136,40 @@ class TrainConfig:
     # training loop computes it from the training views, brush_filter3d_rates, before the first step, after every step
     # that changed the splat count and every filter3d_every steps); a step renders and backpropagates through the
     # effective log-scales and opacities (brush_filter3d_apply / _backward around the existing forward and backward) and
-    # steps the raw parameters, on the separate-call optimizer path.  filter3d_variance: the filter's variance in
-    # squared sampling intervals (0.2 is Mip-Splatting's value: a hyper-parameter default, not a measured number).
-    # Refinement, the opacity reset and the prune thresholds keep reading the RAW parameters, as Mip-Splatting's
-    # densification does.  Combines with antialiased, background / masks, exposure, pose and depth; single-view
-    # training, not with strategy "mcmc".  False (the default) is the step without the option, launch for launch.
-    # DESIGN §8 row 17.
+    # steps the raw parameters.  filter3d_variance: the filter's variance in squared sampling intervals (0.2 is
+    # Mip-Splatting's value: a hyper-parameter default, not a measured number).  Refinement, the opacity reset and the
+    # prune thresholds keep reading the RAW parameters, as Mip-Splatting's densification does.  Combines with
+    # antialiased, background / masks, exposure, pose and depth; not with strategy "mcmc".  False (the default) is the
+    # step without the option, launch for launch.  DESIGN §8 row 17.
     filter3d: bool = False
     filter3d_every: int = 100
     filter3d_variance: float = 0.2
+
+    def check(self, multi_rank: bool = False):
+        """A ValueError naming the first thing wrong with the configuration, before anything touches a dataset or a
+        device.  multi_rank: the run is driven with a dist.ViewExchange of more than one rank, which rules out what has
+        to see every view on one GPU."""
+        from .compose import check_background
+
+        if self.strategy not in ("default", "mcmc"):
+            raise ValueError(f"TrainConfig.strategy must be 'default' or 'mcmc', got {self.strategy!r}")
+        if self.depth_mode not in ("depth", "disparity"):
+            raise ValueError(f"TrainConfig.depth_mode must be 'depth' or 'disparity', got {self.depth_mode!r}")
+        if self.depth_weight < 0 or (self.depth_weight_final or 0.0) < 0:
+            raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
+        self.check_downscale_schedule()
+        prune_at = self.check_contribution_prune()
+        if prune_at and self.strategy == "mcmc":
+            raise ValueError("TrainConfig.contribution_prune_at cannot be combined with strategy='mcmc': a fixed "
+                             "budget relocates splats instead of pruning them")
+        if prune_at and multi_rank:  # (every rank would have to measure every view)
+            raise ValueError("TrainConfig.contribution_prune_at cannot be combined with a multi-rank exchange: pruning "
+                             "by contribution is single-GPU")
+        self.check_filter3d()
+        if self.filter3d and multi_rank:  # (the filter's step is single-view)
+            raise ValueError("TrainConfig.filter3d cannot be combined with a multi-rank exchange: the 3D filter is "
+                             "single-GPU")
+        check_background(self.background)
 
     def check_filter3d(self):
         """A ValueError naming what is wrong with the filter3d fields or their combination with the strategy."""
@@ -263,46 +290,41 @@ def l1_ssim_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_weight: float, windo
     return loss, v_pred
 
 
+def optimizer_path(exchange: bool, grad_sync: bool, fused_backward: bool, mcmc: bool, depth: bool,
+                   filter3d: bool) -> str:
+    """Which way a step's gradients reach Adam, from what the step was given (depth: an active depth term; filter3d: a
+    3D filter is set).  "records": the views' gradient records are exchanged and reduced into Adam (brush_amd.dist).
+    "fused": Adam runs inside the backward's last kernel (brush_render_backward_adam[_pose]).  "separate": the dense
+    backward, then brush_adam_step; what needs the dense gradients between the two (grad_sync, the mcmc regularisers,
+    the 3D filter's VJP) or a backward the fused kernel does not have (the depth gradient) forces it.  The first two
+    step only the SH blocks of the splats the view touches, so only they defer the rest (TrainConfig.deferred_sh_adam).
+    """
+    if exchange:
+        return "records"
+    if grad_sync or mcmc or depth or filter3d or not fused_backward:
+        return "separate"
+    return "fused"
+
+
 class SplatTrainer:
     filter3d: Optional[torch.Tensor] = None  # the 3D filter lengths [N] of set_filter3d, or None
 
     def __init__(self, splats: Splats, config: TrainConfig | None = None):
         self.config = config or TrainConfig()
-        if self.config.strategy not in ("default", "mcmc"):
-            raise ValueError(f"TrainConfig.strategy must be 'default' or 'mcmc', got {self.config.strategy!r}")
-        if self.config.depth_mode not in ("depth", "disparity"):
-            raise ValueError(f"TrainConfig.depth_mode must be 'depth' or 'disparity', got {self.config.depth_mode!r}")
-        if self.config.depth_weight < 0 or (self.config.depth_weight_final or 0.0) < 0:
-            raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
-        self.config.check_downscale_schedule()
-        self.config.check_contribution_prune()
-        self.config.check_filter3d()
+        self.config.check()
         self.filter3d = None
-        from .compose import check_background
-        check_background(self.config.background)
         self._bg_rng, self._bg_fixed = None, {}  # "random"'s device generator; the fixed colours' device tensors
         dev = splats.means.device
         assert dev.type == "cuda", "brush_amd has no CPU path: the splats must live on the GPU"
         self.iter = 0
-        n = splats.num_splats()
-        ncoef = int(splats.sh_coeffs.shape[1])
-        self.grad_2d_accum = torch.zeros(n, device=dev)
-        self.xy_grad_counts = torch.zeros(n, device=dev)
-        # Adam moments of the five groups, [means|log_scales|quats|raw_opac|sh] (AdamConfig of train.rs:184)
-        self.moment1 = torch.zeros(n * (11 + 3 * ncoef), device=dev)
-        self.moment2 = torch.zeros(n * (11 + 3 * ncoef), device=dev)
-        self.opt_time = 0  # Adam's per-parameter step count (reset with the optimizer at refinement)
+        self._reset(splats.num_splats(), int(splats.sh_coeffs.shape[1]), dev)
         self.fused_backward = True  # single view: brush_render_backward_adam instead of backward + brush_adam_step
         # rotation/|rotation| left by the previous fused backward, valid only for the very Parameter object the
         # trainer updated (identity + storage + autograd version); see invalidate_cached_rotation().
-        self._norm_rot, self._norm_rot_key, self._norm_rot_owner = None, None, None
+        self.invalidate_cached_rotation()
         self.last_refine = None  # RefineStats, or mcmc.McmcRefineStats with strategy "mcmc"
         self.rng = torch.Generator(device=dev)
         self.rng.manual_seed(self.config.seed)
-        # deferred Adam of the SH block: per-splat optimizer time of the stored block, table of per-step constants
-        self._lazy: Optional[_lib.BrushLazySh] = None
-        self._lazy_bufs = None      # (sh_time, table) tensors the struct points into
-        self._lazy_pending = False  # some block may be behind opt_time
         splats.lazy_sh_owner = self
 
     def invalidate_cached_rotation(self):
@@ -310,6 +332,28 @@ class SplatTrainer:
         kernel): such writes do not bump the tensor version the cache key watches.  In-place ops on the
         Parameter itself, replacing the Parameter and refine_splats are detected without it."""
         self._norm_rot, self._norm_rot_key, self._norm_rot_owner = None, None, None
+
+    def _rotation_key(self, splats: Splats):
+        return (splats.rotation.data_ptr(), splats.num_splats(), splats.rotation._version)
+
+    def _take_rotation(self, splats: Splats, stream) -> torch.Tensor:
+        """rotation / |rotation|, which Splats::render feeds the op (gaussian_splats.rs:174-175): what the previous
+        update left (_store_rotation) when that was for this very rotation, else recomputed.  Empties the cache."""
+        if self._norm_rot is not None and self._norm_rot_key == self._rotation_key(splats) \
+                and self._norm_rot_owner is splats.rotation:
+            norm_rot = self._norm_rot
+        else:
+            quats = splats.rotation.detach()
+            norm_rot = torch.empty_like(quats)
+            with torch.cuda.device(quats.device):
+                _lib.check(_lib.lib().brush_normalize_quats(quats.data_ptr(), norm_rot.data_ptr(), quats.shape[0],
+                                                            stream), "brush_normalize_quats")
+        self.invalidate_cached_rotation()
+        return norm_rot
+
+    def _store_rotation(self, splats: Splats, norm_rot: torch.Tensor):
+        """Keeps the rotation / |rotation| an update kernel wrote for the rotation it has just stepped in place."""
+        self._norm_rot, self._norm_rot_key, self._norm_rot_owner = norm_rot, self._rotation_key(splats), splats.rotation
 
     def set_filter3d(self, filter: Optional[torch.Tensor]):
         """Sets (None: clears) the 3D smoothing filter the next steps train under: a contiguous float32 [N] device
@@ -372,14 +416,23 @@ class SplatTrainer:
                        "brush_lazy_sh_flush")
         self._lazy_pending = False
 
-    def _reset(self, n: int, ncoef: int, dev):
-        """reset_stats + `self.optim = self.opt_config.init()` (train.rs:201-204,559-563)."""
-        self._lazy, self._lazy_bufs, self._lazy_pending = None, None, False
+    def _reset_stats(self, n: int, dev):
+        """reset_stats (train.rs:201-204): the screen-space gradient statistics refinement decides on."""
         self.grad_2d_accum = torch.zeros(n, device=dev)
         self.xy_grad_counts = torch.zeros(n, device=dev)
+
+    def _reset(self, n: int, ncoef: int, dev):
+        """reset_stats + `self.optim = self.opt_config.init()` (train.rs:201-204,559-563): the state of a trainer of `n`
+        splats that has not stepped yet, at construction and after every change of the count."""
+        # deferred Adam of the SH block: per-splat optimizer time of the stored block, table of per-step constants
+        self._lazy: Optional[_lib.BrushLazySh] = None
+        self._lazy_bufs = None      # (sh_time, table) tensors the struct points into
+        self._lazy_pending = False  # some block may be behind opt_time
+        self._reset_stats(n, dev)
+        # Adam moments of the five groups, [means|log_scales|quats|raw_opac|sh] (AdamConfig of train.rs:184)
         self.moment1 = torch.zeros(n * (11 + 3 * ncoef), device=dev)
         self.moment2 = torch.zeros(n * (11 + 3 * ncoef), device=dev)
-        self.opt_time = 0
+        self.opt_time = 0  # Adam's per-parameter step count
 
     @torch.no_grad()
     def refine_splats(self, splats: Splats, pre_step: dict) -> RefineStats:
@@ -430,14 +483,8 @@ class SplatTrainer:
         scale_pruned = start - new["means"].shape[0]  # cumulative, as train.rs:551
         if (self.iter // c.refine_every) % c.reset_alpha_every_refine == 0:
             new["opac"] = torch.zeros_like(new["opac"]) + math.log(c.reset_alpha_value / (1.0 - c.reset_alpha_value))
-        splats.means = torch.nn.Parameter(new["means"].contiguous())
-        splats.rotation = torch.nn.Parameter(new["rotation"].contiguous())
-        splats.sh_coeffs = torch.nn.Parameter(new["sh"].contiguous())
-        splats.raw_opacity = torch.nn.Parameter(new["opac"].contiguous())
-        splats.log_scales = torch.nn.Parameter(new["scales"].contiguous())
-        n = splats.means.shape[0]
-        splats.xys_dummy = torch.zeros((n, 2), dtype=torch.float32, device=dev, requires_grad=True)
-        self._reset(n, int(splats.sh_coeffs.shape[1]), dev)
+        splats.replace_parameters(new["means"], new["sh"], new["rotation"], new["opac"], new["scales"])
+        self._reset(splats.num_splats(), int(splats.sh_coeffs.shape[1]), dev)
         return RefineStats(ns, int(clone_inds.numel()), alpha_pruned, scale_pruned)
 
     @torch.no_grad()
@@ -448,18 +495,18 @@ class SplatTrainer:
         self.sync(splats)
         dev = splats.means.device
         keep = keep.to(device=dev, dtype=torch.int64)
-        for name in ("means", "rotation", "sh_coeffs", "raw_opacity", "log_scales"):
-            setattr(splats, name, torch.nn.Parameter(getattr(splats, name).detach()[keep].contiguous()))
-        n = splats.means.shape[0]
-        splats.xys_dummy = torch.zeros((n, 2), dtype=torch.float32, device=dev, requires_grad=True)
-        self._reset(n, int(splats.sh_coeffs.shape[1]), dev)
+        splats.replace_parameters(**{name: getattr(splats, name).detach()[keep] for name in
+                                     ("means", "rotation", "sh_coeffs", "raw_opacity", "log_scales")})
+        self._reset(splats.num_splats(), int(splats.sh_coeffs.shape[1]), dev)
         self.invalidate_cached_rotation()
-        return n
+        return splats.num_splats()
+
+    def _decayed(self, start: float, factor: float) -> float:
+        """`start` on its way to start * factor, exponentially over config.total_steps, at this iteration."""
+        return start * (factor ** (1.0 / self.config.total_steps)) ** self.iter
 
     def _lr_mean(self, scene_extent: float) -> float:
-        c = self.config
-        gamma = c.lr_mean_decay ** (1.0 / c.total_steps)
-        return c.lr_mean * gamma ** self.iter * scene_extent
+        return self._decayed(self.config.lr_mean, self.config.lr_mean_decay) * scene_extent
 
     def _background(self, background, dev) -> Optional[torch.Tensor]:
         """step's `background` as the float32 [3] device tensor brush_compose_* reads: a tensor is taken as it is, a
@@ -480,118 +527,206 @@ class SplatTrainer:
         return self._bg_fixed[background]
 
     def _lr_exposure(self) -> float:
-        c = self.config
-        gamma = c.lr_exposure_decay ** (1.0 / c.total_steps)
-        return c.lr_exposure * gamma ** self.iter
+        return self._decayed(self.config.lr_exposure, self.config.lr_exposure_decay)
 
     def _depth_weight(self) -> float:
         c = self.config
         if c.depth_weight_final is None or c.depth_weight <= 0.0 or c.depth_weight_final <= 0.0:
             return c.depth_weight  # (an exponential ramp needs two positive ends)
-        gamma = (c.depth_weight_final / c.depth_weight) ** (1.0 / c.total_steps)
-        return c.depth_weight * gamma ** self.iter
+        return self._decayed(c.depth_weight, c.depth_weight_final / c.depth_weight)
+
+    def _check_step(self, grad_sync, exchange, view_index, poses, exposures, gt_depth):
+        """Refuses the combinations of step's arguments and the configuration that no path serves, before anything is
+        touched (neither the trainer's state nor the splats are looked at)."""
+        c = self.config
+        if c.filter3d and self.filter3d is None:
+            raise ValueError("TrainConfig.filter3d is set but the trainer has no filter: call set_filter3d first "
+                             "(train_loop.TrainLoop does)")
+        if exchange is not None or grad_sync is not None:
+            # what is single-view, in the order it is refused in; a new single-view option is one more row
+            for on, what in ((self.filter3d is not None, "the 3D filter"),
+                             (gt_depth is not None, "depth supervision"),
+                             (c.strategy == "mcmc", "the mcmc strategy"),
+                             (poses is not None, "pose refinement"),
+                             (exposures is not None, "exposure compensation")):
+                if on:
+                    raise ValueError(f"{what} is single-view: it cannot be combined with exchange / grad_sync")
+        for name, table in (("poses", poses), ("exposures", exposures)):
+            if table is not None and view_index is None:
+                raise ValueError(f"{name} needs view_index")
+        if exchange is not None and grad_sync is not None:
+            raise ValueError("exchange and grad_sync are two ways to sum the views' gradients: give one of them")
+        if c.antialiased and exchange is not None:
+            raise ValueError("antialiased training has no data-parallel record path (brush_render_backward_records)")
+
+    def _loss(self, pred, gt_image, batch_views, loss_out, view_index, exposures, background, gt_mask):
+        """(loss [1], d loss / d pred at the raw render `pred`): exposure map, composition over the background and
+        under the mask, L1 / SSIM, and the same stages backwards, each only with its option."""
+        from .compose import compose_backward, compose_forward
+
+        c = self.config
+        bg = None if background is None else self._background(background, pred.device)
+        compose = bg is not None or gt_mask is not None
+        seen = pred if exposures is None else exposures.forward(view_index, pred)
+        target = gt_image
+        if compose:
+            seen, target = compose_forward(seen, gt_image, background=bg, mask=gt_mask)
+        loss, v_pred = l1_ssim_loss(seen, target, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views, out=loss_out)
+        if compose:
+            compose_backward(v_pred, background=bg, mask=gt_mask, out=v_pred)
+        if exposures is not None:  # the loss saw the compensated image; the render backward takes the gradient at pred
+            v_pred = exposures.backward_step(view_index, pred, v_pred, lr=self._lr_exposure())
+        return loss, v_pred
+
+    def _update_records(self, splats, exchange, cfg, size, params, norm_rot, fwd, want_stats):
+        """View-sharded data parallelism: records of this view -> all-gather -> per-splat sum -> Adam."""
+        means, log_scales, quats, raw_opac, sh = params
+        u, aux, pred, v_pred = fwd
+        exchange.backward_records(u, aux, means, log_scales, norm_rot, raw_opac, pred, v_pred)
+        exchange.gather()
+        next_rot = torch.empty_like(quats)
+        exchange.reduce_adam(cfg, size, means, log_scales, quats, raw_opac, sh, self.moment1, self.moment2, next_rot,
+                             self.grad_2d_accum if want_stats else None, self.xy_grad_counts if want_stats else None)
+        self._store_rotation(splats, next_rot)
+
+    def _update_fused(self, splats, cfg, size, params, norm_rot, fwd, want_stats, pose, stream):
+        """Single view: the gradients go straight through the optimizer inside the backward's last kernel."""
+        means, log_scales, quats, raw_opac, sh = params
+        u, aux, pred, v_pred = fwd
+        n, l = means.shape[0], _lib.lib()
+        nbytes = _lib.size_query("brush_bwd_workspace_size_flags", n, size[0], size[1], int(u.sh_degree),
+                                 int(aux.max_intersects), aux.workspace_flags)
+        ws, s_aux = aux.backward_workspace(nbytes, means.device)
+        v_xy = torch.empty((max(n, 1), 2), dtype=torch.float32, device=means.device)
+        next_rot = torch.empty_like(quats)
+        args = (C.byref(u), C.byref(s_aux), C.byref(cfg), means.data_ptr(), log_scales.data_ptr(),
+                norm_rot.data_ptr(), quats.data_ptr(), raw_opac.data_ptr(), sh.data_ptr(), n, pred.data_ptr(),
+                v_pred.data_ptr(), v_xy.data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
+                next_rot.data_ptr(), self.grad_2d_accum.data_ptr() if want_stats else None,
+                self.xy_grad_counts.data_ptr() if want_stats else None, ws.data_ptr(), nbytes)
+        if pose is None:
+            _lib.check(l.brush_render_backward_adam(*args, stream), "brush_render_backward_adam")
+        else:
+            _lib.check(l.brush_render_backward_adam_pose(*args, pose[0].data_ptr(), pose[1].data_ptr(),
+                                                         pose[1].numel(), stream),
+                       "brush_render_backward_adam_pose")
+        self._store_rotation(splats, next_rot)
+
+    def _update_separate(self, cfg, size, params, norm_rot, fwd, want_stats, pose, stream, effective, depth_grad,
+                         grad_sync, batch_views, scene_extent):
+        """Separate calls: the dense backward, then whatever works on dense gradients (the 3D filter's VJP, grad_sync,
+        the refinement statistics, the mcmc regularisers), then brush_adam_step on every splat."""
+        c = self.config
+        use_mcmc = c.strategy == "mcmc"
+        means, log_scales, quats, raw_opac, sh = params
+        u, aux, pred, v_pred = fwd
+        n, ncoef, l = means.shape[0], int(sh.shape[1]), _lib.lib()
+        eff_scales, eff_opac = effective
+        grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
+                                        depth=depth_grad, pose=pose)
+        if self.filter3d is not None:  # gradients at the effective parameters -> at the raw ones, in place
+            F3.backward_into(log_scales, raw_opac, self.filter3d, n, grads["v_scales"], grads["v_opac"], stream)
+        if grad_sync is not None:  # view-sharded data parallelism: sum the per-view gradients
+            grad_sync(block, aux)
+        if want_stats:
+            v_xy = grads["v_xy"]
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and batch_views > 1:
+                from .dist import densification_stats
+                stats = densification_stats(v_xy, aux, size)
+                allreduce_densification_stats(stats)
+                self.grad_2d_accum += stats[0] * float(batch_views)  # undo the 1/batch of the loss scale
+                self.xy_grad_counts += stats[1]
+            else:
+                s_aux = aux._as_struct()
+                _lib.check(l.brush_refine_stats(C.byref(s_aux), v_xy.data_ptr(), n, size[0], size[1],
+                                                self.grad_2d_accum.data_ptr(), self.xy_grad_counts.data_ptr(),
+                                                stream), "brush_refine_stats")
+        if use_mcmc:  # the regularisers go through Adam, as in gsplat
+            mcmc.reg_grads(raw_opac, log_scales, n, c.mcmc_opacity_reg, c.mcmc_scale_reg, grads["v_opac"],
+                           grads["v_scales"], stream)
+        _lib.check(l.brush_adam_step(C.byref(cfg), n, R.sh_degree_from_coeffs(ncoef), means.data_ptr(),
+                                     log_scales.data_ptr(), quats.data_ptr(), raw_opac.data_ptr(), sh.data_ptr(),
+                                     grads["v_means"].data_ptr(), grads["v_scales"].data_ptr(),
+                                     grads["v_quats"].data_ptr(), grads["v_opac"].data_ptr(),
+                                     grads["v_sh"].data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
+                                     stream),
+                   "brush_adam_step")
+        if use_mcmc and c.mcmc_noise_lr != 0.0:
+            mcmc.inject_noise(means, log_scales, quats, raw_opac, n, c.mcmc_noise_lr * self._lr_mean(scene_extent),
+                              c.seed, self.iter, stream)
 
     def step(self, splats: Splats, camera: Camera, gt_image: torch.Tensor, scene_extent: float = 1.0,
              batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None,
              loss_out: Optional[torch.Tensor] = None, view_index: Optional[int] = None, poses=None,
              exposures=None, gt_depth: Optional[torch.Tensor] = None, depth_scale: float = 1.0,
              depth_offset: float = 0.0, background=None, gt_mask: Optional[torch.Tensor] = None):
-        """One reference training iteration on one view (batch size is 1 in the reference,
-        train.rs:216-219).  `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the
-        same bits as its float32 twin; brush_amd.scene_loader keeps the training images on the device in this form).
-        `loss_out`: optional float32 [1] device tensor the loss is written into (l1_ssim_loss's `out`).  With view-sharded data parallelism call it on each rank with
-        `batch_views` = world size and either `exchange` = a brush_amd.dist.ViewExchange (per-view gradient
-        records all-gathered, summed per splat in view order and fed straight into Adam: every rank applies
-        the same bits) or `grad_sync(block, aux)` summing the dense gradient block over views
-        (brush_amd.dist.allreduce_param_grads).
+        """One reference training iteration on one view (batch size is 1 in the reference, train.rs:216-219).  Returns
+        (loss [1] device tensor, the raw render, its aux).
+        `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the same bits as its float32
+        twin; brush_amd.scene_loader keeps the training images on the device in this form).
+        `loss_out`: optional float32 [1] device tensor the loss is written into (l1_ssim_loss's `out`).
+        `batch_views`, `grad_sync`, `exchange`: view-sharded data parallelism.  Call the step on each rank with
+        `batch_views` = world size and either `exchange` = a brush_amd.dist.ViewExchange (per-view gradient records
+        all-gathered, summed per splat in view order and fed straight into Adam: every rank applies the same bits) or
+        `grad_sync(block, aux)` summing the dense gradient block over views (brush_amd.dist.allreduce_param_grads); not
+        both.
         `poses` (a brush_amd.pose.PoseTable) with `view_index`: the view's pending pose update is applied, the view is
         rendered through its current matrix, the backward also returns the view-matrix gradient (the `_pose` entry
-        points) and hands it to the table without waiting for it.  Not with `exchange` / `grad_sync`.
+        points) and hands it to the table without waiting for it.
         `exposures` (a brush_amd.exposure.ExposureTable) with `view_index`: the view's affine colour map is applied to
         the render, the loss is taken on the result, and the table's backward returns the gradient at the raw render
         (which every backward path then receives beside the raw render) and steps the view's map, all on the device.
-        Not with `exchange` / `grad_sync`.  The step still returns the raw render.
-        With TrainConfig.strategy = "mcmc" the step takes the separate-call path (backward, brush_mcmc_reg_grads,
-        brush_adam_step) whatever `fused_backward` says, then brush_mcmc_inject_noise; a refinement step ends in
-        mcmc.refine.  Not with `exchange` / `grad_sync` either.
         `gt_depth` (the view's depth map, [h,w] uint16 or float32 on the device, read as raw * depth_scale +
         depth_offset; scene_loader keeps it there as stored) with a positive current TrainConfig.depth_weight: the view
         is rendered with its depth output, brush_depth_loss adds the depth term's alpha gradient into the colour loss's
         gradient and the term itself into the step's loss, and the backward carries the depth gradient
-        (brush_render_backward_depth); the step then takes the separate-call path whatever `fused_backward` says.  With
-        gt_depth None or a zero weight the step is the one without the option.  Not with `exchange` / `grad_sync`.
+        (brush_render_backward_depth).  With gt_depth None or a zero weight the step is the one without the option.
         `background` (None, "white", "black", "random", an (r, g, b) tuple or a float32 [3] device tensor) and `gt_mask`
         (uint8 [h,w] on the device, nonzero = keep): the image the loss would see (the render, or its exposure-compensated
         form) and the target go through brush_compose_forward first, and the loss's gradient through
         brush_compose_backward, in place, before the exposure backward and every render backward path.  With a
         background the loss compares opaque RGB.  The depth term is not masked here: scene_loader zeroes the depth maps
         under the masks at load.  On every optimizer path; with both None the step is the one without the option.
-        With a 3D filter set (set_filter3d; TrainConfig.filter3d demands one) the step takes the separate-call path
-        whatever `fused_backward` says: brush_filter3d_apply, the forward and the backward on the effective log-scales
-        and opacities, brush_filter3d_backward on the dense gradients, then the refinement statistics and
-        brush_adam_step on the raw parameters as without it.  A filter whose length is not the current splat count is
-        refused.  Not with `exchange` / `grad_sync`."""
+        From the trainer: TrainConfig.strategy = "mcmc" puts brush_mcmc_reg_grads in front of brush_adam_step and
+        brush_mcmc_inject_noise behind it, and a refinement step ends in mcmc.refine; a 3D filter (set_filter3d;
+        TrainConfig.filter3d demands one, and one whose length is not the current splat count is refused) puts
+        brush_filter3d_apply in front of the forward, which like the backward then works on the effective log-scales
+        and opacities, and brush_filter3d_backward on the dense gradients in front of the refinement statistics and
+        brush_adam_step on the raw parameters.
+        Single-view, that is refused with `exchange` / `grad_sync`: the 3D filter, `gt_depth`, strategy "mcmc", `poses`
+        and `exposures` (_check_step); TrainConfig.antialiased is refused with `exchange` alone.  The optimizer path
+        (optimizer_path): the records path with `exchange`; the separate-call path (backward, then brush_adam_step)
+        with `grad_sync`, strategy "mcmc", an active depth term or a 3D filter, whatever `fused_backward` says;
+        otherwise the fused path (brush_render_backward_adam[_pose]) unless `fused_backward` is False."""
         c = self.config
+        self._check_step(grad_sync, exchange, view_index, poses, exposures, gt_depth)
         use_mcmc = c.strategy == "mcmc"
         filt = self.filter3d
-        if c.filter3d and filt is None:
-            raise ValueError("TrainConfig.filter3d is set but the trainer has no filter: call set_filter3d first "
-                             "(train_loop.TrainLoop does)")
-        if filt is not None and (exchange is not None or grad_sync is not None):
-            raise ValueError("the 3D filter is single-view: it cannot be combined with exchange / grad_sync")
-        if gt_depth is not None and (exchange is not None or grad_sync is not None):
-            raise ValueError("depth supervision is single-view: it cannot be combined with exchange / grad_sync")
         depth_w = self._depth_weight() if gt_depth is not None else 0.0
         use_depth = depth_w > 0.0
-        if use_mcmc:
-            from . import mcmc
-            if exchange is not None or grad_sync is not None:
-                raise ValueError("the mcmc strategy is single-view: it cannot be combined with exchange / grad_sync")
-        if poses is not None:
-            if exchange is not None or grad_sync is not None:
-                raise ValueError("pose refinement is single-view: it cannot be combined with exchange / grad_sync")
-            if view_index is None:
-                raise ValueError("poses needs view_index")
-        if exposures is not None:
-            if exchange is not None or grad_sync is not None:
-                raise ValueError("exposure compensation is single-view: it cannot be combined with exchange / grad_sync")
-            if view_index is None:
-                raise ValueError("exposures needs view_index")
-        if c.antialiased and exchange is not None:
-            raise ValueError("antialiased training has no data-parallel record path (brush_render_backward_records)")
+        path = optimizer_path(exchange is not None, grad_sync is not None, self.fused_backward, use_mcmc, use_depth,
+                              filt is not None)
         h, w = int(gt_image.shape[0]), int(gt_image.shape[1])
         n, ncoef = splats.num_splats(), int(splats.sh_coeffs.shape[1])
         if self.moment1.numel() != n * (11 + 3 * ncoef):
             raise ValueError("the number of splats changed outside refine_splats: build a new SplatTrainer")
         means, log_scales, quats = splats.means.detach(), splats.log_scales.detach(), splats.rotation.detach()
         sh, raw_opac = splats.sh_coeffs.detach(), splats.raw_opacity.detach()
-        for t in (means, log_scales, quats, sh, raw_opac):
+        params = (means, log_scales, quats, raw_opac, sh)
+        for t in params:
             assert t.is_contiguous() and t.dtype == torch.float32
         if filt is not None:
-            from . import filter3d as F3
             try:
                 F3.check_filter(filt, n, means.device)
             except ValueError as e:
                 raise ValueError(f"stale 3D filter: {e}; set one for the current splats (set_filter3d)") from None
-        l = _lib.lib()
         stream = _lib.current_stream(means.device)
-        # Splats::render feeds rotation / |rotation| (gaussian_splats.rs:174-175).  The fused backward of the
-        # previous step already wrote it for the updated rotation; recompute when anyone else touched it.
-        key = (quats.data_ptr(), n, splats.rotation._version)
-        if self._norm_rot is not None and self._norm_rot_key == key and self._norm_rot_owner is splats.rotation:
-            norm_rot = self._norm_rot
-        else:
-            norm_rot = torch.empty_like(quats)
-            with torch.cuda.device(means.device):
-                _lib.check(l.brush_normalize_quats(quats.data_ptr(), norm_rot.data_ptr(), n, stream), "brush_normalize_quats")
-        self.invalidate_cached_rotation()
-        # the optimizer runs inside a kernel that sees which splats the step touches: the single-view fused backward, or
-        # the data-parallel reduction of the views' records (both take BrushAdamConfig.lazy_sh)
-        fused = grad_sync is None and (exchange is not None or self.fused_backward) and not use_mcmc and not use_depth \
-            and filt is None
-        lazy = self._lazy_state(splats, n, ncoef) if fused else None
+        norm_rot = self._take_rotation(splats, stream)
+        # on the records and fused paths the optimizer runs inside a kernel that sees which splats the step touches
+        # (both take BrushAdamConfig.lazy_sh); the separate calls read and step every SH block
+        lazy = self._lazy_state(splats, n, ncoef) if path != "separate" else None
         if lazy is None:
-            self.sync(splats)  # this step reads / steps every SH block: nothing may stay pending
+            self.sync(splats)  # nothing may stay pending
             self._lazy = None
         viewmat, pose = None, None
         if poses is not None:
@@ -600,31 +735,15 @@ class SplatTrainer:
             pose = R.pose_buffers(n, means.device)
         depth_bufs = R._depth_buffers(n, (w, h), means.device) if use_depth else None  # (depth map, compact depth)
         # the renderer sees the effective log-scales and opacities; everything else keeps reading the raw ones
-        eff_scales, eff_opac = log_scales, raw_opac
+        effective = (log_scales, raw_opac)
         if filt is not None:
             with torch.cuda.device(means.device):
-                eff_scales, eff_opac = F3.apply_into(log_scales, raw_opac, filt, n, stream)
-        pred, aux, u = R._forward_impl(camera, (w, h), means, eff_scales, norm_rot, sh, eff_opac, False, None,
+                effective = F3.apply_into(log_scales, raw_opac, filt, n, stream)
+        pred, aux, u = R._forward_impl(camera, (w, h), means, effective[0], norm_rot, sh, effective[1], False, None,
                                        lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat, depth=depth_bufs)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
-        bg = None if background is None else self._background(background, means.device)
-        if bg is not None or gt_mask is not None:
-            from .compose import compose_backward, compose_forward
-            seen = pred if exposures is None else exposures.forward(view_index, pred)
-            seen, target = compose_forward(seen, gt_image, background=bg, mask=gt_mask)
-            loss, v_pred = l1_ssim_loss(seen, target, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views,
-                                        out=loss_out)
-            compose_backward(v_pred, background=bg, mask=gt_mask, out=v_pred)
-            if exposures is not None:
-                v_pred = exposures.backward_step(view_index, pred, v_pred, lr=self._lr_exposure())
-        elif exposures is None:
-            loss, v_pred = l1_ssim_loss(pred, gt_image, c.ssim_weight, c.ssim_window_size, 1.0 / batch_views,
-                                        out=loss_out)
-        else:  # the loss sees the compensated image; the backward below sees the raw render and the gradient at it
-            loss, v_out = l1_ssim_loss(exposures.forward(view_index, pred), gt_image, c.ssim_weight,
-                                       c.ssim_window_size, 1.0 / batch_views, out=loss_out)
-            v_pred = exposures.backward_step(view_index, pred, v_out, lr=self._lr_exposure())
+        loss, v_pred = self._loss(pred, gt_image, batch_views, loss_out, view_index, exposures, background, gt_mask)
         depth_grad = None
         if use_depth:  # on the raw render: alpha gradient into v_pred, the term into the step's loss, no read-back
             from .depth_loss import depth_loss_into
@@ -647,70 +766,15 @@ class SplatTrainer:
         if lazy is not None:
             cfg.lazy_sh = C.pointer(lazy)
         want_stats = self.iter > c.warmup_steps and not use_mcmc  # housekeeping, train.rs:284-316
+        fwd = (u, aux, pred, v_pred)
         with torch.cuda.device(means.device):
-            if exchange is not None:
-                # view-sharded data parallelism: records of this view -> all-gather -> per-splat sum -> Adam
-                exchange.backward_records(u, aux, means, log_scales, norm_rot, raw_opac, pred, v_pred)
-                exchange.gather()
-                next_rot = torch.empty_like(quats)
-                exchange.reduce_adam(cfg, (w, h), means, log_scales, quats, raw_opac, sh, self.moment1, self.moment2,
-                                     next_rot, self.grad_2d_accum if want_stats else None,
-                                     self.xy_grad_counts if want_stats else None)
-                self._norm_rot, self._norm_rot_key = next_rot, (quats.data_ptr(), n, splats.rotation._version)
-                self._norm_rot_owner = splats.rotation
-            elif fused:
-                # single view: gradients go straight through the optimizer inside the backward kernel
-                nbytes = _lib.size_query("brush_bwd_workspace_size_flags", n, w, h, int(u.sh_degree),
-                                         int(aux.max_intersects), aux.workspace_flags)
-                ws, s_aux = aux.backward_workspace(nbytes, means.device)
-                v_xy = torch.empty((max(n, 1), 2), dtype=torch.float32, device=means.device)
-                next_rot = torch.empty_like(quats)
-                args = (C.byref(u), C.byref(s_aux), C.byref(cfg), means.data_ptr(), log_scales.data_ptr(),
-                        norm_rot.data_ptr(), quats.data_ptr(), raw_opac.data_ptr(), sh.data_ptr(), n, pred.data_ptr(),
-                        v_pred.data_ptr(), v_xy.data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
-                        next_rot.data_ptr(), self.grad_2d_accum.data_ptr() if want_stats else None,
-                        self.xy_grad_counts.data_ptr() if want_stats else None, ws.data_ptr(), nbytes)
-                if pose is None:
-                    _lib.check(l.brush_render_backward_adam(*args, stream), "brush_render_backward_adam")
-                else:
-                    _lib.check(l.brush_render_backward_adam_pose(*args, pose[0].data_ptr(), pose[1].data_ptr(),
-                                                                 pose[1].numel(), stream),
-                               "brush_render_backward_adam_pose")
-                self._norm_rot, self._norm_rot_key = next_rot, (quats.data_ptr(), n, splats.rotation._version)
-                self._norm_rot_owner = splats.rotation
+            if path == "records":
+                self._update_records(splats, exchange, cfg, (w, h), params, norm_rot, fwd, want_stats)
+            elif path == "fused":
+                self._update_fused(splats, cfg, (w, h), params, norm_rot, fwd, want_stats, pose, stream)
             else:
-                grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
-                                                depth=depth_grad, pose=pose)
-                if filt is not None:  # gradients at the effective parameters -> at the raw ones, in place
-                    F3.backward_into(log_scales, raw_opac, filt, n, grads["v_scales"], grads["v_opac"], stream)
-                if grad_sync is not None:  # view-sharded data parallelism: sum the per-view gradients
-                    grad_sync(block, aux)
-                if want_stats:
-                    v_xy = grads["v_xy"]
-                    if torch.distributed.is_available() and torch.distributed.is_initialized() and batch_views > 1:
-                        from .dist import densification_stats
-                        stats = densification_stats(v_xy, aux, (w, h))
-                        allreduce_densification_stats(stats)
-                        self.grad_2d_accum += stats[0] * float(batch_views)  # undo the 1/batch of the loss scale
-                        self.xy_grad_counts += stats[1]
-                    else:
-                        s_aux = aux._as_struct()
-                        _lib.check(l.brush_refine_stats(C.byref(s_aux), v_xy.data_ptr(), n, w, h,
-                                                        self.grad_2d_accum.data_ptr(), self.xy_grad_counts.data_ptr(),
-                                                        stream), "brush_refine_stats")
-                if use_mcmc:  # the regularisers go through Adam, as in gsplat
-                    mcmc.reg_grads(raw_opac, log_scales, n, c.mcmc_opacity_reg, c.mcmc_scale_reg, grads["v_opac"],
-                                   grads["v_scales"], stream)
-                _lib.check(l.brush_adam_step(C.byref(cfg), n, R.sh_degree_from_coeffs(ncoef), means.data_ptr(),
-                                             log_scales.data_ptr(), quats.data_ptr(), raw_opac.data_ptr(), sh.data_ptr(),
-                                             grads["v_means"].data_ptr(), grads["v_scales"].data_ptr(),
-                                             grads["v_quats"].data_ptr(), grads["v_opac"].data_ptr(),
-                                             grads["v_sh"].data_ptr(), self.moment1.data_ptr(), self.moment2.data_ptr(),
-                                             stream),
-                           "brush_adam_step")
-                if use_mcmc and c.mcmc_noise_lr != 0.0:
-                    mcmc.inject_noise(means, log_scales, quats, raw_opac, n,
-                                      c.mcmc_noise_lr * self._lr_mean(scene_extent), c.seed, self.iter, stream)
+                self._update_separate(cfg, (w, h), params, norm_rot, fwd, want_stats, pose, stream, effective,
+                                      depth_grad, grad_sync, batch_views, scene_extent)
         if pose is not None:
             poses.push(view_index, pose[0])
         self.opt_time += 1
@@ -718,9 +782,8 @@ class SplatTrainer:
             self._lazy_pending = True
         if do_refine:
             self.sync(splats)  # refinement reads the post-step coefficients of every splat
-        if use_mcmc:
-            self.last_refine = mcmc.refine(self, splats) if do_refine else None
+            self.last_refine = mcmc.refine(self, splats) if use_mcmc else self.refine_splats(splats, pre_step)
         else:
-            self.last_refine = self.refine_splats(splats, pre_step) if do_refine else None
+            self.last_refine = None
         self.iter += 1
         return loss, pred, aux

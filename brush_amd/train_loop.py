@@ -148,45 +148,22 @@ def random_init_bounds(scene) -> Tuple[np.ndarray, np.ndarray]:
     return scene.bounds(e * 0.25, e)
 
 
-def check_contribution_prune(config: TrainConfig, exchange=None) -> Tuple[int, ...]:
-    """The validated TrainConfig.contribution_prune_at of a run; a ValueError when the run cannot prune by contribution:
-    strategy "mcmc" (a fixed budget relocates dead splats instead of dropping them) or a multi-rank `exchange` (a
-    dist.ViewExchange of more than one rank: every rank would have to measure every view)."""
-    steps = config.check_contribution_prune()
-    if steps and config.strategy == "mcmc":
-        raise ValueError("TrainConfig.contribution_prune_at cannot be combined with strategy='mcmc': a fixed budget "
-                         "relocates splats instead of pruning them")
-    if steps and exchange is not None and int(getattr(exchange, "world", 1)) > 1:
-        raise ValueError("TrainConfig.contribution_prune_at cannot be combined with a multi-rank exchange: pruning by "
-                         "contribution is single-GPU")
-    return steps
-
-
-def check_filter3d(config: TrainConfig, exchange=None):
-    """A ValueError when the run cannot train under the 3D filter: bad TrainConfig.filter3d fields, strategy "mcmc", or
-    a multi-rank `exchange` (a dist.ViewExchange of more than one rank: the filter's step is single-view)."""
-    config.check_filter3d()
-    if config.filter3d and exchange is not None and int(getattr(exchange, "world", 1)) > 1:
-        raise ValueError("TrainConfig.filter3d cannot be combined with a multi-rank exchange: the 3D filter is "
-                         "single-GPU")
-
-
 class TrainLoop:
     """The state of one run: splats, trainer, resident views and the device loss log.  `train_scene` drives it; tests
     and tools may call step() / evaluate() themselves (from one thread, on the current stream)."""
 
     def __init__(self, dataset: Dataset, config: Optional[TrainConfig] = None, *, steps: int, init=None,
                  init_count: int = 10000, sh_degree: int = 3, seed: int = 42, device=None, exchange=None):
-        """exchange: the dist.ViewExchange of a data-parallel driver, looked at only to refuse what a multi-rank run
-        cannot do (check_contribution_prune); the loop itself trains single-view."""
+        """exchange: the dist.ViewExchange of a data-parallel driver, looked at only to refuse what a run of more than
+        one rank cannot do (TrainConfig.check's multi_rank); the loop itself trains single-view."""
         if steps < 0:
             raise ValueError(f"steps must be >= 0, got {steps}")
-        self._prune_at = frozenset(check_contribution_prune(config or TrainConfig(), exchange))
-        check_filter3d(config or TrainConfig(), exchange)
-        self.dataset = dataset
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         # the mean learning rate decays over the run; the refinement RNG takes the run's seed (train_loop.rs:44-46)
         self.config = dataclasses.replace(config or TrainConfig(), total_steps=max(int(steps), 1), seed=int(seed))
+        self.config.check(multi_rank=exchange is not None and int(getattr(exchange, "world", 1)) > 1)
+        self._prune_at = frozenset(self.config.check_contribution_prune())
+        self.dataset = dataset
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.steps = int(steps)
         self.rng = np.random.default_rng(seed)  # random init and eval view choice, as the reference's one StdRng
         if isinstance(init, Splats):
@@ -211,11 +188,6 @@ class TrainLoop:
 
             self.exposures = ExposureTable(len(self.loader), self.device, self.config.lr_exposure,
                                            self.config.exposure_reg)
-        # depth supervision: the drawn view's resident depth map goes with the step (views without one train as before)
-        self._depth = self.config.depth_weight > 0.0 and any(d is not None for d in self.loader.depths)
-        # background colour and loss masks: the drawn view's resident mask and the configured colour go with the step
-        self._masks = any(m is not None for m in self.loader.masks)
-        self._compose = self.config.background is not None or self._masks
         # 3D smoothing filter: the training views' records go to the device once, so that a refresh is launches only.
         # Full-size intrinsics and the dataset's poses, whatever level the downscale schedule trains at and whatever
         # pose_opt has moved: the filter bounds what the stored images can resolve.
@@ -272,20 +244,18 @@ class TrainLoop:
         if factor != self.loader.downscale:  # a level switch: launches only (SceneLoader.set_downscale)
             self.loader.set_downscale(factor)
             self.log.downscales.append((self.done, factor))
-        if self.poses is None and self.exposures is None and not self._depth and not self._compose:
-            view, gt = self.loader.next_batch()
-            self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
-                              loss_out=self.losses[self.done:self.done + 1])
-        else:
-            i, view, gt = self.loader.next_indexed()
-            depth = self.loader.depth(i) if self._depth else None
-            self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
-                              loss_out=self.losses[self.done:self.done + 1],
-                              view_index=i if (self.poses is not None or self.exposures is not None) else None,
-                              poses=self.poses, exposures=self.exposures, gt_depth=depth,
-                              depth_scale=getattr(view, "depth_scale", 1.0),
-                              depth_offset=getattr(view, "depth_offset", 0.0),
-                              background=self.config.background, gt_mask=self.loader.mask(i) if self._masks else None)
+        # every option that is off hands the step None (or a neutral value): that is the step without the option.  The
+        # drawn view's resident depth map (with depth supervision on) and loss mask go with the step where the view has
+        # them; views without one train as before.
+        i, view, gt = self.loader.next_indexed()
+        self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
+                          loss_out=self.losses[self.done:self.done + 1],
+                          view_index=i if (self.poses is not None or self.exposures is not None) else None,
+                          poses=self.poses, exposures=self.exposures,
+                          gt_depth=self.loader.depth(i) if self.config.depth_weight > 0.0 else None,
+                          depth_scale=getattr(view, "depth_scale", 1.0),
+                          depth_offset=getattr(view, "depth_offset", 0.0),
+                          background=self.config.background, gt_mask=self.loader.mask(i))
         if self.trainer.last_refine is not None:
             self._filter_stale = True  # refinement rebuilt the splats: the filter belongs to the old rows
         if self.done in self._prune_at:
@@ -521,11 +491,15 @@ def main(argv=None) -> int:
     try:
         schedule = downscale_schedule_from_args(args)
         prune_at = () if args.contribution_prune_at is None else parse_prune_steps(args.contribution_prune_at)
-        check_contribution_prune(TrainConfig(strategy=args.strategy, contribution_prune_at=prune_at,
-                                             contribution_prune_min=args.contribution_prune_min))
         from .compose import parse_background
         background = None if args.background is None else parse_background(args.background)
-        check_filter3d(TrainConfig(strategy=args.strategy, filter3d=args.filter3d, filter3d_every=args.filter3d_every))
+        config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
+                             mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt, depth_weight=args.depth_weight,
+                             depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
+                             downscale_schedule=schedule, contribution_prune_at=prune_at,
+                             contribution_prune_min=args.contribution_prune_min, background=background,
+                             use_masks=not args.no_masks, filter3d=args.filter3d, filter3d_every=args.filter3d_every)
+        config.check()  # the configuration the run trains with, before the dataset is loaded
     except ValueError as e:
         p.error(str(e))
     if not os.path.exists(args.dataset):
@@ -534,8 +508,6 @@ def main(argv=None) -> int:
         p.error("--steps and --eval-every must be >= 0")
     if args.cap_max < 1:
         p.error("--cap-max must be >= 1")
-    if args.depth_weight < 0 or (args.depth_weight_final is not None and args.depth_weight_final < 0):
-        p.error("--depth-weight and --depth-weight-final must be >= 0")
     if args.init is not None and not os.path.isfile(args.init):
         p.error(f"--init file not found: {args.init}")
 
@@ -571,12 +543,6 @@ def main(argv=None) -> int:
         cameras.extend({"name": name, "world_to_camera": [[float(x) for x in row] for row in m]}
                        for name, m in loop.train_viewmats())
 
-    config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
-                         mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt, depth_weight=args.depth_weight,
-                         depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
-                         downscale_schedule=schedule, contribution_prune_at=prune_at,
-                         contribution_prune_min=args.contribution_prune_min, background=background,
-                         use_masks=not args.no_masks, filter3d=args.filter3d, filter3d_every=args.filter3d_every)
     splats, log = train_scene(data, config, steps=args.steps,
                               init=init, init_count=args.init_count,
                               sh_degree=args.sh_degree, seed=args.seed, eval_every=args.eval_every,

@@ -207,20 +207,27 @@ def test_train_config_validation_messages():
 
 def test_mcmc_and_exchange_refusals():
     from brush_amd import TrainConfig
-    from brush_amd.train_loop import TrainLoop, check_contribution_prune
+    from brush_amd.train_loop import TrainLoop
 
     class Exchange:
         def __init__(self, world):
             self.world = world
 
     cfg = TrainConfig(contribution_prune_at=(10,))
-    assert check_contribution_prune(cfg) == (10,)
-    assert check_contribution_prune(cfg, Exchange(1)) == (10,)
-    assert check_contribution_prune(TrainConfig(strategy="mcmc"), Exchange(4)) == ()  # nothing asked, nothing refused
+    cfg.check()
+    cfg.check(multi_rank=False)
+    assert cfg.check_contribution_prune() == (10,)
+    TrainConfig(strategy="mcmc").check(multi_rank=True)  # nothing asked, nothing refused
+    assert TrainConfig(strategy="mcmc").check_contribution_prune() == ()
     with pytest.raises(ValueError, match="multi-rank exchange"):
-        check_contribution_prune(cfg, Exchange(2))
+        cfg.check(multi_rank=True)
     with pytest.raises(ValueError, match="strategy='mcmc'"):
-        check_contribution_prune(TrainConfig(strategy="mcmc", contribution_prune_at=(10,)))
+        TrainConfig(strategy="mcmc", contribution_prune_at=(10,)).check()
+    # TrainLoop takes multi_rank from its exchange's world size: one rank is let through, as far as the dataset (None)
+    with pytest.raises(AttributeError, match="train"):
+        TrainLoop(None, cfg, steps=20, exchange=Exchange(1), device="cpu")
+    with pytest.raises(ValueError, match="multi-rank exchange"):
+        TrainLoop(None, cfg, steps=20, exchange=Exchange(2))
     # at construction, before anything touches the dataset or a device
     with pytest.raises(ValueError, match="strategy='mcmc'"):
         TrainLoop(None, TrainConfig(strategy="mcmc", contribution_prune_at=(10,)), steps=20)

@@ -142,7 +142,7 @@ def test_refusals_come_before_any_gpu_call():
 
     from brush_amd import Splats
     from brush_amd.train import SplatTrainer, TrainConfig
-    from brush_amd.train_loop import check_filter3d
+    from brush_amd.train_loop import TrainLoop
 
     z = torch.zeros
     cpu_splats = Splats(z((4, 3)), z((4, 1, 3)), z((4, 4)), z((4,)), z((4, 3)))
@@ -171,10 +171,15 @@ def test_refusals_come_before_any_gpu_call():
         world = 2
 
     with pytest.raises(ValueError, match="multi-rank"):
-        check_filter3d(TrainConfig(filter3d=True), Exchange())
-    check_filter3d(TrainConfig(filter3d=False), Exchange())
+        TrainConfig(filter3d=True).check(multi_rank=True)
+    TrainConfig(filter3d=False).check(multi_rank=True)
+    TrainConfig(filter3d=True).check(multi_rank=False)
+    # TrainLoop derives multi_rank from its exchange's world size, before anything touches the dataset or a device
+    with pytest.raises(ValueError, match="multi-rank"):
+        TrainLoop(None, TrainConfig(filter3d=True), steps=20, exchange=Exchange())
     Exchange.world = 1
-    check_filter3d(TrainConfig(filter3d=True), Exchange())
+    with pytest.raises(AttributeError, match="train"):  # one rank is let through, as far as the dataset (None here)
+        TrainLoop(None, TrainConfig(filter3d=True), steps=20, exchange=Exchange(), device="cpu")
 
 
 def test_parser_flags_and_log():

@@ -33,6 +33,11 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 replay of the compositing walk, and pruning by it (brush_amd/contribution.py; build
                                 extension, RadSplat and LightGaussian are the models; also `python -m brush_amd.prune`,
                                 Splats.select, TrainConfig.contribution_prune_at)
+  splat_error_scores / ErrorScoreBuffers / l1_error_map / error_scores_from_aux  <- per-splat image error over a
+                                set of views (a per-pixel error map distributed to the splats by their blending weights,
+                                from a replay of the compositing walk) and densification by it (brush_amd/error_score.py;
+                                build extension, "Revising Densification in Gaussian Splatting" is the model;
+                                TrainConfig.densify_by = "error", `python -m brush_amd.train_loop --densify-by error`)
   filter3d_rates / apply_filter3d / Splats.bake_filter3d  <- the 3D smoothing filter of Mip-Splatting: per-splat
                                 filter lengths from the training views' sampling rates, and the map of log-scales and
                                 raw opacity that applies them (brush_amd/filter3d.py; build extension;
@@ -71,6 +76,7 @@ _POSE_NAMES = ("se3_exp", "apply_delta", "PoseTable")
 _EXPOSURE_NAMES = ("apply_exposure", "ExposureTable")
 _CONTRIBUTION_NAMES = ("Contributions", "ContributionBuffers", "contributions_from_aux", "splat_contributions",
                        "prune_mask")
+_ERROR_SCORE_NAMES = ("ErrorScores", "ErrorScoreBuffers", "l1_error_map", "error_scores_from_aux", "splat_error_scores")
 
 
 def __getattr__(name):
@@ -89,6 +95,9 @@ def __getattr__(name):
     if name in _CONTRIBUTION_NAMES:
         from . import contribution as _contribution
         return getattr(_contribution, name)
+    if name in _ERROR_SCORE_NAMES:
+        from . import error_score as _error_score
+        return getattr(_error_score, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

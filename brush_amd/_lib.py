@@ -221,6 +221,8 @@ _SYMBOLS = [
      [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.POINTER(BrushUndistort), _P]),
     ("brush_render_contributions", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P]),
+    ("brush_l1_error_map", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("brush_render_error_scores", C.c_int, [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, C.c_uint32, _P]),
     ("brush_filter3d_view_chunk", C.c_uint32, []),
     ("brush_filter3d_rates", C.c_int,
      [_P, C.c_uint32, _P, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),

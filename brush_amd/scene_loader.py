@@ -114,6 +114,11 @@ class SceneLoader:
         loader was built with use_masks=False).  At the current level's size."""
         return self._masks[i]
 
+    def view_at(self, i: int) -> Tuple[object, torch.Tensor, Optional[torch.Tensor]]:
+        """(view i's Camera, its image, its loss mask or None) as resident on the device at the current level, without a
+        draw: the rng is not touched."""
+        return self.scene.views[i].camera, self._images[i], self._masks[i]
+
     def next_batch(self) -> Tuple[object, torch.Tensor]:
         """(SceneView, its image as a uint8 [h,w,3|4] device tensor)."""
         _, view, image = self.next_indexed()

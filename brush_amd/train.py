@@ -144,6 +144,27 @@ class TrainConfig:
     filter3d: bool = False
     filter3d_every: int = 100
     filter3d_variance: float = 0.2
+    # Build extension: error-driven densification (brush_amd/error_score.py; Rota Bulo et al., "Revising Densification
+    # in Gaussian Splatting", ECCV 2024, is the model).  densify_by: "grad" is the reference's rule (mean screen-space
+    # gradient norm >= densify_grad_thresh), launch for launch and bit for bit.  "error": refine_splats clones and splits
+    # the splats whose score (SplatTrainer.set_densify_scores; the training loop hands it each splat's largest share,
+    # over densify_error_views training views, of the per-pixel L1 error distributed by blending weight, in front of
+    # every refining step) is >= densify_error_thresh, in units of pixels of full error in the splat's worst view (1.0:
+    # a hyper-parameter default, not a measured number); at most ceil(densify_growth * N) of them per refinement, the
+    # largest scores first (0.05 is the paper's cap), and never beyond densify_max_splats.  densify_error_views: views
+    # per score pass, 0 = every training view (32: an unmeasured default).  Small / large -> clone / split, the prunes and
+    # the opacity reset stay as they are; the step then skips the gradient statistics.  revised_opacity (the same
+    # paper's correction, gsplat's revised_opacity; under either densify_by): every clone source and split source and
+    # the rows appended for them get the opacity 1 - sqrt(1 - o) of the source's post-step opacity o, so that the pair
+    # covers what the source covered.  "error" is single-GPU and not with strategy "mcmc", pose_opt or exposure_opt
+    # (the score pass would have to render through the refined pose or map).  The defaults are the run without the
+    # options, bit for bit.  DESIGN §8 row 18.
+    densify_by: str = "grad"
+    densify_error_thresh: float = 1.0
+    densify_error_views: int = 32
+    densify_growth: float = 0.05
+    densify_max_splats: Optional[int] = None
+    revised_opacity: bool = False
 
     def check(self, multi_rank: bool = False):
         """A ValueError naming the first thing wrong with the configuration, before anything touches a dataset or a
@@ -170,6 +191,34 @@ class TrainConfig:
             raise ValueError("TrainConfig.filter3d cannot be combined with a multi-rank exchange: the 3D filter is "
                              "single-GPU")
         check_background(self.background)
+        self.check_densify()
+        if self.densify_by == "error":
+            # what the score pass cannot serve, in the order it is refused in
+            for on, what in ((self.strategy == "mcmc", "strategy='mcmc': a fixed budget relocates splats instead of "
+                                                       "densifying them"),
+                             (multi_rank, "a multi-rank exchange: the score pass is single-GPU"),
+                             (self.pose_opt, "pose_opt: the score pass would have to render through the refined poses"),
+                             (self.exposure_opt, "exposure_opt: the score pass would have to render through the "
+                                                 "refined exposure maps")):
+                if on:
+                    raise ValueError(f"TrainConfig.densify_by='error' cannot be combined with {what}")
+
+    def check_densify(self):
+        """A ValueError naming what is wrong with the densification fields."""
+        def number(x):
+            return not isinstance(x, bool) and isinstance(x, (int, float))
+
+        if self.densify_by not in ("grad", "error"):
+            raise ValueError(f"TrainConfig.densify_by must be 'grad' or 'error', got {self.densify_by!r}")
+        t, v, g, m = self.densify_error_thresh, self.densify_error_views, self.densify_growth, self.densify_max_splats
+        if not number(t) or not (math.isfinite(t) and t >= 0.0):
+            raise ValueError(f"TrainConfig.densify_error_thresh must be finite and >= 0, got {t!r}")
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"TrainConfig.densify_error_views must be an integer >= 0, got {v!r}")
+        if not number(g) or not 0.0 < g <= 1.0:  # (a NaN fails too)
+            raise ValueError(f"TrainConfig.densify_growth must be in (0, 1], got {g!r}")
+        if m is not None and (isinstance(m, bool) or not isinstance(m, int) or m < 0):
+            raise ValueError(f"TrainConfig.densify_max_splats must be None or an integer >= 0, got {m!r}")
 
     def check_filter3d(self):
         """A ValueError naming what is wrong with the filter3d fields or their combination with the strategy."""
@@ -254,6 +303,36 @@ def quaternion_vec_multiply(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     return torch.cat([rx, ry, rz], dim=1)
 
 
+def densify_candidates(scores: torch.Tensor, n: int, thresh: float, growth: float,
+                       max_splats: Optional[int] = None) -> torch.Tensor:
+    """A boolean [N] tensor, True where a splat is densified under TrainConfig.densify_by = "error": score >= thresh (a
+    NaN never passes), and when more than min(ceil(growth n), max_splats - n), clamped at 0, pass, the largest by score
+    among them, ties broken by lower index.  `n`: the current splat count, N.  Pure torch; works on CPU tensors and
+    never synchronises a device."""
+    n = int(n)
+    if scores.dim() != 1 or int(scores.shape[0]) != n:
+        raise ValueError(f"scores must be a [N] = [{n}] tensor, got {tuple(scores.shape)}")
+    budget = int(math.ceil(float(growth) * n))
+    if max_splats is not None:
+        budget = min(budget, int(max_splats) - n)
+    budget = min(max(budget, 0), n)
+    passed = scores >= thresh
+    key = torch.where(passed, scores.to(torch.float64), torch.full_like(scores, -math.inf, dtype=torch.float64))
+    order = torch.sort(key, descending=True, stable=True).indices  # stable: among equals the lower index comes first
+    mask = torch.zeros(n, dtype=torch.bool, device=scores.device)
+    mask[order[:budget]] = passed[order[:budget]]
+    return mask
+
+
+def revised_opacity(raw: torch.Tensor) -> torch.Tensor:
+    """logit(1 - sqrt(1 - sigmoid(raw))): the raw opacity of each of the two splats a clone or a split leaves, such that
+    the pair covers what the source covered, 1 - (1 - o')^2 = o ("Revising Densification in Gaussian Splatting";
+    gsplat's revised_opacity).  Written without the cancellations: 1 - o = sigmoid(-raw), r = sqrt(1 - o),
+    o' = o / (1 + r), logit(o') = log(o' / r)."""
+    r = torch.sqrt(torch.sigmoid(-raw))
+    return torch.log(torch.sigmoid(raw) / (1.0 + r) / r)
+
+
 def l1_ssim_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_weight: float, window: int = 11,
                  grad_scale: float = 1.0, out: Optional[torch.Tensor] = None):
     """(loss [1] device tensor, d loss / d pred [h,w,4]) through brush_l1_ssim_loss.  A torch.uint8 `gt` (a view's
@@ -308,11 +387,13 @@ def optimizer_path(exchange: bool, grad_sync: bool, fused_backward: bool, mcmc: 
 
 class SplatTrainer:
     filter3d: Optional[torch.Tensor] = None  # the 3D filter lengths [N] of set_filter3d, or None
+    densify_scores: Optional[torch.Tensor] = None  # the scores [N] of set_densify_scores, until a refinement takes them
 
     def __init__(self, splats: Splats, config: TrainConfig | None = None):
         self.config = config or TrainConfig()
         self.config.check()
         self.filter3d = None
+        self.densify_scores = None
         self._bg_rng, self._bg_fixed = None, {}  # "random"'s device generator; the fixed colours' device tensors
         dev = splats.means.device
         assert dev.type == "cuda", "brush_amd has no CPU path: the splats must live on the GPU"
@@ -368,6 +449,32 @@ class SplatTrainer:
                 raise ValueError("the 3D filter must be a contiguous float32 [N] tensor on the GPU")
             filter = filter.detach()
         self.filter3d = filter
+
+    def set_densify_scores(self, scores: Optional[torch.Tensor]):
+        """Hands the next refinement its scores under TrainConfig.densify_by = "error" (None: clears them): a float32
+        [N] tensor on the splats' device, one score per splat (error_score.ErrorScoreBuffers.scores), kept by
+        reference.  The refinement consumes and clears them; one that finds none, or scores of another length than the
+        splat count, refuses to run."""
+        if scores is not None:
+            if not isinstance(scores, torch.Tensor) or scores.dim() != 1 or scores.dtype != torch.float32 \
+                    or not scores.is_cuda:
+                raise ValueError("the densification scores must be a float32 [N] tensor on the GPU")
+            scores = scores.detach()
+        self.densify_scores = scores
+
+    def _check_densify_scores(self, n: int):
+        if self.densify_scores is None:
+            raise ValueError("TrainConfig.densify_by is 'error' but the trainer has no scores for this refinement: call "
+                             "set_densify_scores first (train_loop.TrainLoop does)")
+        if int(self.densify_scores.shape[0]) != n:
+            raise ValueError(f"stale densification scores: {int(self.densify_scores.shape[0])} scores for {n} splats; "
+                             "set them for the current splats (set_densify_scores)")
+
+    def will_refine(self) -> bool:
+        """Whether the coming step ends in a refinement (train.rs:361: past the warm-up, before max_refine_step, one
+        step after every multiple of refine_every)."""
+        c = self.config
+        return self.iter < c.max_refine_step and self.iter >= c.warmup_steps and self.iter % c.refine_every == 1
 
     LAZY_TABLE_ROWS = 2048
 
@@ -445,8 +552,15 @@ class SplatTrainer:
         dev = splats.means.device
         post = {"means": splats.means.detach(), "rotation": splats.rotation.detach(), "sh": splats.sh_coeffs.detach(),
                 "opac": splats.raw_opacity.detach(), "scales": splats.log_scales.detach()}
-        grads = self.grad_2d_accum / self.xy_grad_counts.clamp_min(1.0)
-        big_grad = grads >= c.densify_grad_thresh
+        if c.densify_by == "error":  # the scores of set_densify_scores take the gradient statistic's place
+            n = int(post["means"].shape[0])
+            self._check_densify_scores(n)
+            big_grad = densify_candidates(self.densify_scores, n, c.densify_error_thresh, c.densify_growth,
+                                          c.densify_max_splats)
+            self.densify_scores = None
+        else:
+            grads = self.grad_2d_accum / self.xy_grad_counts.clamp_min(1.0)
+            big_grad = grads >= c.densify_grad_thresh
         small = post["scales"].exp().max(dim=1).values < c.densify_size_thresh
         app = {k: [] for k in post}
         clone_inds = torch.nonzero(small & big_grad).squeeze(1)
@@ -469,6 +583,13 @@ class SplatTrainer:
                                                   * cur_scale)
             app["means"].append(cur_means + samples_new)
         new = {k: (torch.cat([post[k]] + app[k], 0) if app[k] else post[k]) for k in post}
+        if c.revised_opacity and (clone_inds.numel() > 0 or ns > 0):
+            # sources and the rows appended for them (clones, then splits: the order of `sources`), from the sources'
+            # post-step opacities (`new` is a fresh tensor here: something was appended)
+            sources = torch.cat([clone_inds, split_inds])
+            revised = revised_opacity(post["opac"][sources])
+            new["opac"][sources] = revised
+            new["opac"][post["opac"].shape[0]:] = revised
         start = new["means"].shape[0]
 
         def prune(mask):
@@ -551,6 +672,14 @@ class SplatTrainer:
                              (exposures is not None, "exposure compensation")):
                 if on:
                     raise ValueError(f"{what} is single-view: it cannot be combined with exchange / grad_sync")
+        if c.densify_by == "error":
+            # what the score pass cannot serve (TrainConfig.check refuses the configured forms of the same rows)
+            for on, what in ((c.strategy == "mcmc", "the mcmc strategy"),
+                             (exchange is not None or grad_sync is not None, "exchange / grad_sync"),
+                             (poses is not None, "pose refinement"),
+                             (exposures is not None, "exposure compensation")):
+                if on:
+                    raise ValueError(f"densify_by='error' cannot be combined with {what}")
         for name, table in (("poses", poses), ("exposures", exposures)):
             if table is not None and view_index is None:
                 raise ValueError(f"{name} needs view_index")
@@ -693,6 +822,9 @@ class SplatTrainer:
         brush_filter3d_apply in front of the forward, which like the backward then works on the effective log-scales
         and opacities, and brush_filter3d_backward on the dense gradients in front of the refinement statistics and
         brush_adam_step on the raw parameters.
+        TrainConfig.densify_by = "error": a refining step (will_refine) needs the scores of set_densify_scores for the
+        current splats and is refused without them before anything is stepped; no step gathers the gradient statistics;
+        refused with strategy "mcmc", `exchange` / `grad_sync`, `poses` and `exposures`.
         Single-view, that is refused with `exchange` / `grad_sync`: the 3D filter, `gt_depth`, strategy "mcmc", `poses`
         and `exposures` (_check_step); TrainConfig.antialiased is refused with `exchange` alone.  The optimizer path
         (optimizer_path): the records path with `exchange`; the separate-call path (backward, then brush_adam_step)
@@ -720,6 +852,8 @@ class SplatTrainer:
                 F3.check_filter(filt, n, means.device)
             except ValueError as e:
                 raise ValueError(f"stale 3D filter: {e}; set one for the current splats (set_filter3d)") from None
+        if c.densify_by == "error" and self.will_refine():
+            self._check_densify_scores(n)  # before anything is stepped: the refinement below would refuse
         stream = _lib.current_stream(means.device)
         norm_rot = self._take_rotation(splats, stream)
         # on the records and fused paths the optimizer runs inside a kernel that sees which splats the step touches
@@ -751,7 +885,7 @@ class SplatTrainer:
                                          scale=depth_scale, offset=depth_offset, alpha_min=c.depth_alpha_min,
                                          mode=c.depth_mode, loss_accum=loss)
             depth_grad = (depth_bufs[1], v_depth)
-        do_refine = self.iter < c.max_refine_step and self.iter >= c.warmup_steps and self.iter % c.refine_every == 1
+        do_refine = self.will_refine()
         pre_step = None
         # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)
         if do_refine and not use_mcmc:
@@ -765,7 +899,8 @@ class SplatTrainer:
                                    float(batch_views))
         if lazy is not None:
             cfg.lazy_sh = C.pointer(lazy)
-        want_stats = self.iter > c.warmup_steps and not use_mcmc  # housekeeping, train.rs:284-316
+        # housekeeping, train.rs:284-316; the error rule does not read the gradient statistics
+        want_stats = self.iter > c.warmup_steps and not use_mcmc and c.densify_by != "error"
         fwd = (u, aux, pred, v_pred)
         with torch.cuda.device(means.device):
             if path == "records":

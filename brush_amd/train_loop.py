@@ -19,6 +19,15 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--downscale-schedule STEP:FACTOR,...] [--num-downscales K] [--resolution-schedule S]
         [--contribution-prune-at STEP,...] [--contribution-prune-min 0.01]
         [--background white|black|random|R,G,B] [--no-masks] [--filter3d] [--filter3d-every 100]
+        [--densify-by grad|error] [--densify-error-thresh 1.0] [--densify-error-views 32] [--densify-growth 0.05]
+        [--max-splats N] [--revised-opacity]
+
+--densify-by error replaces the refinement's gradient rule (TrainConfig.densify_by, brush_amd/error_score.py): in front
+of every refining step the loop renders --densify-error-views training views (0: all), distributes each view's per-pixel
+L1 error to the splats by their blending weights and densifies the splats whose largest share reaches
+--densify-error-thresh, at most --densify-growth of the count per refinement and never beyond --max-splats.
+--revised-opacity gives the two splats a clone or split leaves the opacity 1 - sqrt(1 - o) (under either rule).  The
+log's `error_passes` holds (step, views).
 
 --filter3d trains under Mip-Splatting's 3D smoothing filter (TrainConfig.filter3d, brush_amd/filter3d.py): every splat
 is low-passed at the highest rate any training view sampled it, recomputed every --filter3d-every steps and whenever the
@@ -103,6 +112,8 @@ class TrainLog:
     masked_views: int = 0                         # training views whose loss mask the run used
     filter3d: bool = False                        # TrainConfig.filter3d: trained under the 3D smoothing filter
     filter3d_refreshes: List[int] = field(default_factory=list)  # the steps in front of which the filter was recomputed
+    densify_by: str = "grad"                      # TrainConfig.densify_by as configured
+    error_passes: List[Tuple[int, int]] = field(default_factory=list)  # (step, views): the score passes that ran
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
@@ -113,6 +124,7 @@ class TrainLog:
                 "background": list(self.background) if isinstance(self.background, tuple) else self.background,
                 "masked_views": int(self.masked_views), "filter3d": bool(self.filter3d),
                 "filter3d_refreshes": [int(s) for s in self.filter3d_refreshes],
+                "densify_by": self.densify_by, "error_passes": [[int(s), int(v)] for s, v in self.error_passes],
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -202,7 +214,16 @@ class TrainLoop:
         self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes,
                             background=self.config.background,
                             masked_views=sum(m is not None for m in self.loader.masks),
-                            filter3d=bool(self.config.filter3d))
+                            filter3d=bool(self.config.filter3d), densify_by=self.config.densify_by)
+        # error-driven densification: a host generator of its own picks the views of a score pass (the loader's draw
+        # order does not change), and a fixed background colour goes to the device here, once
+        self._score_rng, self._score_bg = None, None
+        if self.config.densify_by == "error":
+            from .compose import as_background
+
+            self._score_rng = np.random.default_rng([int(seed), 0x65727273])
+            bg = "black" if self.config.background == "random" else self.config.background
+            self._score_bg = as_background(bg, self.device)
         self._t0 = time.perf_counter()
         self._eval_seconds = 0.0
         self._last = (0, 0.0)  # (step, training seconds) of the previous eval row
@@ -229,9 +250,31 @@ class TrainLoop:
             self.refresh_filter3d()
         return self.splats.bake_filter3d(self.trainer.filter3d)
 
+    def score_errors(self) -> int:
+        """One score pass of error-driven densification: densify_error_views distinct training views (0: all of them),
+        chosen with a generator of the loop's own, at the loader's current level; each is rendered (the baked splats
+        under TrainConfig.filter3d: their rows are the raw splats' rows) in the config's antialiased mode and over its
+        background ("random" scores over black, as the evals do), its L1 error map under its loss mask is distributed
+        to the splats (error_score.splat_error_scores) and the trainer receives every splat's largest share
+        (SplatTrainer.set_densify_scores).  Appends (step, views) to the log's `error_passes` and returns the number of
+        views.  Launches only: no upload, no read-back, no synchronisation."""
+        from .error_score import splat_error_scores
+
+        total, k = len(self.loader), self.config.densify_error_views
+        k = total if k == 0 else min(k, total)
+        chosen = sorted(int(i) for i in self._score_rng.choice(total, size=k, replace=False))
+        views = [self.loader.view_at(i) for i in chosen]
+        self.trainer.sync(self.splats)
+        bufs = splat_error_scores(self.baked_splats(), views, antialiased=self.config.antialiased,
+                                  background=self._score_bg, use_masks=self.config.use_masks)
+        self.trainer.set_densify_scores(bufs.scores("max"))
+        self.log.error_passes.append((self.done, k))
+        return k
+
     def step(self):
         """One training iteration on a random view, at the level TrainConfig.downscale_at gives for this step; its loss
-        lands in the device log.  With TrainConfig.filter3d the 3D filter is recomputed in front of the step (from the
+        lands in the device log.  With TrainConfig.densify_by = "error" a refining step (SplatTrainer.will_refine) is
+        preceded by score_errors().  With TrainConfig.filter3d the 3D filter is recomputed in front of the step (from the
         training views at full size and at the dataset's poses, refresh_filter3d) before the first step, after any step
         that changed the splat count (refinement, contribution prune) and otherwise when the step index is a multiple
         of filter3d_every; no step synchronises because of the filter."""
@@ -244,6 +287,8 @@ class TrainLoop:
         if factor != self.loader.downscale:  # a level switch: launches only (SceneLoader.set_downscale)
             self.loader.set_downscale(factor)
             self.log.downscales.append((self.done, factor))
+        if self.config.densify_by == "error" and self.trainer.will_refine():
+            self.score_errors()
         # every option that is off hands the step None (or a neutral value): that is the step without the option.  The
         # drawn view's resident depth map (with depth supervision on) and loss mask go with the step where the view has
         # them; views without one train as before.
@@ -475,6 +520,19 @@ def parser():
                    help="train under Mip-Splatting's 3D smoothing filter; evals and --export use the baked splats")
     p.add_argument("--filter3d-every", type=int, default=TrainConfig.filter3d_every, metavar="K",
                    help="--filter3d: recompute the filter every K steps (and whenever the splat count changed)")
+    p.add_argument("--densify-by", choices=("grad", "error"), default="grad",
+                   help="what refinement clones and splits on: the screen-space gradient statistic, or each splat's "
+                        "share of the per-pixel image error over a set of training views")
+    p.add_argument("--densify-error-thresh", type=float, default=TrainConfig.densify_error_thresh, metavar="T",
+                   help="--densify-by error: densify at this many pixels of full error in a splat's worst view")
+    p.add_argument("--densify-error-views", type=int, default=TrainConfig.densify_error_views, metavar="V",
+                   help="--densify-by error: training views per score pass (0: all)")
+    p.add_argument("--densify-growth", type=float, default=TrainConfig.densify_growth, metavar="G",
+                   help="--densify-by error: densify at most this fraction of the splats per refinement")
+    p.add_argument("--max-splats", type=int, default=None, metavar="N",
+                   help="--densify-by error: never grow beyond this many splats")
+    p.add_argument("--revised-opacity", action="store_true",
+                   help="give the two splats a clone or split leaves the opacity 1 - sqrt(1 - o) of their source")
     p.add_argument("--no-undistort", action="store_true",
                    help="train on views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
                         "loaded, as if they were pinhole, instead of undistorting them first")
@@ -498,7 +556,10 @@ def main(argv=None) -> int:
                              depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
                              downscale_schedule=schedule, contribution_prune_at=prune_at,
                              contribution_prune_min=args.contribution_prune_min, background=background,
-                             use_masks=not args.no_masks, filter3d=args.filter3d, filter3d_every=args.filter3d_every)
+                             use_masks=not args.no_masks, filter3d=args.filter3d, filter3d_every=args.filter3d_every,
+                             densify_by=args.densify_by, densify_error_thresh=args.densify_error_thresh,
+                             densify_error_views=args.densify_error_views, densify_growth=args.densify_growth,
+                             densify_max_splats=args.max_splats, revised_opacity=args.revised_opacity)
         config.check()  # the configuration the run trains with, before the dataset is loaded
     except ValueError as e:
         p.error(str(e))
@@ -566,7 +627,10 @@ def main(argv=None) -> int:
     if args.json:
         res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree,
                "antialiased": bool(args.antialiased), "strategy": args.strategy,
-               "cap_max": int(args.cap_max) if args.strategy == "mcmc" else None}
+               "cap_max": int(args.cap_max) if args.strategy == "mcmc" else None,
+               "densify_error_thresh": float(args.densify_error_thresh),
+               "densify_error_views": int(args.densify_error_views), "densify_growth": float(args.densify_growth),
+               "max_splats": args.max_splats, "revised_opacity": bool(args.revised_opacity)}
         res.update(log.to_json())
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)

@@ -696,6 +696,39 @@ int brush_render_contributions(const BrushUniforms *h_uniforms, const BrushAux *
                                uint32_t *max_bits /* [N] */, uint64_t *counts /* [N,3]: sum_q24, hits, stops */,
                                uint32_t *mismatch /* [1] or NULL */, uint32_t n, brush_stream_t stream);
 
+/* ---- per-splat image error (build extension; error-driven densification, Rota Bulo et al., "Revising Densification in
+ *      Gaussian Splatting", ECCV 2024) ------------------------------------------------------------------------------ */
+/* brush_l1_error_map: the per-pixel error the densification score distributes, one pass, a lane per pixel:
+ *   out[p] = min(((|dr| + |dg|) + |db|) * (1.0f / 3.0f), 1.0f),   d = pred[p].rgb - gt[p].rgb
+ * in exactly this association, every operation one f32 operation (no product feeds an add), so a float32 restatement
+ * gives the same bits.  pred [h][w][4] f32 (channels 0..2 are used, as rendered); gt [h][w][Cg], Cg = gt_channels = 3 or
+ * 4 (an alpha channel is not read), u8 (BRUSH_EVAL_GT_U8, read as (float)b / 255.0f with an IEEE division) or f32
+ * (BRUSH_EVAL_GT_F32); mask [h][w] u8 or NULL: where mask[p] == 0, out[p] = +0.0f (by selection).  A NaN difference
+ * gives 1.0f (fminf).  out [h][w] f32, row pitch w.  pred 16-byte aligned, an f32 gt and out 4-byte; w h in [1, 2^28).
+ * brush_render_error_scores: replays the compositing walk of a FINISHED forward over the tile lists it left in the aux
+ * (projected_splats, tile_bins, compact_gid_from_isect, global_from_compact_gid, num_visible: what
+ * brush_render_contributions reads, without final_index) and distributes a per-pixel error to the splats by their
+ * blending weights.  error_map [h][w] f32, row pitch w (NOT tile-padded), 4-byte aligned; every pixel reads its value
+ * once and clamps it, e = min(max(E, 0), 1): a NaN and every negative value count as 0, everything above 1 as 1.  For
+ * every splat the walk meets, into the row of its GLOBAL id g < n:
+ *   view_err[g] += sum over the pixels the forward ADDED the splat to of (uint32) rint((fac e) 2^24)
+ * with fac = alpha T as in brush_render_contributions (fac e: one f32 product; the scale is exact; ties to even), as
+ * exact 64-bit integers: view_err / 2^24 is the splat's share of the view's summed error, "pixels of full error".  The
+ * stop quirk is walked as the forward walks it (T evolves identically) and contributes nothing.  With an all-ones map
+ * view_err is bit for bit counts[g][0] of brush_render_contributions.  The entry only ACCUMULATES into view_err [N]
+ * (8-byte aligned), which the caller zeroes; the adds are order-independent integers, so the same inputs give the same
+ * bits on every run, in both BRUSH_AUX_DETERMINISTIC settings and with BRUSH_AUX_ANTIALIASED.
+ * Both: a NULL required pointer, a misaligned one, tile_bounds that do not belong to img_size or any other gt_dtype /
+ * gt_channels return BRUSH_ERR_INVALID_ARG before any device work; brush_render_error_scores with n == 0 returns
+ * BRUSH_OK and launches nothing.  Device pointers except the two structs.  No workspace, no allocation, no
+ * synchronisation: graph-capturable. */
+int brush_l1_error_map(const float *pred, const void *gt, uint32_t gt_dtype, uint32_t gt_channels,
+                       const uint8_t *mask /* [h,w] or NULL */, float *out /* [h,w] */, uint32_t w, uint32_t h,
+                       brush_stream_t stream);
+int brush_render_error_scores(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                              const float *error_map /* [h,w] */, uint64_t *view_err /* [N] */, uint32_t n,
+                              brush_stream_t stream);
+
 /* ---- 3D smoothing filter (build extension; Mip-Splatting, Yu et al. 2024, is the model) ------------------------- */
 /* The world-space half of Mip-Splatting: every splat is low-passed at the highest rate any training view sampled it.
  * A splat carries a filter length f; the renderer sees the covariance Sigma + f^2 I and the opacity scaled by

@@ -42,6 +42,11 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 filter lengths from the training views' sampling rates, and the map of log-scales and
                                 raw opacity that applies them (brush_amd/filter3d.py; build extension;
                                 TrainConfig.filter3d, `python -m brush_amd.train_loop --filter3d`)
+  TsdfVolume / Mesh / mesh_to_ply / mesh_from_ply / default_bounds / grid_for  <- mesh export: rendered depth maps
+                                fused into a dense TSDF volume of integers (order-independent, bitwise repeatable) and
+                                an indexed, watertight triangle mesh cut out of it by marching tetrahedra
+                                (brush_amd/tsdf.py, brush_amd/mesh.py; build extension, the TSDF exports of 2DGS, GOF
+                                and nerfstudio are the models; also `python -m brush_amd.mesh`)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -77,6 +82,9 @@ _EXPOSURE_NAMES = ("apply_exposure", "ExposureTable")
 _CONTRIBUTION_NAMES = ("Contributions", "ContributionBuffers", "contributions_from_aux", "splat_contributions",
                        "prune_mask")
 _ERROR_SCORE_NAMES = ("ErrorScores", "ErrorScoreBuffers", "l1_error_map", "error_scores_from_aux", "splat_error_scores")
+_TSDF_NAMES = ("TsdfVolume", "TsdfArrays")
+# (brush_amd.mesh is a command line too: imported on first use, as brush_amd.eval is)
+_MESH_NAMES = ("Mesh", "mesh_to_ply", "mesh_from_ply", "default_bounds", "grid_for")
 
 
 def __getattr__(name):
@@ -98,6 +106,12 @@ def __getattr__(name):
     if name in _ERROR_SCORE_NAMES:
         from . import error_score as _error_score
         return getattr(_error_score, name)
+    if name in _TSDF_NAMES:
+        from . import tsdf as _tsdf
+        return getattr(_tsdf, name)
+    if name in _MESH_NAMES:
+        from . import mesh as _mesh
+        return getattr(_mesh, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

@@ -121,6 +121,19 @@ class BrushFilterView(C.Structure):
     ]
 
 
+class BrushTsdfGrid(C.Structure):
+    """The voxel grid of the brush_tsdf_* entries (include/brush_hip.h: BrushTsdfGrid), 32 bytes."""
+    _fields_ = [
+        ("origin", C.c_float * 3), ("voxel", C.c_float), ("trunc", C.c_float),
+        ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32),
+    ]
+
+
+class BrushTsdfViewData(C.Structure):
+    """The device pointers of one view of brush_tsdf_integrate (include/brush_hip.h: BrushTsdfViewData)."""
+    _fields_ = [("img", C.c_void_p), ("depth", C.c_void_p), ("mask", C.c_void_p)]
+
+
 class BrushError(RuntimeError):
     pass
 
@@ -228,6 +241,13 @@ _SYMBOLS = [
      [_P, C.c_uint32, _P, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),
     ("brush_filter3d_apply", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P]),
     ("brush_filter3d_backward", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P]),
+    ("brush_tsdf_integrate", C.c_int,
+     [C.POINTER(BrushTsdfGrid), _P, _P, C.POINTER(BrushTsdfViewData), C.c_uint32, C.c_float, C.c_float, C.c_float,
+      _P]),
+    ("brush_tsdf_mesh_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("brush_tsdf_mesh_count", C.c_int, [C.POINTER(BrushTsdfGrid), _P, C.c_uint32, _P, _P, C.c_size_t, _P]),
+    ("brush_tsdf_mesh_emit", C.c_int,
+     [C.POINTER(BrushTsdfGrid), _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

@@ -778,6 +778,96 @@ int brush_filter3d_apply(const float *log_scales, const float *raw_opacity, cons
 int brush_filter3d_backward(const float *log_scales, const float *raw_opacity, const float *filter, uint32_t n,
                             float *v_scales, float *v_opac, brush_stream_t stream);
 
+/* ---- mesh export (build extension; KinectFusion's volumetric fusion, Curless & Levoy 1996, and the TSDF mesh
+ *      exports of 2DGS / GOF / nerfstudio are the models) ------------------------------------------------------------ */
+/* Rendered depth maps are fused into a dense truncated signed distance volume, and an indexed triangle mesh is cut
+ * out of it by marching tetrahedra.  Every sum is an integer that one lane owns: no atomics, no float accumulation
+ * across views, so a volume's bits depend on neither the view order, the views per launch nor the launch shape, and
+ * the mesh arrays (not only the sets) are the same on every run.
+ * The grid: nx ny nz voxels, each side in [1, BRUSH_TSDF_MAX_SIDE], nx ny nz <= BRUSH_TSDF_MAX_VOXELS, x fastest;
+ * voxel (i, j, k) has the linear index (k ny + j) nx + i and its centre at origin + (idx + 0.5) voxel, in f32
+ *   x = origin[0] + ((float)i + 0.5f) * voxel      (one product, one sum; y z likewise).
+ * voxel and trunc must be finite and > 0.
+ * The volume: BRUSH_TSDF_PLANES planes of nx ny nz 32-bit words each, one after the other (SoA, so that a wave reads
+ * and writes whole lines of one plane), 16-byte aligned:
+ *   plane 0  count      u32   the views that observed the voxel
+ *   plane 1  sdf_sum    i32   the sum of their truncated distances, each quantised to [-32767, 32767]
+ *   plane 2-4 rgb_sum   u32   the sums of the 8-bit colours the views near the surface saw (r, g, b)
+ *   plane 5  rgb_count  u32   the number of those views
+ * A fresh volume is all zero (the caller's memset). */
+#define BRUSH_TSDF_MAX_SIDE 2048u
+#define BRUSH_TSDF_MAX_VOXELS (1u << 28)
+#define BRUSH_TSDF_PLANES 6u
+#define BRUSH_TSDF_MAX_VIEWS 16u /* views of one brush_tsdf_integrate call */
+typedef struct BrushTsdfGrid {
+    float origin[3];
+    float voxel;
+    float trunc;
+    uint32_t nx, ny, nz;
+} BrushTsdfGrid;
+/* What one view of brush_tsdf_integrate reads, all DEVICE pointers: the raw render img [h][w][4] f32 (premultiplied
+ * colour and alpha, as brush_render_forward_depth leaves it; 16-byte aligned), its accumulated depth [h][w] f32 and a
+ * mask [h][w] u8 or NULL (0 = ignore the pixel); h w are the sizes of the view's record. */
+typedef struct BrushTsdfViewData {
+    const float *img;
+    const float *depth;
+    const uint8_t *mask;
+} BrushTsdfViewData;
+/* Fuses num_views views, 1 <= num_views <= BRUSH_TSDF_MAX_VIEWS, into the volume with one launch: one lane owns one
+ * voxel, reads its six words once, goes through the views in registers and writes the words it changed once.  views:
+ * a DEVICE array of records (staged through LDS); h_data: a HOST array of the views' pointers (copied into the launch).
+ * Per voxel centre x and view, every operation one f32 operation, no contraction, IEEE divisions:
+ *   p = W x + t, rows summed as brush_filter3d_rates sums them;      skip unless p.z > near_z
+ *   u = (fx p.x) / p.z + cx,   v = (fy p.y) / p.z + cy
+ *   pixel (floorf(u), floorf(v));                                     skip unless 0 <= floor u < w, 0 <= floor v < h
+ *                                                                     skip if the mask is 0 there
+ *   a = img.w;                                                        skip unless a >= alpha_min
+ *   d = depth / a;                                                    skip unless 0 < d <= max_depth
+ *   s = d - p.z;                                                      skip unless s >= -trunc
+ *   count += 1;   sdf_sum += (int) rintf(fminf(1.0f, s / trunc) * 32767.0f)
+ *   if |s| <= trunc:   rgb_sum[c] += (uint) rintf(255.0f * fminf(fmaxf(img[c] / a, 0.0f), 1.0f));   rgb_count += 1
+ * so free space in front of a surface is carved (+32767 per view) and space more than trunc behind it stays
+ * unobserved.  alpha_min must be finite and > 0, near_z finite and >= 0, max_depth > 0 (+inf: no limit).  A NULL
+ * required pointer, a misaligned one, a grid over the limits, a bad scalar or a view count outside its range return
+ * BRUSH_ERR_INVALID_ARG before any device work.  No workspace, no allocation, no synchronisation. */
+int brush_tsdf_integrate(const BrushTsdfGrid *h_grid, uint32_t *volume, const BrushFilterView *views,
+                         const BrushTsdfViewData *h_data, uint32_t num_views, float alpha_min, float max_depth,
+                         float near_z, brush_stream_t stream);
+/* The mesh: marching tetrahedra on the lattice of voxel centres.  A cell is the cube between lattice point (i, j, k)
+ * and (i+1, j+1, k+1), corner c = bit 0: +x, bit 1: +y, bit 2: +z; it is cut into the six tetrahedra of the Kuhn
+ * decomposition around the diagonal corner 0 - corner 7: tetrahedron number t = 0..5 is (0, 1 << a, 1 << a | 1 << b,
+ * 7) for the t-th permutation (a, b, c) of the axes in lexicographic order.  The decomposition is the same in every
+ * cell, so neighbours agree on the face diagonals and the surface has no cracks.  A lattice point is VALID when
+ * count >= min_views and INSIDE when sdf_sum < 0 (0 is outside).  Every lattice point owns the 7 edges to the points
+ * at offset code e + 1 (bits as the corners), e = 0..6 its SLOT; an edge is ACTIVE when its far end is in the grid,
+ * both ends are valid and exactly one is inside.  Vertices: one per active edge, ordered by owner's linear index,
+ * then slot.  With m = (float)sdf_sum / (float)count at both ends and w = m0 / (m0 - m1):
+ *   x = fmaf(((float)i + 0.5f) + w * (float)di, voxel, origin[0])    (y z likewise; the one fused operation: a vertex
+ *                                                                     is then within 1 ulp or so of its exact position)
+ *   colour[c] = (u8) rintf(fminf(fmaxf(c0 + w * (c1 - c0), 0), 255)),  c_e = (float)rgb_sum[c] / (float)rgb_count
+ * where an end with rgb_count == 0 takes the other end's colour and two such ends give 128.  Faces: a cell takes part
+ * when its 8 corners are valid; faces are ordered by cell (the linear index of its corner 0), then tetrahedron, then
+ * triangle.  Of a tetrahedron (t0, t1, t2, t3) with inside vertices I and outside vertices O, both ascending in the
+ * position within the tetrahedron, and (p, q) the vertex on the edge between p and q:
+ *   |I| = 1: (i, o0) (i, o1) (i, o2)         |I| = 3: (i0, o) (i1, o) (i2, o)
+ *   |I| = 2: (i0, o0) (i0, o1) (i1, o1)  and  (i0, o0) (i1, o1) (i1, o0)
+ * and the last two vertices of a triangle are swapped when its normal at the edge midpoints points from the outside
+ * vertices' centroid to the inside ones': normals point towards positive distance, at the cameras.  The table of the
+ * 6 x 16 cases is generated from this rule at compile time.
+ * brush_tsdf_mesh_count: four launch groups — the edge masks and counts per lattice point, their scan, the triangle
+ * counts per cell, their scan — and totals[0] = V, totals[1] = F (DEVICE, 2 words), which the caller reads back to
+ * size the outputs.  brush_tsdf_mesh_emit, with the SAME grid, volume, min_views and workspace contents: the vertex
+ * kernel and the face kernel.  vertices [V][3] f32, colors [V][3] u8, faces [F][3] u32, all device; V == 0 or F == 0
+ * skips that launch (the pointers may then be NULL).  The workspace (brush_tsdf_mesh_workspace_size, 256-byte aligned)
+ * carries the masks and offsets from count to emit.  min_views >= 1.  Invalid arguments as above; a small workspace is
+ * BRUSH_ERR_WORKSPACE_SMALL.  No allocation, no synchronisation. */
+int brush_tsdf_mesh_workspace_size(uint32_t nx, uint32_t ny, uint32_t nz, size_t *bytes);
+int brush_tsdf_mesh_count(const BrushTsdfGrid *h_grid, const uint32_t *volume, uint32_t min_views, uint32_t *totals,
+                          void *workspace, size_t workspace_bytes, brush_stream_t stream);
+int brush_tsdf_mesh_emit(const BrushTsdfGrid *h_grid, const uint32_t *volume, uint32_t min_views, uint32_t num_vertices,
+                         uint32_t num_faces, float *vertices, uint8_t *colors, uint32_t *faces, void *workspace,
+                         size_t workspace_bytes, brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

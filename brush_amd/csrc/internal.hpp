@@ -45,6 +45,16 @@ hipError_t launch_tile_bin_edges(const uint32_t *sorted_tile_ids, const uint32_t
                                  uint32_t cap, uint32_t *tile_bins, const uint32_t *perm,
                                  const uint32_t *gid_unsorted, uint32_t *gid_sorted, hipStream_t s);
 
+// radix_sort.hip
+// The tile sort: sort_launch's arguments with edge_keys = num_tiles, same outputs and workspace.  In the default mode
+// (compact gids as values, keys_out == nullptr, edges given), with the fused launch shape and a tile id of 9 to 16
+// significant bits (257 to 65 536 tiles) it is three launches: one count + scatter pair on the id's top 8 bits, then
+// one workgroup per bucket orders its bucket by the bits below and stores the bin edges of its tiles.  Anything else
+// runs sort_launch.
+hipError_t tile_sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
+                            const uint32_t *d_n, uint32_t max_n, uint32_t bits, void *ws, hipStream_t s, uint32_t *edges,
+                            uint32_t num_tiles);
+
 // rasterize.hip (forward), rasterize_bwd.hip (backward, zero-fill); raster_common.hpp, raster_zero_fill.hpp
 // bin_edges != nullptr: the tile sort's last pass left (~start, end) per tile there (sort_launch: edges) instead of a
 // GetTileBinEdges launch; the kernel decodes them and writes tile_bins (every tile) for the aux / the backward.

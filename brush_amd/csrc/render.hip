@@ -277,9 +277,12 @@ static int render_forward_impl(const BrushUniforms *h_uniforms, const float *mea
     // three or more passes, i.e. more than 65 535 tiles, the ping-pong also routes an intermediate pass through the
     // output buffer, so it is kept then.)
     const bool drop_keys = !det && bits <= 16;
-    BRUSH_HIP_CHECK(sort_launch(ws.tile_unsorted, det ? nullptr : ws.gid_unsorted, drop_keys ? nullptr : ws.tile_sorted,
-                                det ? aux.isect_unsorted_pos : aux.compact_gid_from_isect, aux.num_intersections, cap,
-                                bits, ws.sort_ws, s, det ? nullptr : ws.bin_edges, num_tiles));
+    // 257 to 65 535 tiles in the default mode with the fused sort shape: one scatter into tile-range buckets, the bins
+    // are ordered and their edges stored by the workgroup that finishes a bucket.
+    BRUSH_HIP_CHECK(tile_sort_launch(ws.tile_unsorted, det ? nullptr : ws.gid_unsorted,
+                                     drop_keys ? nullptr : ws.tile_sorted,
+                                     det ? aux.isect_unsorted_pos : aux.compact_gid_from_isect, aux.num_intersections,
+                                     cap, bits, ws.sort_ws, s, det ? nullptr : ws.bin_edges, num_tiles));
     mark_fwd(s, 1 + BRUSH_STAGE_TILE_SORT);
     if (stop_behind(BRUSH_STAGE_TILE_SORT)) return BRUSH_OK;
     if (det) {

@@ -127,7 +127,7 @@ size_t scan_workspace_bytes(uint32_t n);
 hipError_t scan_launch(const uint32_t *in, uint32_t *out, uint32_t n, const uint32_t *d_valid_n,
                        uint32_t *d_total, uint32_t cap, uint32_t *d_overflow, void *ws, hipStream_t s);
 
-// radix_sort.hip
+// radix_sort.hip (sort_common.hpp)
 size_t sort_workspace_bytes(uint32_t max_n);
 // vals_in == nullptr sorts the positions 0..n-1 themselves (argsort proper).
 // edges != nullptr (zero-initialised [edge_keys][2], keys < edge_keys): the last pass also records the run of every
@@ -138,6 +138,7 @@ size_t sort_workspace_bytes(uint32_t max_n);
 hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
                        uint32_t *vals_out, const uint32_t *d_n, uint32_t max_n, uint32_t bits,
                        void *ws, hipStream_t s, uint32_t *edges = nullptr, uint32_t edge_keys = 0);
+// depth_sort.hip (sort_common.hpp)
 // The depth sort: all 32 bits of the keys, same outputs and workspace as sort_launch.  Clouds of up to 2^20 splats
 // (depth_sort_uses_buckets, chosen from max_n like the launch shapes) are partitioned by ONE count + scatter pair into
 // 256 key-range buckets around splitters from a sorted sample, and a third launch finishes every bucket inside one

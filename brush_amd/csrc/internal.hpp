@@ -45,7 +45,7 @@ hipError_t launch_tile_bin_edges(const uint32_t *sorted_tile_ids, const uint32_t
                                  uint32_t cap, uint32_t *tile_bins, const uint32_t *perm,
                                  const uint32_t *gid_unsorted, uint32_t *gid_sorted, hipStream_t s);
 
-// radix_sort.hip
+// tile_sort.hip (sort_common.hpp)
 // The tile sort: sort_launch's arguments with edge_keys = num_tiles, same outputs and workspace.  In the default mode
 // (compact gids as values, keys_out == nullptr, edges given), with the fused launch shape and a tile id of 9 to 16
 // significant bits (257 to 65 536 tiles) it is three launches: one count + scatter pair on the id's top 8 bits, then

@@ -1,4 +1,5 @@
-// radix_sort.hip — stable LSD radix argsort of u32 key/value pairs (replaces crates/brush-sort).
+// radix_sort.hip — stable LSD radix argsort of u32 key/value pairs (replaces crates/brush-sort), and the count +
+// scatter pair that partitions the keys for the two bucket sorts (sort_partition_launch; depth_sort.hip, tile_sort.hip).
 //
 // Reference: radix_argsort() crates/brush-sort/src/lib.rs:32-147 — FidelityFX-style, 4 bits per
 // pass, 5 launches per pass (count / reduce / scan / scan_add / scatter), element count read
@@ -7,13 +8,12 @@
 // gfx950 design: 8-bit digits (half the passes), 1024-thread workgroups (16 waves), tiles of
 // 1024 x {1,2,4,8,16} keys chosen ON THE DEVICE from *d_n: at most 128 tiles while that fits (a 103 k-key
 // sort: 101 tiles of 1024 keys, a 419 k-key sort: 103 of 4096), 16384-key tiles when the sort is large.
-//   k_upsweep   : per-wave LDS histograms -> counts of the tile's 256 digits
-//   k_scan      : (large sorts only) one block per digit scans counts[digit][*] over the tiles
-//   k_downsweep : every wave ranks its contiguous chunk with ballot match-any masks (8 x v_cmp per
+//   k_sort_upsweep   : per-wave LDS histograms -> counts of the tile's 256 digits
+//   k_sort_scan      : (large sorts only) one block per digit scans counts[digit][*] over the tiles
+//   k_sort_downsweep : every wave ranks its contiguous chunk with ballot match-any masks (8 x v_cmp per
 //                 key on 64-bit masks, the lowest peer lane bumps the wave's private LDS counter),
 //                 16-wave combine, then the pairs are REORDERED BY DIGIT IN LDS and written out so
-//                 that consecutive lanes write consecutive addresses of a digit run (round 1 scattered
-//                 one dword per lane into 256 runs: 2.1x write amplification at the HBM counters).
+//                 that consecutive lanes write consecutive addresses of a digit run.
 // Two launch shapes, chosen on the host from max_n:
 //   * FUSED (max_n <= 512 tiles of 16384 keys, i.e. the reference's 8.39 M intersection cap and below):
 //     2 launches per pass.  counts are laid out [tile][digit]; every downsweep block sums the rows of the
@@ -24,37 +24,19 @@
 //     512-thread scatter workgroups whose 76 KiB of LDS let two of them share a CU (one's loads and stores overlap the
 //     other's ranking): the 18 M-key tile sort of the 4K / 20 M-splat frame 326 -> 246 us (37 % of the HBM peak);
 //     256-thread / 4096-key workgroups (four per CU) measured slower (278 us: shorter digit runs, twice the tiles).
-// The depth sort of clouds up to 2^20 splats does not run these passes: depth_sort_launch (below) scatters once into 256
-// key-range buckets and finishes every bucket inside one workgroup, 3 launches instead of 8.
-// Nor does the tile sort of a frame of 257 to 65 535 tiles in the default mode and the fused shape: tile_sort_launch
-// (below) runs ONE plain count + scatter pair on the top 8 bits of the tile id (the bucket of a key is a shift of the key)
-// and k_tile_bucket_finish orders every bucket by the at most 8 bits below, one workgroup per bucket, streaming the
-// bucket through registers in 8192-pair chunks.  Every tile's run lies inside one bucket, so the bin edges are plain
-// stores of that workgroup (no per-key atomicMax proposals): 3 launches instead of 4, tile sort 27.7 -> 20.5 us in situ at
-// the headline scene (profiles/tile_sort_buckets.json).
-// The element count stays on the device (*d_n): grids are sized for max_n and surplus blocks exit on
-// their first instruction.  Stability: tiles, wave chunks, rounds and lanes are all ranked in index order.
+// The BUCKET instantiations of the two pass kernels take "bucket of key" over sampled splitters as the digit; they and
+// the plain pair with the run starts published are what sort_partition_launch runs (contract: sort_common.hpp).
+// Stability: tiles, wave chunks, rounds and lanes are all ranked in index order.
 // Traffic per pass: 4 B/key (upsweep) + 16 B/pair (downsweep).  Roofline: HBM at large n, kernel
 // boundaries at n ~ 100 k.  The pass structure sorts exactly the reference's 4*ceil(bits/4) low bits.
-#include "common.hpp"
-#include "internal.hpp"
+#include "sort_common.hpp"
 #include "trace.hpp"
 
 namespace brush {
 namespace {
 
-constexpr uint32_t kSortThreads = 1024;
-constexpr uint32_t kSortWaves = kSortThreads / kWave;  // 16
-constexpr uint32_t kSortMaxItems = 16;
-// Measured at the headline scene (sweep of the keys per lane): the 103 k-key depth sort is fastest with 1 key per
-// lane (101 tiles), the 419 k-key tile sort with 4 (103 tiles): ~100 workgroups either way.
-constexpr uint32_t kSortTargetTiles = 128;
-constexpr uint32_t kRadix = 256;
-constexpr uint32_t kMaxTileKeys = kSortThreads * kSortMaxItems;  // 16384
-constexpr uint32_t kFusedMaxTiles = 512;
-// Sorts larger than that (3-launch shape): fixed 8192-key tiles, scattered by 512-thread workgroups of 16 keys per
-// lane whose LDS image (74 KiB) lets TWO of them share a CU, so one's loads and stores overlap the other's ranking.
-constexpr uint32_t kBigTileKeys = 8192;
+// 3-launch shape: the 8192-key tiles are scattered by 512-thread workgroups of 16 keys per lane whose LDS image
+// (74 KiB) lets TWO of them share a CU, so one's loads and stores overlap the other's ranking.
 constexpr uint32_t kBigThreads = 512;
 // FUSED scatter: count-table rows every thread requests before the element count has arrived (4 quarters x 32 rows =
 // the first kSortTargetTiles rows)
@@ -64,31 +46,14 @@ constexpr uint32_t kSpecRows = 16;
 constexpr uint32_t kTableGroups = 8;
 static_assert(kTableGroups * kSpecRows == kSortTargetTiles, "the table always has the speculatively loaded rows");
 
-// Keys per lane for a sort of n keys: smallest power of two K in [1,16] with n / (1024 K) <= 128.
-__host__ __device__ __forceinline__ uint32_t sort_items(uint32_t n) {
-    uint32_t k = 1;
-    while (k < kSortMaxItems && (uint64_t)kSortThreads * k * kSortTargetTiles < n) k <<= 1;
-    return k;
-}
-// Upper bound of the tile count over every n <= max_n.
-inline uint32_t sort_max_tiles(uint32_t max_n) {
-    const uint32_t big = (uint32_t)(((uint64_t)max_n + kMaxTileKeys - 1) / kMaxTileKeys);
-    if (big > kFusedMaxTiles) return (uint32_t)(((uint64_t)max_n + kBigTileKeys - 1) / kBigTileKeys);
-    return big > kSortTargetTiles ? big : kSortTargetTiles;  // n <= 128 * 1024 * K selects K: never more than 128 tiles
-}
-inline bool sort_is_fused(uint32_t max_n) {
-    return (uint32_t)(((uint64_t)max_n + kMaxTileKeys - 1) / kMaxTileKeys) <= kFusedMaxTiles;
-}
-
-// ---- depth sort by key-range buckets (depth_sort_launch) ----
-// Clouds of up to kBucketMaxN splats: ONE count + scatter pair partitions the keys into kRadix key-range buckets (the
-// digit of that pass is "bucket of key": a binary search over 255 splitters picked from a sorted fixed-stride sample),
-// then one workgroup per bucket finishes its bucket in LDS, where a pass costs a barrier and not a kernel boundary.
-constexpr uint32_t kBucketMaxN = 1u << 20;
+// ---- the bucket of a key by sampled splitters (the BUCKET instantiations of the two pass kernels) ----
 constexpr uint32_t kSampleKeys = kSortThreads;  // one sampled key per thread of a count workgroup
-constexpr uint32_t kBucketLdsKeys = 8192;       // pairs a finish workgroup sorts in LDS; larger buckets: global passes
-static_assert(kBucketMaxN / kRadix <= kBucketLdsKeys / 2, "evenly spread keys fill a bucket's LDS at most half");
 static_assert(kBucketMaxN <= kSortThreads * 8 * kSortTargetTiles, "bucket scatter: at most 8 keys per lane");
+
+// Trace tag of a count or scatter launch of the 1024-thread kernels: the pass's shift, the pass number and the sort.
+__device__ __forceinline__ uint32_t sort_pass_tag(uint32_t shift, uint32_t max_n) {
+    return shift | (((shift >> 3) + (max_n > (1u << 21) ? 4u : 0u)) << 24);
+}
 
 // Every thread of a 1024-thread workgroup: sorts a fixed-stride sample of the keys (all of them below kSampleKeys,
 // padded with the largest key) with a bitonic network, steps inside a wave by lane exchange and the rest through `xch`,
@@ -140,7 +105,7 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_upsweep(const uint32_t *_
                                                               uint32_t shift, uint32_t mask,
                                                               uint32_t *__restrict__ counts, uint32_t max_tiles,
                                                               uint32_t *__restrict__ splitters) {
-    BRUSH_KTRACE(kTrSortUp, shift | (((shift >> 3) + (max_n > (1u << 21) ? 4u : 0u)) << 24));
+    BRUSH_KTRACE(kTrSortUp, sort_pass_tag(shift, max_n));
     const uint32_t n = min(*d_n, max_n);
     BRUSH_KTRACE_MARK(1, n);
     const uint32_t items = FUSED ? sort_items(n) : kBigTileKeys / kSortThreads;
@@ -148,7 +113,7 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_upsweep(const uint32_t *_
     const uint32_t tile = blockIdx.x;
     if ((uint64_t)tile * tile_keys >= n) return;
     __shared__ uint32_t hist[kSortWaves][kRadix];
-    for (uint32_t i = threadIdx.x; i < kSortWaves * kRadix; i += kSortThreads) (&hist[0][0])[i] = 0;
+    zero_wave_hist<kSortWaves, kSortThreads>(hist);
     const uint32_t *spl = nullptr;
     if constexpr (BUCKET) {
         __shared__ uint32_t spl_s[kRadix], xch[2][kSampleKeys];
@@ -172,6 +137,7 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_upsweep(const uint32_t *_
     if (threadIdx.x < kRadix) {
         const uint32_t d = threadIdx.x;
         uint32_t c = 0;
+        // the 16-wave total, written out: kernel_diff refused a shared helper (the adds swap their operands)
 #pragma unroll
         for (uint32_t w = 0; w < kSortWaves; w++) c += hist[w][d];
         // FUSED: 16-bit counts (a tile holds at most 16384 keys), row = 128 dwords of digit pairs
@@ -229,24 +195,6 @@ using DownLds = DownLdsT<kMaxTileKeys, kSortWaves, kTableGroups>;
 using DownLdsBig = DownLdsT<kBigTileKeys, kBigThreads / kWave, 1>;
 static_assert(2 * sizeof(DownLdsBig) <= 160 * 1024, "two large-sort workgroups per CU");
 
-// Exclusive scans of two 256-entry arrays held by threads 0..255 (one value of each per thread) behind the same
-// two barriers; all 1024 threads must call.
-__device__ __forceinline__ void block_excl_scan256_pair(uint32_t &a, uint32_t &b, uint32_t (*wave_tot)[2]) {
-    const uint32_t ia = wave_inclusive_scan(a), ib = wave_inclusive_scan(b);
-    if (threadIdx.x < kRadix && lane_id() == 63) {
-        wave_tot[threadIdx.x / kWave][0] = ia;
-        wave_tot[threadIdx.x / kWave][1] = ib;
-    }
-    __syncthreads();
-    uint32_t oa = ia - a, ob = ib - b;
-    for (uint32_t w = 0; w < threadIdx.x / kWave && w < 4; w++) {
-        oa += wave_tot[w][0];
-        ob += wave_tot[w][1];
-    }
-    __syncthreads();
-    a = oa, b = ob;
-}
-
 // Sums of the speculatively loaded count-table rows (thread = (group g8, digit pair dp), rows g8 + 8 j): keys of the
 // pair's digits in the tiles before `tile` / in all `num_tiles` tiles, as packed 16-bit-pair sums of at most 16 rows
 // each (16 * 16384 overflows 16 bits, so the halves are split before they are added up).
@@ -289,8 +237,8 @@ __device__ __forceinline__ void table_sums_to_lds(const uint32_t (&spec)[kSpecRo
     L.part_all()[g8][2 * dp] = ps.all[0], L.part_all()[g8][2 * dp + 1] = ps.all[1];
 }
 
-// BUCKET (depth_sort_launch): the digit of a key is its bucket (bucket_of over `spl`, 256 splitters in LDS that are
-// visible from barrier A on), kept packed four to a register; tile 0 also publishes the 257 bucket offsets.
+// BUCKET (sort_partition_launch by splitters): the digit of a key is its bucket (bucket_of over `spl`, 256 splitters in
+// LDS that are visible from barrier A on), kept packed four to a register; tile 0 also publishes the 257 bucket offsets.
 template <bool FUSED, uint32_t ITEMS, uint32_t THREADS, typename LDS, bool BUCKET = false>
 __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys_in,
                                                const uint32_t *__restrict__ vals_in,
@@ -311,7 +259,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     const uint32_t tile = blockIdx.x;
     const uint32_t wid = threadIdx.x / kWave;
     const uint32_t lane = lane_id();
-    for (uint32_t i = threadIdx.x; i < kWaves * kRadix; i += THREADS) (&L.wave_hist[0][0])[i] = 0;
+    zero_wave_hist<kWaves, THREADS>(L.wave_hist);
 
     // Each wave owns a contiguous chunk of 64*ITEMS keys; round i covers keys chunk + i*64 + lane.
     // The loads are issued first so that they are in flight during the table sums below.
@@ -367,6 +315,8 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
         const uint32_t idx = chunk + i * kWave + lane;
         const bool valid = idx < n;
         const uint32_t digit = digit_of(i);
+        // the match-any ranking step, claim included, written out: kernel_diff refused claim_rank here (all three
+        // scatter kernels are scheduled differently)
         uint64_t peers = __ballot(valid);
 #pragma unroll
         for (uint32_t b = 0; b < 8; b++) {
@@ -395,6 +345,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     uint32_t tile_cnt = 0;
     if (threadIdx.x < kRadix) {
         const uint32_t d = threadIdx.x;
+        // wave_hist_to_starts, written out: kernel_diff refused the helper here (other branches in the 1024-thread kernels)
 #pragma unroll
         for (uint32_t w = 0; w < kWaves; w++) {
             const uint32_t t = L.wave_hist[w][d];
@@ -411,7 +362,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     if (threadIdx.x < kRadix) {
         L.digit_base[threadIdx.x] = smaller + glob_base;
         L.tile_start[threadIdx.x] = run_start;
-        // BUCKET, or a plain pass whose runs are finished per digit (tile_sort_launch): the run starts are published
+        // BUCKET, or a plain pass whose runs are finished per digit (sort_partition_launch by shift): the run starts are published
         if ((BUCKET || bucket_off != nullptr) && tile == 0) {  // tile 0 exists whenever n > 0
             bucket_off[threadIdx.x] = smaller;
             if (threadIdx.x == kRadix - 1) bucket_off[kRadix] = n;
@@ -472,8 +423,7 @@ __device__ __forceinline__ void downsweep_body(const uint32_t *__restrict__ keys
     __syncthreads();
     BRUSH_KTRACE_MARK_VIA(trace, 2, L.keys[threadIdx.x]);  // (big tiles: mark 2 is free; reordered in LDS, values loaded)
     // ... and write out: position lp of the reordered tile belongs to the run of its digit, so consecutive lanes
-    // write consecutive global addresses (round 1 scattered one dword per lane into 256 runs: 2.1x write
-    // amplification at the HBM counters)
+    // write consecutive global addresses
     const uint32_t tile_n = min(kTileKeys, n - tile_base);
     // 16 keys per lane at 1024 threads (128 registers): fully unrolled it spills
     constexpr uint32_t kOutUnroll = (ITEMS > 8 && THREADS == kSortThreads) ? 4 : ITEMS;
@@ -510,7 +460,7 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_downsweep(
     uint32_t max_n, uint32_t shift, uint32_t mask, const uint32_t *__restrict__ counts,
     const uint32_t *__restrict__ totals, uint32_t max_tiles, uint32_t *__restrict__ edges, uint32_t edge_keys,
     const uint32_t *__restrict__ splitters, uint32_t *__restrict__ bucket_off) {
-    BRUSH_KTRACE(kTrSortDown, shift | (((shift >> 3) + (max_n > (1u << 21) ? 4u : 0u)) << 24));
+    BRUSH_KTRACE(kTrSortDown, sort_pass_tag(shift, max_n));
     // The first 128 rows of the [tile][digit] count table (every row a sort of up to 2 M keys has) are requested before
     // the element count is known: the table sum used to start only when *d_n had arrived and took two dependent batches
     // of loads (2.2 us of the kernel's 6.5 at 100 k keys, profiles/r04_small_kernel_timeline.json).  The table has at least
@@ -583,310 +533,12 @@ __global__ void k_sort_copy(const uint32_t *__restrict__ keys_in, const uint32_t
     }
 }
 
-// ---- bucket finish: one workgroup per bucket ----
-struct FinishLds {
-    uint32_t keys[2][kBucketLdsKeys];
-    uint32_t vals[2][kBucketLdsKeys];
-    uint32_t wave_hist[kSortWaves][kRadix];
-    uint32_t wave_tot2[4][2];
-    uint32_t or_and[kSortWaves][2];
-};
-static_assert(sizeof(FinishLds) <= 160 * 1024, "one finish workgroup per CU");
-
-// One stable counting pass of the whole workgroup over `cnt` pairs, src -> dst (LDS or this bucket's own range of a
-// global buffer) by the digit (key >> shift) & mask.  Every wave owns a contiguous chunk: it counts its digits, the
-// counts are scanned in (digit, wave) order, then it walks the chunk again in index order and ranks 64 keys at a time
-// with match-any ballots, so nothing per key stays in registers and every loop is bounded by cnt.  Ends with a barrier
-// (workgroup-scope release / acquire: the next pass reads what this one wrote, also in global memory).
-__device__ __forceinline__ void bucket_pass(const uint32_t *sk, const uint32_t *sv, uint32_t *dk, uint32_t *dv,
-                                            uint32_t cnt, uint32_t shift, uint32_t mask, FinishLds &L) {
-    const uint32_t wid = threadIdx.x / kWave, lane = lane_id();
-    for (uint32_t i = threadIdx.x; i < kSortWaves * kRadix; i += kSortThreads) (&L.wave_hist[0][0])[i] = 0;
-    __syncthreads();
-    const uint32_t per_wave = ceil_div(cnt, kSortThreads) * kWave;  // cnt <= kBucketMaxN
-    const uint32_t beg = min(cnt, wid * per_wave), end = min(cnt, beg + per_wave);
-    for (uint32_t i = beg + lane; i < end; i += kWave) atomicAdd(&L.wave_hist[wid][(sk[i] >> shift) & mask], 1u);
-    __syncthreads();
-    uint32_t tot = 0, unused = 0;
-    if (threadIdx.x < kRadix) {
-#pragma unroll
-        for (uint32_t w = 0; w < kSortWaves; w++) {
-            const uint32_t t = L.wave_hist[w][threadIdx.x];
-            L.wave_hist[w][threadIdx.x] = tot;
-            tot += t;
-        }
-    }
-    block_excl_scan256_pair(tot, unused, L.wave_tot2);  // tot: pairs of a smaller digit
-    if (threadIdx.x < kRadix) {
-#pragma unroll
-        for (uint32_t w = 0; w < kSortWaves; w++) L.wave_hist[w][threadIdx.x] += tot;
-    }
-    __syncthreads();
-    const uint64_t lt = lanemask_lt();
-    for (uint32_t i0 = beg; i0 < end; i0 += kWave) {  // wave-uniform
-        const uint32_t i = i0 + lane;
-        const bool valid = i < end;
-        const uint32_t k = valid ? sk[i] : 0u, v = valid ? sv[i] : 0u;
-        const uint32_t digit = (k >> shift) & mask;
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (uint32_t b = 0; b < 8; b++) {
-            const bool bit = (digit >> b) & 1u;
-            const uint64_t vote = __ballot(valid && bit);
-            peers &= bit ? vote : ~vote;
-        }
-        const uint32_t below = __popcll(peers & lt);
-        const int leader = valid ? (__ffsll((long long)peers) - 1) : 0;
-        uint32_t old = 0;
-        if (valid && (int)lane == leader) {
-            old = L.wave_hist[wid][digit];
-            L.wave_hist[wid][digit] = old + __popcll(peers);
-        }
-        old = __shfl(old, leader, 64);
-        if (valid) {
-            dk[old + below] = k;
-            dv[old + below] = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-}
-
-// Workgroup b sorts bucket b = pairs [off[b], off[b + 1]) of the scatter's output (tmp) by key, stable, into the same
-// range of the final buffers.  The bucket's keys agree in every bit above the highest one in which any two of them
-// differ (OR ^ AND over the bucket), so only the bits below it are sorted, split evenly over ceil(bits / 8) passes.
-//   * up to kBucketLdsKeys pairs: loaded once, passes between two LDS images, the last one writes the result;
-//   * more (long runs of equal keys, a spike the sample missed): the same passes between the bucket's range of tmp
-//     and of out, an odd number of them so that the last one lands in out.  Slow, and alone in its own range.
-// No workgroup waits for another one.
-__global__ __launch_bounds__(kSortThreads) void k_sort_bucket_finish(uint32_t *tmp_keys, uint32_t *tmp_vals,
-                                                                    uint32_t *keys_out, uint32_t *vals_out,
-                                                                    const uint32_t *__restrict__ d_n, uint32_t max_n,
-                                                                    const uint32_t *__restrict__ bucket_off) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    FinishLds &L = *reinterpret_cast<FinishLds *>(lds_raw);
-    const uint32_t off0 = bucket_off[blockIdx.x], off1 = bucket_off[blockIdx.x + 1];
-    const uint32_t n = min(*d_n, max_n);
-    if (n == 0) return;  // no scatter workgroup ran: the offsets are leftovers
-    const uint32_t start = min(off0, n), stop = min(off1, n);
-    if (stop <= start) return;
-    const uint32_t cnt = stop - start;
-    const bool in_lds = cnt <= kBucketLdsKeys;  // block-uniform
-    tmp_keys += start, tmp_vals += start, keys_out += start, vals_out += start;
-    uint32_t k_or = 0, k_and = 0xFFFFFFFFu;
-    for (uint32_t i = threadIdx.x; i < cnt; i += kSortThreads) {
-        const uint32_t k = tmp_keys[i];
-        k_or |= k, k_and &= k;
-        if (in_lds) L.keys[0][i] = k, L.vals[0][i] = tmp_vals[i];
-    }
-#pragma unroll
-    for (uint32_t m = kWave / 2; m; m >>= 1) {
-        k_or |= (uint32_t)__shfl_xor((int)k_or, (int)m, (int)kWave);
-        k_and &= (uint32_t)__shfl_xor((int)k_and, (int)m, (int)kWave);
-    }
-    if (lane_id() == 0) L.or_and[threadIdx.x / kWave][0] = k_or, L.or_and[threadIdx.x / kWave][1] = k_and;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t w = 0; w < kSortWaves; w++) k_or |= L.or_and[w][0], k_and &= L.or_and[w][1];
-    const uint32_t differ = k_or ^ k_and;
-    const uint32_t bits = differ ? 32u - (uint32_t)__clz((int)differ) : 0u;
-    uint32_t passes = (bits + 7u) / 8u;
-    if (in_lds) {
-        if (passes == 0) {  // one key value: the scatter's order is the result
-            for (uint32_t i = threadIdx.x; i < cnt; i += kSortThreads) keys_out[i] = L.keys[0][i], vals_out[i] = L.vals[0][i];
-            return;
-        }
-        const uint32_t width = (bits + passes - 1u) / passes, mask = (1u << width) - 1u;
-        uint32_t p = 0;
-        for (; p + 1 < passes; p++)
-            bucket_pass(L.keys[p & 1u], L.vals[p & 1u], L.keys[(p + 1u) & 1u], L.vals[(p + 1u) & 1u], cnt, p * width,
-                        mask, L);
-        bucket_pass(L.keys[p & 1u], L.vals[p & 1u], keys_out, vals_out, cnt, p * width, mask, L);
-        return;
-    }
-    passes |= 1u;  // 1, 3 or 5: tmp -> out -> tmp ... -> out (a pass over bits that agree is a stable copy)
-    const uint32_t width = (bits + passes - 1u) / passes, mask = (1u << width) - 1u;  // <= 8; 5 passes: 7 bits, shifts <= 28
-    for (uint32_t p = 0; p < passes; p++) {
-        const bool to_out = (p & 1u) == 0;
-        bucket_pass(to_out ? tmp_keys : keys_out, to_out ? tmp_vals : vals_out, to_out ? keys_out : tmp_keys,
-                    to_out ? vals_out : tmp_vals, cnt, p * width, mask, L);
-    }
-}
-
-// ---- tile sort by tile-range buckets (tile_sort_launch) ----
-// A tile id of 9 to 16 significant bits: bucket = its top 8 bits, a shift of the key, so the plain count and scatter
-// kernels partition the pairs with (shift, mask) = (sig - 8, 0xFF) and one workgroup per bucket finishes its bucket with
-// ONE stable counting pass over the `shift` <= 8 bits below.  Every tile's run lies inside one bucket, so that workgroup
-// also knows the run's start and end: the bin edges are plain stores.
-constexpr uint32_t kTileFinishItems = 8;                                // pairs per lane and chunk, in registers
-constexpr uint32_t kTileFinishChunk = kSortThreads * kTileFinishItems;  // 8192: pairs a finish workgroup ranks at a time
-struct TileFinishLds {
-    uint32_t wave_hist[kSortWaves][kRadix];
-    uint32_t wave_tot2[4][2];
-};
-
-// Workgroup b: bucket b = pairs [off[b], off[b + 1]) of the scatter's output (tmp), all with key >> shift == b, in
-// ascending compact gid order inside every tile (the scatter is stable).  Values -> the same range of vals_out ordered
-// by (key, position); no keys are written.  Tile t = (b << shift) | d with a non-zero count: edges[2 t] = ~start,
-// edges[2 t + 1] = end (the caller zeroed the array, absent tiles stay (0, 0)).
-// The bucket is streamed in chunks of kTileFinishChunk pairs held in registers: the waves own contiguous pieces of a
-// chunk and rank 64 keys at a time with match-any ballots (index order = stable), thread d carries digit d's running
-// output position from chunk to chunk.  A bucket of one chunk (every evenly spread scene up to 2 M pairs) takes its
-// digit totals from the ranking itself: one trip to memory.  A longer one counts its digits in a coalesced pass first.
-// Any size is the same path; no workgroup waits for another one and every loop is bounded by a count read once.
-__global__ __launch_bounds__(kSortThreads) void k_tile_bucket_finish(
-    const uint32_t *__restrict__ tmp_keys, const uint32_t *__restrict__ tmp_vals, uint32_t *__restrict__ vals_out,
-    uint32_t *__restrict__ edges, uint32_t edge_keys, const uint32_t *__restrict__ d_n, uint32_t max_n, uint32_t shift,
-    const uint32_t *__restrict__ bucket_off) {
-    __shared__ TileFinishLds L;
-    const uint32_t off0 = bucket_off[blockIdx.x], off1 = bucket_off[blockIdx.x + 1];  // requested beside the count
-    const uint32_t n = min(*d_n, max_n);
-    if (n == 0) return;  // no scatter workgroup ran: the offsets are leftovers, nothing has looked at them
-    const uint32_t start = min(off0, n), stop = min(off1, n);
-    if (stop <= start) return;
-    const uint32_t cnt = stop - start;
-    const uint32_t sub_mask = (1u << shift) - 1u;  // shift <= 8
-    const uint32_t wid = threadIdx.x / kWave, lane = lane_id();
-    const uint64_t lt = lanemask_lt();
-    tmp_keys += start, tmp_vals += start;
-    const bool one_chunk = cnt <= kTileFinishChunk;  // block-uniform
-
-    // thread d < 256: pairs of digit d in the whole bucket -> position of the next pair of digit d in vals_out, and
-    // the edges of tile (b << shift) | d.  Every thread calls (two barriers).
-    uint32_t next_pos = 0;
-    auto publish = [&](uint32_t tot) {
-        uint32_t smaller = tot, unused = 0;
-        block_excl_scan256_pair(smaller, unused, L.wave_tot2);
-        next_pos = start + smaller;
-        const uint32_t t = (blockIdx.x << shift) | threadIdx.x;
-        if (threadIdx.x <= sub_mask && tot != 0u && t < edge_keys) {
-            edges[2 * t] = ~next_pos;
-            edges[2 * t + 1] = next_pos + tot;
-        }
-    };
-    if (!one_chunk) {
-        for (uint32_t i = threadIdx.x; i < kSortWaves * kRadix; i += kSortThreads) (&L.wave_hist[0][0])[i] = 0;
-        __syncthreads();
-        constexpr uint32_t kCountLoads = 8;
-        for (uint32_t i0 = 0; i0 < cnt; i0 += kSortThreads * kCountLoads) {
-            uint32_t k[kCountLoads];
-#pragma unroll
-            for (uint32_t j = 0; j < kCountLoads; j++) {
-                const uint32_t i = i0 + j * kSortThreads + threadIdx.x;
-                k[j] = i < cnt ? tmp_keys[i] : 0u;
-            }
-#pragma unroll
-            for (uint32_t j = 0; j < kCountLoads; j++)
-                if (i0 + j * kSortThreads + threadIdx.x < cnt) atomicAdd(&L.wave_hist[wid][k[j] & sub_mask], 1u);
-        }
-        __syncthreads();
-        uint32_t tot = 0;
-        if (threadIdx.x < kRadix) {
-#pragma unroll
-            for (uint32_t w = 0; w < kSortWaves; w++) tot += L.wave_hist[w][threadIdx.x];
-        }
-        publish(tot);  // its barriers also order the reads above before the zeroing below
-    }
-    for (uint32_t c0 = 0; c0 < cnt; c0 += kTileFinishChunk) {  // block-uniform
-        const uint32_t m = min(kTileFinishChunk, cnt - c0);
-        const uint32_t per_wave = ceil_div(m, kSortThreads) * kWave;
-        const uint32_t beg = min(m, wid * per_wave), end = min(m, beg + per_wave);
-        uint32_t key[kTileFinishItems], val[kTileFinishItems], rank[kTileFinishItems];
-#pragma unroll
-        for (uint32_t i = 0; i < kTileFinishItems; i++) {
-            const uint32_t idx = beg + i * kWave + lane;
-            key[i] = idx < end ? tmp_keys[c0 + idx] : 0u;
-            val[i] = idx < end ? tmp_vals[c0 + idx] : 0u;
-        }
-        for (uint32_t i = threadIdx.x; i < kSortWaves * kRadix; i += kSortThreads) (&L.wave_hist[0][0])[i] = 0;
-        __syncthreads();
-#pragma unroll
-        for (uint32_t i = 0; i < kTileFinishItems; i++) {
-            if (beg + i * kWave >= end) break;  // wave-uniform
-            const bool valid = beg + i * kWave + lane < end;
-            const uint32_t digit = key[i] & sub_mask;
-            uint64_t peers = __ballot(valid);
-#pragma unroll
-            for (uint32_t b = 0; b < 8; b++) {
-                if (b >= shift) break;  // uniform
-                const bool bit = (digit >> b) & 1u;
-                const uint64_t vote = __ballot(valid && bit);
-                peers &= bit ? vote : ~vote;
-            }
-            const uint32_t below = __popcll(peers & lt);
-            const int leader = valid ? (__ffsll((long long)peers) - 1) : 0;
-            uint32_t old = 0;
-            if (valid && (int)lane == leader) {
-                old = L.wave_hist[wid][digit];
-                L.wave_hist[wid][digit] = old + __popcll(peers);
-            }
-            rank[i] = __shfl(old, leader, 64) + below;
-            __builtin_amdgcn_wave_barrier();
-        }
-        __syncthreads();
-        // thread d: the waves' counts of digit d -> output positions of their first pair of digit d
-        uint32_t chunk_tot = 0;
-        if (threadIdx.x < kRadix) {
-#pragma unroll
-            for (uint32_t w = 0; w < kSortWaves; w++) chunk_tot += L.wave_hist[w][threadIdx.x];
-        }
-        if (one_chunk) publish(chunk_tot);
-        if (threadIdx.x < kRadix) {
-            uint32_t pos = next_pos;
-#pragma unroll
-            for (uint32_t w = 0; w < kSortWaves; w++) {
-                const uint32_t t = L.wave_hist[w][threadIdx.x];
-                L.wave_hist[w][threadIdx.x] = pos;
-                pos += t;
-            }
-            next_pos = pos;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t i = 0; i < kTileFinishItems; i++) {
-            if (beg + i * kWave + lane < end) vals_out[L.wave_hist[wid][key[i] & sub_mask] + rank[i]] = val[i];
-        }
-        if (!one_chunk) __syncthreads();  // the next chunk zeroes the counters
-    }
-}
-
-struct SortWs {
-    uint32_t *tmp_keys, *tmp_vals, *counts, *totals;
-    uint32_t max_tiles;
-    size_t bytes;
-};
-
-SortWs carve_sort(void *ws, uint32_t max_n) {
-    SortWs w;
-    Carver c(ws);
-    w.max_tiles = sort_max_tiles(max_n ? max_n : 1);
-    w.tmp_keys = c.take<uint32_t>(max_n ? max_n : 1);
-    w.tmp_vals = c.take<uint32_t>(max_n ? max_n : 1);
-    w.counts = c.take<uint32_t>((size_t)kRadix * w.max_tiles);
-    w.totals = c.take<uint32_t>(kRadix);
-    w.bytes = c.bytes();
-    return w;
-}
-
-// The downsweep needs more LDS than the 64 KiB a kernel gets by default: opt in once per DEVICE (the attribute
-// belongs to the function's instance on the current device; an embedder may drive several devices from one process).
-hipError_t enable_big_lds() {
+// The 1024- and 512-thread scatter kernels hold a whole tile in dynamic LDS.
+hipError_t enable_downsweep_lds() {
     static std::atomic<int> done[kMaxDevices];
-    const int dev = current_device_slot();
-    if (done[dev].load(std::memory_order_acquire)) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sort_downsweep<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DownLds));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sort_downsweep_big),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DownLdsBig));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sort_downsweep<true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DownLds));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sort_bucket_finish),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FinishLds));
-    if (e == hipSuccess) done[dev].store(1, std::memory_order_release);
-    return e;
+    return enable_big_lds(done, {{reinterpret_cast<const void *>(&k_sort_downsweep<true>), sizeof(DownLds)},
+                                 {reinterpret_cast<const void *>(&k_sort_downsweep_big), sizeof(DownLdsBig)},
+                                 {reinterpret_cast<const void *>(&k_sort_downsweep<true, true>), sizeof(DownLds)}});
 }
 
 }  // namespace
@@ -907,7 +559,7 @@ hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_
                            keys_out, vals_out, d_n, max_n);
         return hipGetLastError();
     }
-    const hipError_t lds = enable_big_lds();
+    const hipError_t lds = enable_downsweep_lds();
     if (lds != hipSuccess) return lds;
     const bool fused = sort_is_fused(max_n);
     const uint32_t *src_k = keys_in, *src_v = vals_in;
@@ -917,8 +569,7 @@ hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_
     // result: the bits above the bound are zero in every key.
     uint32_t even_width = 0;
     if (edge_keys > 1u) {
-        uint32_t sig = 0;
-        while (sig < 32u && ((edge_keys - 1u) >> sig) != 0u) sig++;
+        const uint32_t sig = significant_bits(edge_keys - 1u);
         if (sig <= total_bits) even_width = (sig + passes - 1u) / passes;
     }
     for (uint32_t p = 0; p < passes; p++) {
@@ -929,15 +580,13 @@ hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_
         uint32_t *dst_k = to_out ? keys_out : w.tmp_keys;  // keys_out may be nullptr: the last pass then writes no keys
         uint32_t *dst_v = to_out ? vals_out : w.tmp_vals;
         uint32_t *pass_edges = p + 1 == passes ? edges : nullptr;
+        hipLaunchKernelGGL((fused ? k_sort_upsweep<true, false> : k_sort_upsweep<false, false>), dim3(w.max_tiles),
+                           dim3(kSortThreads), 0, s, src_k, d_n, max_n, shift, mask, w.counts, w.max_tiles, nullptr);
         if (fused) {
-            hipLaunchKernelGGL(k_sort_upsweep<true>, dim3(w.max_tiles), dim3(kSortThreads), 0, s, src_k, d_n, max_n,
-                               shift, mask, w.counts, w.max_tiles, nullptr);
             hipLaunchKernelGGL(k_sort_downsweep<true>, dim3(w.max_tiles), dim3(kSortThreads), sizeof(DownLds), s, src_k,
                                src_v, dst_k, dst_v, d_n, max_n, shift, mask, w.counts, w.totals, w.max_tiles, pass_edges,
                                edge_keys, nullptr, nullptr);
         } else {
-            hipLaunchKernelGGL(k_sort_upsweep<false>, dim3(w.max_tiles), dim3(kSortThreads), 0, s, src_k, d_n, max_n,
-                               shift, mask, w.counts, w.max_tiles, nullptr);
             hipLaunchKernelGGL(k_sort_scan, dim3(kRadix), dim3(256), 0, s, w.counts, d_n, max_n, w.max_tiles, w.totals);
             hipLaunchKernelGGL(k_sort_downsweep_big, dim3(w.max_tiles), dim3(kBigThreads), sizeof(DownLdsBig), s,
                                src_k, src_v, dst_k, dst_v, d_n, max_n, shift, mask, w.counts, w.totals, w.max_tiles,
@@ -949,58 +598,19 @@ hipError_t sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_
     return hipGetLastError();
 }
 
-bool depth_sort_uses_buckets(uint32_t max_n) { return max_n <= kBucketMaxN; }
-
-hipError_t depth_sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
-                             const uint32_t *d_n, uint32_t max_n, void *ws, hipStream_t s) {
-    if (!depth_sort_uses_buckets(max_n)) return sort_launch(keys_in, vals_in, keys_out, vals_out, d_n, max_n, 32, ws, s);
-    if (max_n == 0) return hipSuccess;
-    if (!keys_out) return hipErrorInvalidValue;
-    const SortWs w = carve_sort(ws, max_n);
-    const hipError_t lds = enable_big_lds();
+hipError_t sort_partition_launch(const uint32_t *keys_in, const uint32_t *vals_in, const uint32_t *d_n, uint32_t max_n,
+                                 const SortWs &w, hipStream_t s, bool by_splitters, uint32_t shift) {
+    const hipError_t lds = enable_downsweep_lds();
     if (lds != hipSuccess) return lds;
-    // The fused shape leaves two pieces of its workspace unused: `totals` (here: the splitters) and the upper half of
-    // the count table, whose rows are 16-bit (here: the kRadix + 1 bucket offsets).
-    static_assert(kRadix + 1 <= (kRadix / 2) * kSortTargetTiles, "the offsets fit in the unused half");
-    uint32_t *splitters = w.totals, *bucket_off = w.counts + (size_t)(kRadix / 2) * w.max_tiles;
-    hipLaunchKernelGGL((k_sort_upsweep<true, true>), dim3(w.max_tiles), dim3(kSortThreads), 0, s, keys_in, d_n, max_n, 0u,
-                       kRadix - 1u, w.counts, w.max_tiles, splitters);
-    hipLaunchKernelGGL((k_sort_downsweep<true, true>), dim3(w.max_tiles), dim3(kSortThreads), sizeof(DownLds), s, keys_in,
-                       vals_in, w.tmp_keys, w.tmp_vals, d_n, max_n, 0u, kRadix - 1u, w.counts, w.totals, w.max_tiles,
-                       (uint32_t *)nullptr, 0u, (const uint32_t *)splitters, bucket_off);
-    hipLaunchKernelGGL(k_sort_bucket_finish, dim3(kRadix), dim3(kSortThreads), sizeof(FinishLds), s, w.tmp_keys,
-                       w.tmp_vals, keys_out, vals_out, d_n, max_n, (const uint32_t *)bucket_off);
-    return hipGetLastError();
-}
-
-static bool tile_sort_uses_buckets(uint32_t max_n, uint32_t num_tiles) {
-    uint32_t sig = 0;
-    while (sig < 32u && num_tiles > 1u && ((num_tiles - 1u) >> sig) != 0u) sig++;
-    return sort_is_fused(max_n) && sig > 8u && sig <= 16u;
-}
-
-hipError_t tile_sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
-                            const uint32_t *d_n, uint32_t max_n, uint32_t bits, void *ws, hipStream_t s, uint32_t *edges,
-                            uint32_t num_tiles) {
-    if (!vals_in || keys_out || !edges || !tile_sort_uses_buckets(max_n, num_tiles))
-        return sort_launch(keys_in, vals_in, keys_out, vals_out, d_n, max_n, bits, ws, s, edges, num_tiles);
-    if (max_n == 0) return hipSuccess;
-    const SortWs w = carve_sort(ws, max_n);
-    const hipError_t lds = enable_big_lds();
-    if (lds != hipSuccess) return lds;
-    uint32_t sig = 0;
-    while (((num_tiles - 1u) >> sig) != 0u) sig++;  // 9 .. 16
-    const uint32_t shift = sig - 8u;
-    // the bucket offsets go where depth_sort_launch puts them (the forward runs both sorts in one workspace, in turn)
-    uint32_t *bucket_off = w.counts + (size_t)(kRadix / 2) * w.max_tiles;
-    hipLaunchKernelGGL(k_sort_upsweep<true>, dim3(w.max_tiles), dim3(kSortThreads), 0, s, keys_in, d_n, max_n, shift,
-                       kRadix - 1u, w.counts, w.max_tiles, nullptr);
-    hipLaunchKernelGGL(k_sort_downsweep<true>, dim3(w.max_tiles), dim3(kSortThreads), sizeof(DownLds), s, keys_in, vals_in,
-                       w.tmp_keys, w.tmp_vals, d_n, max_n, shift, kRadix - 1u, w.counts, w.totals, w.max_tiles,
-                       (uint32_t *)nullptr, 0u, (const uint32_t *)nullptr, bucket_off);
-    hipLaunchKernelGGL(k_tile_bucket_finish, dim3(kRadix), dim3(kSortThreads), 0, s, (const uint32_t *)w.tmp_keys,
-                       (const uint32_t *)w.tmp_vals, vals_out, edges, num_tiles, d_n, max_n, shift,
-                       (const uint32_t *)bucket_off);
+    // the BUCKET instantiations take the plain ones' arguments: one argument list, the kernels chosen here
+    const auto count = by_splitters ? k_sort_upsweep<true, true> : k_sort_upsweep<true, false>;
+    const auto scatter = by_splitters ? k_sort_downsweep<true, true> : k_sort_downsweep<true, false>;
+    uint32_t *const spl = by_splitters ? w.splitters : nullptr, *const no_edges = nullptr;
+    hipLaunchKernelGGL(count, dim3(w.max_tiles), dim3(kSortThreads), 0, s, keys_in, d_n, max_n, shift, kRadix - 1u,
+                       w.counts, w.max_tiles, spl);
+    hipLaunchKernelGGL(scatter, dim3(w.max_tiles), dim3(kSortThreads), sizeof(DownLds), s, keys_in, vals_in, w.tmp_keys,
+                       w.tmp_vals, d_n, max_n, shift, kRadix - 1u, w.counts, w.totals, w.max_tiles, no_edges, 0u,
+                       (const uint32_t *)spl, w.bucket_off);
     return hipGetLastError();
 }
 

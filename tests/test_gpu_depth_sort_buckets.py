@@ -1,6 +1,6 @@
 """The bucketed depth sort against numpy, element by element (pytest -m gpu).
 
-Clouds of up to 2^20 splats sort their depth keys in three launches (radix_sort.hip, depth_sort_launch): a count and a
+Clouds of up to 2^20 splats sort their depth keys in three launches (depth_sort.hip, depth_sort_launch): a count and a
 scatter whose digit is "bucket of key" (255 splitters from a sorted sample of S keys), then one workgroup per bucket
 finishes its bucket — in LDS up to C pairs, with passes over its own range of the two global buffers above that.
 
@@ -18,7 +18,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-# Mirrors of brush_amd/csrc/radix_sort.hip
+# Mirrors of brush_amd/csrc/depth_sort.hip (kSampleKeys: radix_sort.hip; kRadix, kBucketMaxN: sort_common.hpp)
 S = 1024            # kSampleKeys: keys in the sample the splitters are picked from
 B = 256             # kRadix: buckets
 C = 8192            # kBucketLdsKeys: pairs a finish workgroup sorts in LDS

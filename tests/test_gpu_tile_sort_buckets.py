@@ -1,7 +1,7 @@
 """The bucketed tile sort against the CPU oracle, element by element (pytest -m gpu).
 
 Frames of 257 to 65 535 tiles sort their (tile id, compact gid) pairs in three launches in the default mode
-(radix_sort.hip, tile_sort_launch): a count and a scatter on the top 8 of the id's `sig` significant bits, then one
+(tile_sort.hip, tile_sort_launch): a count and a scatter on the top 8 of the id's `sig` significant bits, then one
 workgroup per bucket orders its bucket by the `sig - 8` bits below in chunks of C pairs and stores the bin edges of its
 tiles.  Every other frame, the deterministic mode and every intersection capacity above 512 x 16 384 keep the LSD
 passes.
@@ -27,7 +27,7 @@ from tests import test_gpu_render as RT
 
 pytestmark = pytest.mark.gpu
 
-# Mirrors of brush_amd/csrc/radix_sort.hip
+# Mirrors of brush_amd/csrc/tile_sort.hip (kTileFinishChunk) and sort_common.hpp (the rest)
 B = 256                     # kRadix: buckets
 C = 8192                    # kTileFinishChunk: pairs a finish workgroup ranks at a time (its only internal switch)
 SORT_THREADS = 1024         # kSortThreads

@@ -230,6 +230,38 @@ def test_fixed_sum_kernels_static_lds_and_spills(lib):
     assert sorted(seen, key=str) == sorted(want, key=str)
 
 
+def test_sort_kernels_static_lds_and_spills(lib):
+    """The kernels of the three sorters (radix_sort.hip, depth_sort.hip, tile_sort.hip): exactly these ten, each in one
+    translation unit, with the static LDS of its own arrays (the scatter kernels and the depth finish take theirs as
+    dynamic LDS: 0 here, or the 1024 bytes of the BUCKET scatter's splitters), and no spills or scratch: the two plain
+    scatter kernels sit at 128 and 124 VGPRs, where one more live value spills."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("kernel_diff", os.path.join(ROOT, "tools", "kernel_diff.py"))
+    kd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kd)
+    from brush_amd import _lib
+
+    assert lib is not None
+    res = kd.resources(_lib.LIB_PATH, r"k_sort_|k_tile_bucket")
+    want = {("k_sort_copy", None): 0, ("k_sort_scan", None): 20,
+            ("k_sort_upsweep", "Lb0ELb0E"): 16384, ("k_sort_upsweep", "Lb1ELb0E"): 16384,
+            ("k_sort_upsweep", "Lb1ELb1E"): 25600,
+            ("k_sort_downsweep", "Lb1ELb0E"): 0, ("k_sort_downsweep", "Lb1ELb1E"): 1024,
+            ("k_sort_downsweep_big", None): 0, ("k_sort_bucket_finish", None): 0,
+            ("k_tile_bucket_finish", None): 16416}
+    seen = []
+    for name, r in res.items():
+        m = re.search(r"N_1\d+(k_[a-z_]+?)(?:I((?:Lb[01]E){2})EEv|E)P", name)
+        assert m, name
+        key = (m.group(1), m.group(2))
+        assert key in want, name
+        assert (r["vgpr_spill_count"], r["sgpr_spill_count"], r["private_segment_fixed_size"]) == (0, 0, 0), name
+        assert r["group_segment_fixed_size"] == want[key], name
+        seen.append(key)
+    assert sorted(seen, key=str) == sorted(want, key=str)
+
+
 def test_product_and_bench_do_not_import_the_oracle():
     """The oracle is test infrastructure: importing the package, or bench.py up to its timed path
     (synthetic inputs included), must not load it; only bench.py's cpu_baseline leg and the tests do."""

@@ -47,6 +47,11 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 an indexed, watertight triangle mesh cut out of it by marching tetrahedra
                                 (brush_amd/tsdf.py, brush_amd/mesh.py; build extension, the TSDF exports of 2DGS, GOF
                                 and nerfstudio are the models; also `python -m brush_amd.mesh`)
+  render_median_depth / median_depth_from_aux  <- the median depth (the z of the splat at which the accumulated
+                                opacity first reaches one half) and the id of that splat per pixel, from a replay of the
+                                compositing walk; not differentiable (brush_amd/median_depth.py; build extension, the
+                                depth 2DGS, GOF and RaDe-GS fuse; Splats.render_median_depth,
+                                TsdfVolume.integrate_splats(depth="median"), `python -m brush_amd.mesh --depth median`)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -84,6 +89,7 @@ _CONTRIBUTION_NAMES = ("Contributions", "ContributionBuffers", "contributions_fr
 _ERROR_SCORE_NAMES = ("ErrorScores", "ErrorScoreBuffers", "l1_error_map", "error_scores_from_aux", "splat_error_scores")
 _TSDF_NAMES = ("TsdfVolume", "TsdfArrays")
 # (brush_amd.mesh is a command line too: imported on first use, as brush_amd.eval is)
+_MEDIAN_DEPTH_NAMES = ("render_median_depth", "median_depth_from_aux")
 _MESH_NAMES = ("Mesh", "mesh_to_ply", "mesh_from_ply", "default_bounds", "grid_for")
 
 
@@ -109,6 +115,9 @@ def __getattr__(name):
     if name in _TSDF_NAMES:
         from . import tsdf as _tsdf
         return getattr(_tsdf, name)
+    if name in _MEDIAN_DEPTH_NAMES:
+        from . import median_depth as _median_depth
+        return getattr(_median_depth, name)
     if name in _MESH_NAMES:
         from . import mesh as _mesh
         return getattr(_mesh, name)

@@ -19,6 +19,7 @@ DEPTH_LOSS_DEPTH = 0   # BrushDepthLoss.mode: BRUSH_DEPTH_LOSS_DEPTH
 DEPTH_LOSS_DISPARITY = 1  # BRUSH_DEPTH_LOSS_DISPARITY
 DEPTH_GT_U16 = 0       # BrushDepthLoss.gt_dtype: BRUSH_DEPTH_GT_U16
 DEPTH_GT_F32 = 1       # BRUSH_DEPTH_GT_F32
+TSDF_DEPTH_METRIC = 1  # brush_tsdf_integrate_ex flags: BRUSH_TSDF_DEPTH_METRIC
 UNIFORM_WORDS = 28
 NUM_VISIBLE_WORD = 25
 TILE_WIDTH = 16
@@ -236,6 +237,8 @@ _SYMBOLS = [
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P]),
     ("brush_l1_error_map", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P]),
     ("brush_render_error_scores", C.c_int, [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, C.c_uint32, _P]),
+    ("brush_render_median_depth", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.c_float, _P, _P, C.c_uint32, _P]),
     ("brush_filter3d_view_chunk", C.c_uint32, []),
     ("brush_filter3d_rates", C.c_int,
      [_P, C.c_uint32, _P, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),
@@ -244,6 +247,9 @@ _SYMBOLS = [
     ("brush_tsdf_integrate", C.c_int,
      [C.POINTER(BrushTsdfGrid), _P, _P, C.POINTER(BrushTsdfViewData), C.c_uint32, C.c_float, C.c_float, C.c_float,
       _P]),
+    ("brush_tsdf_integrate_ex", C.c_int,
+     [C.POINTER(BrushTsdfGrid), _P, _P, C.POINTER(BrushTsdfViewData), C.c_uint32, C.c_float, C.c_float, C.c_float,
+      C.c_uint32, _P]),
     ("brush_tsdf_mesh_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     ("brush_tsdf_mesh_count", C.c_int, [C.POINTER(BrushTsdfGrid), _P, C.c_uint32, _P, _P, C.c_size_t, _P]),
     ("brush_tsdf_mesh_emit", C.c_int,

@@ -108,6 +108,8 @@ __device__ __forceinline__ float centre(float origin, uint32_t idx, float voxel)
     return origin + ((float)idx + 0.5f) * voxel;
 }
 
+// METRIC: d.depth is already a distance (a median depth map), not the accumulated depth D = sum T alpha z.
+template <bool METRIC>
 __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(BrushTsdfGrid g, uint32_t nvox, uint32_t *__restrict__ vol,
                                                              const BrushFilterView *__restrict__ views,
                                                              ViewPointers data, uint32_t num_views, float alpha_min,
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(BrushTsdfGrid g, ui
         const float4 c = reinterpret_cast<const float4 *>(d.img)[pix];
         const float a = c.w;
         if (!(a >= alpha_min)) continue;
-        const float depth = d.depth[pix] / a;
+        const float depth = METRIC ? d.depth[pix] : d.depth[pix] / a;
         if (!(depth > 0.0f && depth <= max_depth)) continue;
         const float s = depth - pz;
         if (!(s >= -g.trunc)) continue;
@@ -368,9 +370,10 @@ MeshWs carve_mesh_ws(void *ws, uint32_t n) {
 
 using namespace brush;
 
-extern "C" int brush_tsdf_integrate(const BrushTsdfGrid *h_grid, uint32_t *volume, const BrushFilterView *views,
-                                    const BrushTsdfViewData *h_data, uint32_t num_views, float alpha_min,
-                                    float max_depth, float near_z, brush_stream_t stream) {
+extern "C" int brush_tsdf_integrate_ex(const BrushTsdfGrid *h_grid, uint32_t *volume, const BrushFilterView *views,
+                                       const BrushTsdfViewData *h_data, uint32_t num_views, float alpha_min,
+                                       float max_depth, float near_z, uint32_t flags, brush_stream_t stream) {
+    if ((flags & ~BRUSH_TSDF_DEPTH_METRIC) != 0u) return BRUSH_ERR_INVALID_ARG;
     if (!grid_ok(h_grid) || !volume || !views || !h_data) return BRUSH_ERR_INVALID_ARG;
     if (num_views < 1u || num_views > kMaxViews) return BRUSH_ERR_INVALID_ARG;
     if (misaligned(volume, 16) || misaligned(views, 16)) return BRUSH_ERR_INVALID_ARG;
@@ -384,11 +387,17 @@ extern "C" int brush_tsdf_integrate(const BrushTsdfGrid *h_grid, uint32_t *volum
         data.v[v] = d;
     }
     const uint32_t nvox = h_grid->nx * h_grid->ny * h_grid->nz;
-    hipLaunchKernelGGL(k_tsdf_integrate, dim3(ceil_div(nvox, kThreads)), dim3(kThreads), 0,
-                       static_cast<hipStream_t>(stream), *h_grid, nvox, volume, views, data, num_views, alpha_min,
-                       max_depth, near_z);
+    const auto kernel = (flags & BRUSH_TSDF_DEPTH_METRIC) ? k_tsdf_integrate<true> : k_tsdf_integrate<false>;
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(nvox, kThreads)), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       *h_grid, nvox, volume, views, data, num_views, alpha_min, max_depth, near_z);
     BRUSH_HIP_CHECK(hipGetLastError());
     return BRUSH_OK;
+}
+
+extern "C" int brush_tsdf_integrate(const BrushTsdfGrid *h_grid, uint32_t *volume, const BrushFilterView *views,
+                                    const BrushTsdfViewData *h_data, uint32_t num_views, float alpha_min,
+                                    float max_depth, float near_z, brush_stream_t stream) {
+    return brush_tsdf_integrate_ex(h_grid, volume, views, h_data, num_views, alpha_min, max_depth, near_z, 0u, stream);
 }
 
 extern "C" int brush_tsdf_mesh_workspace_size(uint32_t nx, uint32_t ny, uint32_t nz, size_t *bytes) {

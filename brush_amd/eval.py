@@ -9,6 +9,7 @@ Command line (prints one line per view, then the means):
     python -m brush_amd.eval SPLATS DATASET [--format auto|nerf|colmap] [--eval-split-every K]
                              [--max-resolution R] [--num-frames K] [--seed S] [--window 11] [--json OUT]
                              [--depth-metrics] [--depth-mode depth|disparity] [--downscale 1,2,4,8]
+                             [--depth-dir DIR [--depth-median]]
                              [--background white|black|R,G,B] [--no-masks]
 
 --background white scores over a white background (the protocol of the NeRF-synthetic numbers in the literature): the
@@ -261,9 +262,11 @@ def eval_depth(splats, scene, *, mode: str = "depth", alpha_min: float = 0.5,
             for k, v in enumerate(views)]
 
 
-def write_depth_maps(splats, views, out_dir: str):
+def write_depth_maps(splats, views, out_dir: str, median: bool = False):
     """For each view: <stem>_depth.npy, the accumulated depth D = sum T alpha z (Splats.render_depth), and
-    <stem>_depth_norm.npy, D / max(alpha, 1e-6) with 0 where alpha is 0; both f32 [h,w].  Returns the written paths."""
+    <stem>_depth_norm.npy, D / max(alpha, 1e-6) with 0 where alpha is 0; both f32 [h,w].  `median`: also
+    <stem>_depth_median.npy, the median depth at level 0.5 (Splats.render_median_depth; 0 where alpha < 0.5).  Returns
+    the written paths."""
     import os
 
     os.makedirs(out_dir, exist_ok=True)
@@ -271,11 +274,15 @@ def write_depth_maps(splats, views, out_dir: str):
     with torch.no_grad():
         for v in views:
             h, w = int(v.image.shape[0]), int(v.image.shape[1])
-            img, depth, _ = splats.render_depth(v.camera, (w, h))
+            if median:
+                img, depth, med, _, _ = splats.render_median_depth(v.camera, (w, h))
+            else:
+                img, depth, _ = splats.render_depth(v.camera, (w, h))
             alpha = img[..., 3]
             norm = torch.where(alpha > 0, depth / torch.clamp(alpha, min=1e-6), torch.zeros_like(depth))
             stem = os.path.splitext(os.path.basename(v.name))[0]
-            for suffix, t in (("_depth.npy", depth), ("_depth_norm.npy", norm)):
+            maps = (("_depth.npy", depth), ("_depth_norm.npy", norm)) + ((("_depth_median.npy", med),) if median else ())
+            for suffix, t in maps:
                 path = os.path.join(out_dir, stem + suffix)
                 np.save(path, t.cpu().numpy().astype(np.float32))
                 paths.append(path)
@@ -363,6 +370,9 @@ def parser():
     p.add_argument("--depth-dir", default=None,
                    help="also write every eval view's accumulated depth D (<view stem>_depth.npy, f32 [h,w]) and "
                         "D / alpha (<view stem>_depth_norm.npy, 0 where alpha is 0) to this directory")
+    p.add_argument("--depth-median", action="store_true",
+                   help="--depth-dir: also write every eval view's median depth (<view stem>_depth_median.npy: the z "
+                        "of the splat at which the accumulated opacity first reaches one half, 0 where it never does)")
     p.add_argument("--antialiased", action="store_true",
                    help="render in the antialiased mode (opacity compensation of the 2D blur), e.g. for splats "
                         "trained with it")
@@ -426,6 +436,8 @@ def main(argv=None) -> int:
     compose_args = {"background": background, "use_masks": not args.no_masks}
     if (args.zoom is None) != (args.image_dir is None):
         p.error("--zoom and --image-dir go together")
+    if args.depth_median and args.depth_dir is None:
+        p.error("--depth-median needs --depth-dir")
     if args.zoom is not None and not (args.zoom > 0 and args.zoom < float("inf")):
         p.error("--zoom must be a positive factor")
 
@@ -468,7 +480,7 @@ def main(argv=None) -> int:
                                "views": [{"name": s.view.name, "psnr": s.psnr, "ssim": s.ssim} for s in st.samples],
                                "mean_psnr": st.mean_psnr(), "mean_ssim": st.mean_ssim()})
     if args.depth_dir:
-        write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir)
+        write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir, median=args.depth_median)
     if args.zoom is not None:
         for path in write_zoomed_renders(splats, [s.view for s in stats.samples], args.zoom, args.image_dir,
                                          antialiased=args.antialiased, background=background):

@@ -171,6 +171,18 @@ class Splats(torch.nn.Module):
         return render_splats_depth(camera, img_size, self.means, self.xys_dummy, self.log_scales, norm_rot,
                                    self.sh_coeffs, self.raw_opacity, max_intersects, antialiased=antialiased)
 
+    def render_median_depth(self, camera: Camera, img_size, *, level: float = 0.5, antialiased: bool = False,
+                            max_intersects=None):
+        """render_depth() plus the median depth and the splat under every pixel (median_depth.render_median_depth):
+        (img [h,w,4], depth [h,w], median [h,w], ids [h,w] i32, aux).  Not differentiable."""
+        from .median_depth import render_median_depth
+
+        with torch.no_grad():
+            norm_rot = self._synced_norm_rotation()
+        return render_median_depth(camera, img_size, self.means, self.log_scales, norm_rot, self.sh_coeffs,
+                                   self.raw_opacity, level=level, antialiased=antialiased,
+                                   max_intersects=max_intersects)
+
     def render_pose(self, camera: Camera, img_size, viewmat, max_intersects=None, antialiased: bool = False,
                     depth: bool = False):
         """render() / render_depth() through the explicit world-to-camera matrix `viewmat` (float32 [4,4] CPU tensor),

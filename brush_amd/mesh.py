@@ -4,12 +4,15 @@ the surface (brush_amd/tsdf.py).
     python -m brush_amd.mesh SPLATS DATASET [--resolution 256 | --voxel-size S] [--bounds x0,y0,z0,x1,y1,z1]
                              [--trunc-voxels 4] [--alpha-min 0.5] [--max-depth D] [--min-views 2]
                              [--views train|eval|all] [--antialiased] [--no-undistort] [--no-masks]
+                             [--depth expected|median] [--median-level 0.5]
                              [--export OUT.ply] [--json OUT.json]
                              [--format auto|nerf|colmap] [--eval-split-every K] [--max-resolution R]
 
 Without --bounds the grid encloses the central 98 % of the splats whose opacity is at least 0.1 (default_bounds), padded
 by 5 % of its longest side.  Prints the grid and its size in bytes, the number of views fused, the fraction of voxels
 any view observed, and the vertex and face counts; --export writes a binary PLY with per-vertex colours.
+--depth median fuses the median depth (brush_amd/median_depth.py) instead of the expected depth D / alpha: no skirts at
+silhouettes, thin structures survive.
 """
 from __future__ import annotations
 
@@ -153,6 +156,11 @@ def parser():
     p.add_argument("--views", choices=("train", "eval", "all"), default="train", help="the views to fuse")
     p.add_argument("--antialiased", action="store_true", help="render in the antialiased mode")
     p.add_argument("--no-masks", action="store_true", help="ignore the dataset's loss masks")
+    p.add_argument("--depth", choices=("expected", "median"), default="expected",
+                   help="the depth to fuse: the expected depth D / alpha, or the median depth (the splat at which the "
+                        "accumulated opacity first reaches --median-level)")
+    p.add_argument("--median-level", type=float, default=0.5, metavar="L",
+                   help="--depth median: the accumulated opacity at which the depth is taken, 0 < L < 1")
     p.add_argument("--export", default=None, metavar="OUT.ply", help="write the mesh to this .ply")
     p.add_argument("--json", default=None, metavar="OUT.json", help="also write the numbers to this file")
     p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
@@ -192,6 +200,8 @@ def plan_from_args(args) -> dict:
         raise ValueError(f"--max-depth must be > 0, got {args.max_depth}")
     if args.min_views < 1:
         raise ValueError(f"--min-views must be at least 1, got {args.min_views}")
+    if not (math.isfinite(args.median_level) and 0.0 < args.median_level < 1.0):
+        raise ValueError(f"--median-level must be finite with 0 < L < 1, got {args.median_level}")
     plan = {"grid_kw": grid_kw, "bounds": None, "grid": None}
     if args.bounds is not None:
         plan["bounds"] = parse_bounds(args.bounds)
@@ -242,7 +252,8 @@ def main(argv=None) -> int:
     print(f"grid\t{dims[0]} x {dims[1]} x {dims[2]}\tvoxel {voxel:g}\torigin {origin[0]:g},{origin[1]:g},{origin[2]:g}"
           f"\t{vol.nbytes} bytes")
     vol.integrate_splats(splats, views, antialiased=args.antialiased, use_masks=not args.no_masks,
-                         alpha_min=args.alpha_min, max_depth=args.max_depth)
+                         alpha_min=args.alpha_min, max_depth=args.max_depth, depth=args.depth,
+                         level=args.median_level)
     observed = float((vol.state[0] != 0).float().mean())
     mesh = vol.extract_mesh(args.min_views)
     nv, nf = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
@@ -258,7 +269,8 @@ def main(argv=None) -> int:
                         "bytes": vol.nbytes},
                "views": args.views, "num_views": len(views), "antialiased": bool(args.antialiased),
                "use_masks": not args.no_masks, "alpha_min": args.alpha_min, "max_depth": args.max_depth,
-               "min_views": args.min_views, "observed_fraction": observed, "vertices": nv, "faces": nf}
+               "min_views": args.min_views, "depth": args.depth, "median_level": args.median_level,
+               "observed_fraction": observed, "vertices": nv, "faces": nf}
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
     return 0

@@ -49,6 +49,15 @@ def check_grid(voxel_size, dims):
     return voxel_size, dims
 
 
+def _depth_kind_flags(depth_kind) -> int:
+    """The flags of brush_tsdf_integrate_ex for TsdfVolume.integrate's `depth_kind`, or a ValueError."""
+    if depth_kind == "accumulated":
+        return 0
+    if depth_kind == "metric":
+        return _lib.TSDF_DEPTH_METRIC
+    raise ValueError(f"depth_kind must be 'accumulated' or 'metric', got {depth_kind!r}")
+
+
 @dataclass
 class TsdfArrays:
     """TsdfVolume.read(): host arrays indexed [k, j, i] (x fastest).  `sdf`: the mean distance in units of the
@@ -140,16 +149,19 @@ class TsdfVolume:
 
     def integrate(self, views, imgs: Sequence[torch.Tensor], depths: Sequence[torch.Tensor], *,
                   masks: Optional[Sequence[Optional[torch.Tensor]]] = None, alpha_min: float = 0.5,
-                  max_depth: Optional[float] = None, near: float = 0.2) -> None:
-        """Fuses views into the volume (brush_tsdf_integrate), up to MAX_VIEWS per launch: launches and the upload of the
+                  max_depth: Optional[float] = None, near: float = 0.2, depth_kind: str = "accumulated") -> None:
+        """Fuses views into the volume (brush_tsdf_integrate_ex), up to MAX_VIEWS per launch: launches and the upload of the
         view records (96 bytes a view), no read-back, no synchronisation.  `views`:
         SceneViews or (Camera, (w, h)) pairs, or their filter3d.view_records as a float32 [V, 24] HOST array; `imgs[v]`:
         the view's raw render, float32 [h, w, 4] on the volume's device (premultiplied colour and alpha, as
         render_splats_depth returns it); `depths[v]`: its accumulated depth, float32 [h, w]; `masks[v]`: uint8 [h, w]
         or None, 0 = ignore the pixel.  A pixel is used where alpha >= alpha_min and 0 < depth / alpha <= max_depth
-        (None: no limit); a voxel is seen by a view where its camera-space z exceeds `near`."""
+        (None: no limit); a voxel is seen by a view where its camera-space z exceeds `near`.  `depth_kind`:
+        "accumulated" (the default): depths[v] is D = sum T alpha z and the distance is D / alpha; "metric": depths[v]
+        already is a distance (a median depth map) and is used as it is, alpha still gating the pixel."""
         from .filter3d import VIEW_WORDS, view_records
 
+        flags = _depth_kind_flags(depth_kind)
         rec = views if isinstance(views, np.ndarray) else view_records(views)
         if rec.ndim != 2 or rec.shape[1] != VIEW_WORDS or rec.dtype != np.float32:
             raise ValueError(f"view records must be a float32 [V,{VIEW_WORDS}] host array, got {rec.dtype} {rec.shape}")
@@ -185,10 +197,10 @@ class TsdfVolume:
                 k = min(MAX_VIEWS, nv - base)
                 chunk = C.cast(C.addressof(data) + base * C.sizeof(_lib.BrushTsdfViewData),
                                C.POINTER(_lib.BrushTsdfViewData))
-                _lib.check(_lib.lib().brush_tsdf_integrate(C.byref(grid), self.state.data_ptr(),
-                                                           rec_dev.data_ptr() + base * VIEW_WORDS * 4, chunk, k,
-                                                           float(alpha_min), max_depth, float(near), stream),
-                           "brush_tsdf_integrate")
+                _lib.check(_lib.lib().brush_tsdf_integrate_ex(C.byref(grid), self.state.data_ptr(),
+                                                              rec_dev.data_ptr() + base * VIEW_WORDS * 4, chunk, k,
+                                                              float(alpha_min), max_depth, float(near), flags, stream),
+                           "brush_tsdf_integrate_ex")
         self.views += nv
 
     def _checked(self, t, shape, dtype, what):
@@ -200,13 +212,21 @@ class TsdfVolume:
 
     def integrate_splats(self, splats, views, *, antialiased: bool = False, use_masks: bool = True,
                          views_per_launch: Optional[int] = None, alpha_min: float = 0.5,
-                         max_depth: Optional[float] = None, near: float = 0.2) -> None:
+                         max_depth: Optional[float] = None, near: float = 0.2, depth: str = "expected",
+                         level: float = 0.5) -> None:
         """Renders `splats` from every view (Splats.render_depth at the view's own size) and fuses the renders,
         `views_per_launch` at a time (default DEFAULT_VIEWS_PER_LAUNCH, at most MAX_VIEWS): that many renders are alive
         at once.  `views`: SceneViews, whose loss masks are honoured unless `use_masks` is False, or (Camera, (w, h))
-        pairs.  The volume's bits do not depend on `views_per_launch` or on the order of the views."""
+        pairs.  The volume's bits do not depend on `views_per_launch` or on the order of the views.
+        `depth`: "expected" (the default) fuses D / alpha; "median" fuses the median depth at `level`
+        (Splats.render_median_depth: the z of the splat at which the accumulated opacity first reaches `level`), which
+        does not blend a silhouette's foreground with what lies behind it."""
         from .filter3d import _camera_and_size
+        from .median_depth import check_level
 
+        if depth not in ("expected", "median"):
+            raise ValueError(f"depth must be 'expected' or 'median', got {depth!r}")
+        level = check_level(level)
         k = DEFAULT_VIEWS_PER_LAUNCH if views_per_launch is None else int(views_per_launch)
         if not 1 <= k <= MAX_VIEWS:
             raise ValueError(f"views_per_launch must be in [1, {MAX_VIEWS}], got {views_per_launch!r}")
@@ -217,12 +237,16 @@ class TsdfVolume:
                 imgs, depths, masks = [], [], []
                 for v in chunk:
                     cam, size = _camera_and_size(v)
-                    img, depth, _ = splats.render_depth(cam, size, antialiased=antialiased)
+                    if depth == "median":
+                        img, _, dmap, _, _ = splats.render_median_depth(cam, size, level=level, antialiased=antialiased)
+                    else:
+                        img, dmap, _ = splats.render_depth(cam, size, antialiased=antialiased)
                     imgs.append(img)
-                    depths.append(depth)
+                    depths.append(dmap)
                     m = getattr(v, "mask", None) if use_masks else None
                     masks.append(None if m is None else torch.from_numpy(np.ascontiguousarray(m)).to(self.device))
-                self.integrate(chunk, imgs, depths, masks=masks, alpha_min=alpha_min, max_depth=max_depth, near=near)
+                self.integrate(chunk, imgs, depths, masks=masks, alpha_min=alpha_min, max_depth=max_depth, near=near,
+                               depth_kind="metric" if depth == "median" else "accumulated")
 
     def extract_mesh(self, min_views: int = 2):
         """The surface sdf = 0 as an indexed triangle mesh (brush_amd.mesh.Mesh, host arrays): marching tetrahedra over

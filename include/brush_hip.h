@@ -729,6 +729,31 @@ int brush_render_error_scores(const BrushUniforms *h_uniforms, const BrushAux *h
                               const float *error_map /* [h,w] */, uint64_t *view_err /* [N] */, uint32_t n,
                               brush_stream_t stream);
 
+/* ---- median depth and the splat under a pixel (build extension; the depth 2DGS, GOF, RaDe-GS and gsplat's 2DGS path
+ *      fuse into their meshes) -------------------------------------------------------------------------------------- */
+/* Replays the compositing walk of a FINISHED brush_render_forward_depth over the tile lists it left in the aux
+ * (projected_splats, tile_bins, compact_gid_from_isect, global_from_compact_gid, num_visible: what
+ * brush_render_contributions reads, without final_index) and picks, per pixel, the MEDIAN entry: the first entry the
+ * forward ADDED after which the transmittance is at or below t_level,
+ *   next_T = T (1 - alpha) <= t_level,   t_level = 1.0f - level   (one f32 subtraction, on the host),
+ * i.e. the splat at which the accumulated opacity 1 - T first reaches `level` (0.5: the median).  The comparison is
+ * `<=`: an entry that takes T to exactly t_level is the median.  An entry that ends the pixel without being added (the
+ * stop quirk, rasterize.wgsl:88-91) is never the median, and a pixel keeps its FIRST crossing.  Per pixel the walk
+ * repeats the forward's float operations, in both BRUSH_AUX_DETERMINISTIC settings and with BRUSH_AUX_ANTIALIASED (word
+ * 8 of a projected row already holds the compensated opacity), so at level 0.5 a pixel has a median exactly where the
+ * forward's alpha is >= 0.5.
+ *   out_depth[p]  [h][w] f32: the bits of compact_depth[c] of the median entry's compact id c (compact_depth: what that
+ *                 forward left, the camera-space z of every visible splat's mean), or 0.0f when no entry crosses;
+ *   out_id[p]     [h][w] i32 or NULL: the median entry's GLOBAL id, or -1.
+ * Every in-frame pixel is written on every call, empty tiles and n == 0 (no list is read then) included; nothing is
+ * accumulated, every pixel has one writer: bitwise repeatable.  No interpolation between the entries around the
+ * crossing, no gradient.  level must be finite with 0 < level < 1; a NULL required pointer, a pointer that is not
+ * 4-byte aligned or tile_bounds that do not belong to img_size return BRUSH_ERR_INVALID_ARG before any device work.  No
+ * workspace, no allocation, no synchronisation: graph-capturable. */
+int brush_render_median_depth(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                              const float *compact_depth /* [N] */, float level, float *out_depth /* [h,w] */,
+                              int32_t *out_id /* [h,w] or NULL */, uint32_t n, brush_stream_t stream);
+
 /* ---- 3D smoothing filter (build extension; Mip-Splatting, Yu et al. 2024, is the model) ------------------------- */
 /* The world-space half of Mip-Splatting: every splat is low-passed at the highest rate any training view sampled it.
  * A splat carries a filter length f; the renderer sees the covariance Sigma + f^2 I and the opacity scaled by
@@ -833,6 +858,16 @@ typedef struct BrushTsdfViewData {
 int brush_tsdf_integrate(const BrushTsdfGrid *h_grid, uint32_t *volume, const BrushFilterView *views,
                          const BrushTsdfViewData *h_data, uint32_t num_views, float alpha_min, float max_depth,
                          float near_z, brush_stream_t stream);
+/* brush_tsdf_integrate with flags.  BRUSH_TSDF_DEPTH_METRIC: the view's depth map already holds a distance per pixel
+ * (a median depth map of brush_render_median_depth), so the line above reads
+ *   d = depth                                                         skip unless 0 < d <= max_depth
+ * and nothing else changes: the pixel is still used only where a = img.w >= alpha_min, and the colour is img[c] / a.
+ * flags == 0 is brush_tsdf_integrate bit for bit (which forwards here); any other bit returns BRUSH_ERR_INVALID_ARG
+ * before any device work. */
+#define BRUSH_TSDF_DEPTH_METRIC 1u
+int brush_tsdf_integrate_ex(const BrushTsdfGrid *h_grid, uint32_t *volume, const BrushFilterView *views,
+                            const BrushTsdfViewData *h_data, uint32_t num_views, float alpha_min, float max_depth,
+                            float near_z, uint32_t flags, brush_stream_t stream);
 /* The mesh: marching tetrahedra on the lattice of voxel centres.  A cell is the cube between lattice point (i, j, k)
  * and (i+1, j+1, k+1), corner c = bit 0: +x, bit 1: +y, bit 2: +z; it is cut into the six tetrahedra of the Kuhn
  * decomposition around the diagonal corner 0 - corner 7: tetrahedron number t = 0..5 is (0, 1 << a, 1 << a | 1 << b,

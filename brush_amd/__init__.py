@@ -52,6 +52,13 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 compositing walk; not differentiable (brush_amd/median_depth.py; build extension, the
                                 depth 2DGS, GOF and RaDe-GS fuse; Splats.render_median_depth,
                                 TsdfVolume.integrate_splats(depth="median"), `python -m brush_amd.mesh --depth median`)
+  render_features / splat_feature_sums / lift_labels / FeatureSums / features_from_aux / feature_grads_from_aux /
+  feature_sums_from_aux      <- per-splat feature vectors composited into an image (N-channel rasterisation, differentiable
+                                with respect to the features only: the geometry is frozen), and the transpose that lifts 2D
+                                feature maps or label images onto the splats as exact integer sums, from replays of the
+                                compositing walk (brush_amd/features.py; build extension, gsplat's N-channel rasterisation,
+                                LangSplat and FlashSplat are the models; Splats.render_features,
+                                `python -m brush_amd.lift`)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -90,6 +97,8 @@ _ERROR_SCORE_NAMES = ("ErrorScores", "ErrorScoreBuffers", "l1_error_map", "error
 _TSDF_NAMES = ("TsdfVolume", "TsdfArrays")
 # (brush_amd.mesh is a command line too: imported on first use, as brush_amd.eval is)
 _MEDIAN_DEPTH_NAMES = ("render_median_depth", "median_depth_from_aux")
+_FEATURE_NAMES = ("render_features", "splat_feature_sums", "lift_labels", "FeatureSums", "labels_from_sums",
+                  "features_from_aux", "feature_grads_from_aux", "feature_sums_from_aux")
 _MESH_NAMES = ("Mesh", "mesh_to_ply", "mesh_from_ply", "default_bounds", "grid_for")
 
 
@@ -118,6 +127,9 @@ def __getattr__(name):
     if name in _MEDIAN_DEPTH_NAMES:
         from . import median_depth as _median_depth
         return getattr(_median_depth, name)
+    if name in _FEATURE_NAMES:
+        from . import features as _features
+        return getattr(_features, name)
     if name in _MESH_NAMES:
         from . import mesh as _mesh
         return getattr(_mesh, name)

@@ -239,6 +239,12 @@ _SYMBOLS = [
     ("brush_render_error_scores", C.c_int, [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, C.c_uint32, _P]),
     ("brush_render_median_depth", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.c_float, _P, _P, C.c_uint32, _P]),
+    ("brush_render_features", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.c_uint32, _P, C.c_uint32, _P]),
+    ("brush_render_features_backward", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.c_uint32, _P, C.c_uint32, _P]),
+    ("brush_render_feature_sums", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P]),
     ("brush_filter3d_view_chunk", C.c_uint32, []),
     ("brush_filter3d_rates", C.c_int,
      [_P, C.c_uint32, _P, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),

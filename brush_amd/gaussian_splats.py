@@ -183,6 +183,17 @@ class Splats(torch.nn.Module):
                                    self.raw_opacity, level=level, antialiased=antialiased,
                                    max_intersects=max_intersects)
 
+    def render_features(self, camera: Camera, img_size, features, *, antialiased: bool = False, max_intersects=None):
+        """render() without autograd plus `features` (float32 [N,C], C <= 64) composited by the same blending weights
+        (features.render_features): (img [h,w,4], feat [h,w,C], aux).  The geometry is frozen: feat is differentiable
+        with respect to `features` only, img is detached."""
+        from .features import render_features
+
+        with torch.no_grad():
+            norm_rot = self._synced_norm_rotation()
+        return render_features(camera, img_size, self.means, self.log_scales, norm_rot, self.sh_coeffs,
+                               self.raw_opacity, features, antialiased=antialiased, max_intersects=max_intersects)
+
     def render_pose(self, camera: Camera, img_size, viewmat, max_intersects=None, antialiased: bool = False,
                     depth: bool = False):
         """render() / render_depth() through the explicit world-to-camera matrix `viewmat` (float32 [4,4] CPU tensor),

@@ -754,6 +754,48 @@ int brush_render_median_depth(const BrushUniforms *h_uniforms, const BrushAux *h
                               const float *compact_depth /* [N] */, float level, float *out_depth /* [h,w] */,
                               int32_t *out_id /* [h,w] or NULL */, uint32_t n, brush_stream_t stream);
 
+/* ---- per-splat features through the compositing walk (build extension; gsplat's N-channel rasterisation is the model,
+ *      LangSplat / Feature-3DGS / Gaussian Grouping / FlashSplat are the uses) ---------------------------------------- */
+/* Three replays of the compositing walk of a FINISHED forward over the tile lists it left in the aux (projected_splats,
+ * tile_bins, compact_gid_from_isect, global_from_compact_gid, num_visible: what brush_render_error_scores reads).  A
+ * "hit" is an entry the forward ADDED to the pixel, fac = alpha T its blending weight; per pixel the walk repeats the
+ * forward's float operations (the stop quirk included, which contributes nothing), in both BRUSH_AUX_DETERMINISTIC
+ * settings and with BRUSH_AUX_ANTIALIASED.  C channels, 1 <= C <= BRUSH_FEATURE_MAX_CHANNELS, walked in passes of at most
+ * 16 (one launch per pass).  The geometry is FROZEN: none of the three produces a gradient for it.
+ * brush_render_features: features [N][C] f32, row-major, indexed by GLOBAL id; out [h][w][C] f32, pixel-major, row pitch
+ *   w C (NOT tile-padded).  In list order every hit does out[p][c] = fmaf(features[g][c], fac, out[p][c]): the
+ *   forward's own association, so the drawn colours (or compact_depth scattered to global ids) as features reproduce
+ *   the forward's rgb (or out_depth) bit for bit.  Every in-frame pixel writes all C channels exactly once, +0.0f where
+ *   nothing was added, empty tiles and n == 0 (no list is read then; features may be NULL) included.  No atomics:
+ *   bitwise repeatable.
+ * brush_render_features_backward: the transpose.  v_out [h][w][C] f32, arbitrary;
+ *   v_features[g][c] += sum over the pixels p the forward added g to of fac v_out[p][c]
+ *   with hardware float atomics, one instruction per (record, 8x8 quadrant, pass) on consecutive words of the row.  The
+ *   entry only ACCUMULATES into v_features [N][C] f32, which the caller zeroes.  ORDER DEPENDENT in its last bits.
+ * brush_render_feature_sums: the exact transpose of maps in [0, 1].  map_kind BRUSH_FEATURE_MAP_F32: maps [h][w][C] f32,
+ *   every value clamped, m = min(max(M, 0), 1): a NaN and every negative value count as 0, everything above 1 as 1.
+ *   BRUSH_FEATURE_MAP_LABEL_U8: maps [h][w] u8, channel c's map is `label == c`; a label >= C belongs to no class (255:
+ *   "ignore").
+ *   sums[g][c] += sum over the pixels the forward added g to of (uint32) rint((fac m[p][c]) 2^24)
+ *   (fac m: one f32 product; the scale is exact; ties to even) as exact 64-bit integers, into sums [N][C] u64 (8-byte
+ *   aligned), which the caller zeroes.  With C = 1 it is brush_render_error_scores bit for bit; a label image gives the
+ *   bits of its one-hot f32 maps.  Order independent: the same inputs give the same bits on every run.
+ * All three: a NULL required pointer, a misaligned one (f32: 4 bytes, sums: 8), C outside [1, 64], another map_kind or
+ * tile_bounds that do not belong to img_size return BRUSH_ERR_INVALID_ARG before any device work; with n == 0 the
+ * forward still writes zeros and the other two return BRUSH_OK and launch nothing.  Device pointers except the two
+ * structs.  No workspace, no allocation, no synchronisation: graph-capturable. */
+#define BRUSH_FEATURE_MAX_CHANNELS 64u
+#define BRUSH_FEATURE_MAP_F32 0u
+#define BRUSH_FEATURE_MAP_LABEL_U8 1u
+int brush_render_features(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *features /* [N,C] */,
+                          uint32_t C, float *out /* [h,w,C] */, uint32_t n, brush_stream_t stream);
+int brush_render_features_backward(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                                   const float *v_out /* [h,w,C] */, uint32_t C, float *v_features /* [N,C] */,
+                                   uint32_t n, brush_stream_t stream);
+int brush_render_feature_sums(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                              const void *maps /* [h,w,C] f32 or [h,w] u8 */, uint32_t map_kind, uint32_t C,
+                              uint64_t *sums /* [N,C] */, uint32_t n, brush_stream_t stream);
+
 /* ---- 3D smoothing filter (build extension; Mip-Splatting, Yu et al. 2024, is the model) ------------------------- */
 /* The world-space half of Mip-Splatting: every splat is low-passed at the highest rate any training view sampled it.
  * A splat carries a filter length f; the renderer sees the covariance Sigma + f^2 I and the opacity scaled by

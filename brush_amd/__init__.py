@@ -59,6 +59,12 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 compositing walk (brush_amd/features.py; build extension, gsplat's N-channel rasterisation,
                                 LangSplat and FlashSplat are the models; Splats.render_features,
                                 `python -m brush_amd.lift`)
+  splat_normals / depth_normals / normal_loss_into / normal_consistency_loss / render_normals  <- per-splat normals
+                                (the shortest axis, facing the camera), the normals a rendered depth map implies, and the
+                                depth-normal consistency loss between the rendered normal map and them
+                                (brush_amd/normal_loss.py; build extension, 2DGS, GOF, RaDe-GS and PGSR are the models;
+                                Splats.render_normals, TrainConfig.normal_weight,
+                                `python -m brush_amd.train_loop --normal-weight`)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -78,6 +84,8 @@ from . import dataset  # noqa: F401
 # reachable as `from brush_amd.depth_loss import ...`)
 from .depth_loss import depth_loss, depth_loss_into  # noqa: F401
 from .compose import as_background, compose, compose_backward, compose_forward  # noqa: F401  (as depth_loss above)
+from .normal_loss import (depth_normals, normal_consistency_loss, normal_loss_into, render_normals,  # noqa: F401
+                          splat_normals)
 from .pyramid import area_resize, downscaled_size, nearest_resize  # noqa: F401
 from .filter3d import apply_filter3d, filter3d_rates  # noqa: F401
 from .undistort import (Distortion, fit_scale, undistort_dataset, undistort_depth, undistort_image,  # noqa: F401

@@ -106,6 +106,11 @@ class BrushDepthLoss(C.Structure):
     ]
 
 
+class BrushNormalLoss(C.Structure):
+    """Per-call configuration of brush_normal_loss (include/brush_hip.h: BrushNormalLoss)."""
+    _fields_ = [("weight", C.c_float), ("alpha_min", C.c_float)]
+
+
 class BrushUndistort(C.Structure):
     """The map of brush_undistort_u8 / brush_undistort_nearest (include/brush_hip.h: BrushUndistort)."""
     _fields_ = [(name, C.c_float) for name in ("fx", "fy", "cx", "cy", "iofx", "iofy", "ocx", "ocy", "k1", "k2", "k3",
@@ -245,6 +250,11 @@ _SYMBOLS = [
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.c_uint32, _P, C.c_uint32, _P]),
     ("brush_render_feature_sums", C.c_int,
      [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P]),
+    ("brush_splat_normals", C.c_int, [C.POINTER(BrushUniforms), _P, _P, _P, C.c_uint32, _P, _P]),
+    ("brush_splat_normals_backward", C.c_int, [C.POINTER(BrushUniforms), _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    ("brush_normal_loss_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("brush_normal_loss", C.c_int,
+     [C.POINTER(BrushUniforms), _P, _P, _P, C.POINTER(BrushNormalLoss), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     ("brush_filter3d_view_chunk", C.c_uint32, []),
     ("brush_filter3d_rates", C.c_int,
      [_P, C.c_uint32, _P, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),

@@ -9,12 +9,17 @@ Command line (prints one line per view, then the means):
     python -m brush_amd.eval SPLATS DATASET [--format auto|nerf|colmap] [--eval-split-every K]
                              [--max-resolution R] [--num-frames K] [--seed S] [--window 11] [--json OUT]
                              [--depth-metrics] [--depth-mode depth|disparity] [--downscale 1,2,4,8]
-                             [--depth-dir DIR [--depth-median]]
+                             [--depth-dir DIR [--depth-median]] [--normal-dir DIR]
                              [--background white|black|R,G,B] [--no-masks]
 
 --background white scores over a white background (the protocol of the NeRF-synthetic numbers in the literature): the
 render and the image's straight RGBA are composed over the colour first (brush_amd/compose.py).  A view's loss mask
 (nerfstudio's mask_path, COLMAP's masks/<image name>.png) leaves its zero pixels out of the PSNR unless --no-masks.
+
+--normal-dir DIR writes two camera-space normal maps per eval view (brush_amd/normal_loss.py): <stem>_normal.npy, the
+rendered map of the splats' normals divided by its length where alpha >= 0.5 (0 elsewhere), and <stem>_normal_depth.npy,
+the normals of the surface the rendered depth map implies (0 where a pixel or a neighbour is not covered); both f32
+[h,w,3], facing the camera (z < 0).
 
 --downscale 1,2,4,8 is Mip-Splatting's multi-scale protocol: the views are scored once per scale, rendered at 1 / scale
 of their size against the image area-filtered to that size on the device (brush_amd/pyramid.py); one block of lines per
@@ -289,6 +294,33 @@ def write_depth_maps(splats, views, out_dir: str, median: bool = False):
     return paths
 
 
+def write_normal_maps(splats, views, out_dir: str, antialiased: bool = False):
+    """For each view: <stem>_normal.npy, the rendered normal map (Splats.render_normals) divided by its length where
+    alpha >= 0.5, 0 elsewhere, and <stem>_normal_depth.npy, the normals the rendered depth map implies
+    (normal_loss.depth_normals, alpha_min 0.5; 0 where invalid); both f32 [h,w,3], camera space.  Returns the written
+    paths."""
+    import os
+
+    from .normal_loss import depth_normals
+
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    with torch.no_grad():
+        for v in views:
+            h, w = int(v.image.shape[0]), int(v.image.shape[1])
+            img, depth, nimg, _ = splats.render_normals(v.camera, (w, h), antialiased=antialiased)
+            length = torch.sqrt((nimg * nimg).sum(dim=2, keepdim=True))
+            keep = (img[..., 3:4] >= 0.5) & (length > 0)
+            unit = torch.where(keep, nimg / torch.where(keep, length, torch.ones_like(length)), torch.zeros_like(nimg))
+            from_depth, _ = depth_normals(v.camera, (w, h), img, depth, alpha_min=0.5)
+            stem = os.path.splitext(os.path.basename(v.name))[0]
+            for suffix, t in (("_normal.npy", unit), ("_normal_depth.npy", from_depth)):
+                path = os.path.join(out_dir, stem + suffix)
+                np.save(path, t.cpu().numpy().astype(np.float32))
+                paths.append(path)
+    return paths
+
+
 def zoomed_camera(camera, img_size, zoom: float):
     """`camera` with `zoom` times its focal lengths on an image of the same size and the same principal point: the
     central 1 / zoom of the view, magnified (a zoom-in no training view sampled, which is what the 3D smoothing filter
@@ -373,6 +405,10 @@ def parser():
     p.add_argument("--depth-median", action="store_true",
                    help="--depth-dir: also write every eval view's median depth (<view stem>_depth_median.npy: the z "
                         "of the splat at which the accumulated opacity first reaches one half, 0 where it never does)")
+    p.add_argument("--normal-dir", default=None,
+                   help="also write every eval view's rendered normal map (<view stem>_normal.npy, unit where alpha >= "
+                        "0.5, else 0) and the normals its depth map implies (<view stem>_normal_depth.npy) to this "
+                        "directory, f32 [h,w,3] in camera space")
     p.add_argument("--antialiased", action="store_true",
                    help="render in the antialiased mode (opacity compensation of the 2D blur), e.g. for splats "
                         "trained with it")
@@ -481,6 +517,8 @@ def main(argv=None) -> int:
                                "mean_psnr": st.mean_psnr(), "mean_ssim": st.mean_ssim()})
     if args.depth_dir:
         write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir, median=args.depth_median)
+    if args.normal_dir:
+        write_normal_maps(splats, [s.view for s in stats.samples], args.normal_dir, antialiased=args.antialiased)
     if args.zoom is not None:
         for path in write_zoomed_renders(splats, [s.view for s in stats.samples], args.zoom, args.image_dir,
                                          antialiased=args.antialiased, background=background):

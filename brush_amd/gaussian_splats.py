@@ -194,6 +194,16 @@ class Splats(torch.nn.Module):
         return render_features(camera, img_size, self.means, self.log_scales, norm_rot, self.sh_coeffs,
                                self.raw_opacity, features, antialiased=antialiased, max_intersects=max_intersects)
 
+    def render_normals(self, camera: Camera, img_size, *, antialiased: bool = False, max_intersects=None):
+        """render_depth() plus the rendered normal map (normal_loss.render_normals): (img [h,w,4], depth [h,w],
+        normals_img [h,w,3], aux).  img and depth are differentiable as render_depth()'s; normals_img is differentiable
+        with respect to the rotations ONLY (through the per-splat normals): its blending weights are frozen."""
+        from .normal_loss import render_normals
+
+        norm_rot = self._synced_norm_rotation()
+        return render_normals(camera, img_size, self.means, self.log_scales, norm_rot, self.sh_coeffs,
+                              self.raw_opacity, antialiased=antialiased, max_intersects=max_intersects)
+
     def render_pose(self, camera: Camera, img_size, viewmat, max_intersects=None, antialiased: bool = False,
                     depth: bool = False):
         """render() / render_depth() through the explicit world-to-camera matrix `viewmat` (float32 [4,4] CPU tensor),

@@ -405,7 +405,7 @@ class _RenderSplatsDepthFn(torch.autograd.Function):
         out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
                                     raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
                                     depth=depth, antialiased=holder["antialiased"])
-        holder["aux"] = aux
+        holder["aux"], holder["uniforms"] = aux, u  # (the uniforms: for replays of this forward, normal_loss.py)
         ctx.u, ctx.aux, ctx.ncoef = u, aux, sh_coeffs.shape[1]
         ctx.save_for_backward(means, log_scales, quats, raw_opacity, out, depth[1])
         return out, depth[0]

@@ -165,6 +165,21 @@ class TrainConfig:
     densify_growth: float = 0.05
     densify_max_splats: Optional[int] = None
     revised_opacity: bool = False
+    # Build extension: the depth-normal consistency loss of the surface-oriented trainers (brush_amd/normal_loss.py; 2DGS,
+    # GOF, RaDe-GS and PGSR are the models).  From step normal_from_step on (7000 is 2DGS's schedule: a hyper-parameter
+    # default, not a measured number) a step adds normal_weight * mean over all pixels of (alpha - Nr . Nd) to the loss:
+    # Nr the rendered map of the per-splat normals (their shortest axes, facing the camera), Nd the normal of the surface
+    # the rendered depth map implies, over the pixels with alpha >= normal_alpha_min whose four neighbours have it too.
+    # Needs no extra data.  The gradient reaches the rotations through the per-splat normals, and everything through the
+    # depth map and the alpha channel; the blending weights of Nr are frozen (a replay of the finished forward), and
+    # with `poses` the pose receives no gradient from this term's normals (the depth gradient reaches it as depth
+    # supervision's does).  The replay's transpose uses float atomics: a trajectory with the term on is NOT bitwise
+    # reproducible, in deterministic mode too.  Single-view.  Reads the RAW log-scales under the 3D filter (the shortest
+    # axis of Sigma + f^2 I is that of Sigma).  0 (the default) or a step before normal_from_step is the step without the
+    # option, same path, bit for bit.  DESIGN §8 row 22.
+    normal_weight: float = 0.0
+    normal_from_step: int = 7000
+    normal_alpha_min: float = 0.5
 
     def check(self, multi_rank: bool = False):
         """A ValueError naming the first thing wrong with the configuration, before anything touches a dataset or a
@@ -178,6 +193,7 @@ class TrainConfig:
             raise ValueError(f"TrainConfig.depth_mode must be 'depth' or 'disparity', got {self.depth_mode!r}")
         if self.depth_weight < 0 or (self.depth_weight_final or 0.0) < 0:
             raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
+        self.check_normal()
         self.check_downscale_schedule()
         prune_at = self.check_contribution_prune()
         if prune_at and self.strategy == "mcmc":
@@ -202,6 +218,16 @@ class TrainConfig:
                                                  "refined exposure maps")):
                 if on:
                     raise ValueError(f"TrainConfig.densify_by='error' cannot be combined with {what}")
+
+    def check_normal(self):
+        """A ValueError naming what is wrong with the normal-consistency fields."""
+        w, s, a = self.normal_weight, self.normal_from_step, self.normal_alpha_min
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not (math.isfinite(w) and w >= 0.0):
+            raise ValueError(f"TrainConfig.normal_weight must be finite and >= 0, got {w!r}")
+        if isinstance(s, bool) or not isinstance(s, int) or s < 0:
+            raise ValueError(f"TrainConfig.normal_from_step must be an integer >= 0, got {s!r}")
+        if isinstance(a, bool) or not isinstance(a, (int, float)) or not (math.isfinite(a) and a > 0.0):
+            raise ValueError(f"TrainConfig.normal_alpha_min must be finite and > 0, got {a!r}")
 
     def check_densify(self):
         """A ValueError naming what is wrong with the densification fields."""
@@ -371,7 +397,8 @@ def l1_ssim_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_weight: float, windo
 
 def optimizer_path(exchange: bool, grad_sync: bool, fused_backward: bool, mcmc: bool, depth: bool,
                    filter3d: bool) -> str:
-    """Which way a step's gradients reach Adam, from what the step was given (depth: an active depth term; filter3d: a
+    """Which way a step's gradients reach Adam, from what the step was given (depth: an active depth term or an active
+    normal-consistency term, which hands the backward a depth gradient too; filter3d: a
     3D filter is set).  "records": the views' gradient records are exchanged and reduced into Adam (brush_amd.dist).
     "fused": Adam runs inside the backward's last kernel (brush_render_backward_adam[_pose]).  "separate": the dense
     backward, then brush_adam_step; what needs the dense gradients between the two (grad_sync, the mcmc regularisers,
@@ -656,6 +683,10 @@ class SplatTrainer:
             return c.depth_weight  # (an exponential ramp needs two positive ends)
         return self._decayed(c.depth_weight, c.depth_weight_final / c.depth_weight)
 
+    def _normal_active(self) -> bool:
+        """Whether the coming step carries the normal-consistency term (TrainConfig.normal_weight / normal_from_step)."""
+        return self.config.normal_weight > 0.0 and self.iter >= self.config.normal_from_step
+
     def _check_step(self, grad_sync, exchange, view_index, poses, exposures, gt_depth):
         """Refuses the combinations of step's arguments and the configuration that no path serves, before anything is
         touched (neither the trainer's state nor the splats are looked at)."""
@@ -667,6 +698,7 @@ class SplatTrainer:
             # what is single-view, in the order it is refused in; a new single-view option is one more row
             for on, what in ((self.filter3d is not None, "the 3D filter"),
                              (gt_depth is not None, "depth supervision"),
+                             (self._normal_active(), "the normal-consistency term"),
                              (c.strategy == "mcmc", "the mcmc strategy"),
                              (poses is not None, "pose refinement"),
                              (exposures is not None, "exposure compensation")):
@@ -742,9 +774,10 @@ class SplatTrainer:
         self._store_rotation(splats, next_rot)
 
     def _update_separate(self, cfg, size, params, norm_rot, fwd, want_stats, pose, stream, effective, depth_grad,
-                         grad_sync, batch_views, scene_extent):
-        """Separate calls: the dense backward, then whatever works on dense gradients (the 3D filter's VJP, grad_sync,
-        the refinement statistics, the mcmc regularisers), then brush_adam_step on every splat."""
+                         grad_sync, batch_views, scene_extent, normal_grad=None):
+        """Separate calls: the dense backward, then whatever works on dense gradients (the splat-normal VJP of an active
+        normal-consistency term, the 3D filter's VJP, grad_sync, the refinement statistics, the mcmc regularisers), then
+        brush_adam_step on every splat.  normal_grad: None or the [N,3] gradient at the per-splat normals."""
         c = self.config
         use_mcmc = c.strategy == "mcmc"
         means, log_scales, quats, raw_opac, sh = params
@@ -753,6 +786,9 @@ class SplatTrainer:
         eff_scales, eff_opac = effective
         grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
                                         depth=depth_grad, pose=pose)
+        if normal_grad is not None:  # the rendered normal map's gradient -> the quaternions the forward was fed
+            from .normal_loss import splat_normals_backward_into
+            splat_normals_backward_into(u, means, log_scales, norm_rot, normal_grad, grads["v_quats"])
         if self.filter3d is not None:  # gradients at the effective parameters -> at the raw ones, in place
             F3.backward_into(log_scales, raw_opac, self.filter3d, n, grads["v_scales"], grads["v_opac"], stream)
         if grad_sync is not None:  # view-sharded data parallelism: sum the per-view gradients
@@ -829,15 +865,25 @@ class SplatTrainer:
         and `exposures` (_check_step); TrainConfig.antialiased is refused with `exchange` alone.  The optimizer path
         (optimizer_path): the records path with `exchange`; the separate-call path (backward, then brush_adam_step)
         with `grad_sync`, strategy "mcmc", an active depth term or a 3D filter, whatever `fused_backward` says;
-        otherwise the fused path (brush_render_backward_adam[_pose]) unless `fused_backward` is False."""
+        otherwise the fused path (brush_render_backward_adam[_pose]) unless `fused_backward` is False.
+        TrainConfig.normal_weight > 0 from step normal_from_step on (the depth-normal consistency term, single-view,
+        separate-call path): the view is rendered with its depth output; after the colour loss brush_splat_normals on
+        the rotations the forward was fed and the feature replay of that forward give the rendered normal map,
+        brush_normal_loss adds its alpha gradient into the colour loss's gradient and the term (weight / batch_views)
+        into the step's loss, its depth gradient is summed with the depth term's when both are on, the replay's
+        transpose gives the gradient at the per-splat normals and brush_splat_normals_backward adds it into v_quats
+        behind the render backward.  The replay's blending weights are frozen; with `poses` the pose gets no gradient
+        through the normals; the transpose's float atomics make the trajectory order dependent in its last bits, in
+        deterministic mode too.  Before normal_from_step, or with weight 0, the step is the one without the option."""
         c = self.config
         self._check_step(grad_sync, exchange, view_index, poses, exposures, gt_depth)
         use_mcmc = c.strategy == "mcmc"
         filt = self.filter3d
         depth_w = self._depth_weight() if gt_depth is not None else 0.0
         use_depth = depth_w > 0.0
-        path = optimizer_path(exchange is not None, grad_sync is not None, self.fused_backward, use_mcmc, use_depth,
-                              filt is not None)
+        use_normal = self._normal_active()
+        path = optimizer_path(exchange is not None, grad_sync is not None, self.fused_backward, use_mcmc,
+                              use_depth or use_normal, filt is not None)
         h, w = int(gt_image.shape[0]), int(gt_image.shape[1])
         n, ncoef = splats.num_splats(), int(splats.sh_coeffs.shape[1])
         if self.moment1.numel() != n * (11 + 3 * ncoef):
@@ -867,7 +913,8 @@ class SplatTrainer:
             poses.apply(view_index)  # the update this view's previous draw left
             viewmat = poses.viewmat(view_index, camera).numpy()
             pose = R.pose_buffers(n, means.device)
-        depth_bufs = R._depth_buffers(n, (w, h), means.device) if use_depth else None  # (depth map, compact depth)
+        # (depth map, compact depth)
+        depth_bufs = R._depth_buffers(n, (w, h), means.device) if use_depth or use_normal else None
         # the renderer sees the effective log-scales and opacities; everything else keeps reading the raw ones
         effective = (log_scales, raw_opac)
         if filt is not None:
@@ -885,6 +932,18 @@ class SplatTrainer:
                                          scale=depth_scale, offset=depth_offset, alpha_min=c.depth_alpha_min,
                                          mode=c.depth_mode, loss_accum=loss)
             depth_grad = (depth_bufs[1], v_depth)
+        normal_grad = None
+        if use_normal:  # on the same raw render; the raw log-scales pick the axis (see TrainConfig)
+            from .features import feature_grads_from_aux, features_from_aux
+            from .normal_loss import normal_loss_into, splat_normals_from
+            normals_img = features_from_aux(u, aux, splat_normals_from(u, means, log_scales, norm_rot))
+            v_depth, v_normals_img, _ = normal_loss_into(u, pred, depth_bufs[0], normals_img, v_pred,
+                                                         weight=c.normal_weight / batch_views,
+                                                         alpha_min=c.normal_alpha_min, loss_accum=loss,
+                                                         v_depth_accum=None if depth_grad is None else depth_grad[1])
+            depth_grad = (depth_bufs[1], v_depth)
+            normal_grad = torch.zeros((n, 3), dtype=torch.float32, device=means.device)
+            feature_grads_from_aux(u, aux, v_normals_img, normal_grad)
         do_refine = self.will_refine()
         pre_step = None
         # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)
@@ -909,7 +968,7 @@ class SplatTrainer:
                 self._update_fused(splats, cfg, (w, h), params, norm_rot, fwd, want_stats, pose, stream)
             else:
                 self._update_separate(cfg, (w, h), params, norm_rot, fwd, want_stats, pose, stream, effective,
-                                      depth_grad, grad_sync, batch_views, scene_extent)
+                                      depth_grad, grad_sync, batch_views, scene_extent, normal_grad)
         if pose is not None:
             poses.push(view_index, pose[0])
         self.opt_time += 1

@@ -16,6 +16,7 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased] [--pose-opt] [--export-cameras CAMS.json]
         [--strategy default|mcmc] [--cap-max 1000000] [--exposure-opt] [--export-exposures EXP.json]
         [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
+        [--normal-weight W] [--normal-from-step S]
         [--downscale-schedule STEP:FACTOR,...] [--num-downscales K] [--resolution-schedule S]
         [--contribution-prune-at STEP,...] [--contribution-prune-min 0.01]
         [--background white|black|random|R,G,B] [--no-masks] [--filter3d] [--filter3d-every 100]
@@ -52,6 +53,11 @@ the pairs (i S, 2^(K - i)) for i = 0..K.  Evals render at the eval views' full s
 depths/<image stem>.png|.npy): W times the mean absolute difference of depth / alpha (--depth-mode disparity: alpha /
 depth, for maps that hold inverse depths) is added to the loss of every view that has a map (TrainConfig.depth_weight,
 brush_amd/depth_loss.py).  --depth-weight-final W2 moves the weight exponentially from W to W2 over the run.
+
+--normal-weight W > 0 adds the depth-normal consistency loss of the surface-oriented trainers from step
+--normal-from-step on (TrainConfig.normal_weight, brush_amd/normal_loss.py): W times the mean over all pixels of
+alpha - Nr . Nd, Nr the rendered map of the splats' normals, Nd the normal the rendered depth map implies.  It needs no
+extra data; a run with it is not bitwise reproducible (float atomics in the gradient of Nr).
 
 --strategy mcmc trains with a fixed splat budget of --cap-max (TrainConfig.strategy, brush_amd/mcmc.py) instead of the
 clone / split / prune refinement.
@@ -114,6 +120,7 @@ class TrainLog:
     filter3d_refreshes: List[int] = field(default_factory=list)  # the steps in front of which the filter was recomputed
     densify_by: str = "grad"                      # TrainConfig.densify_by as configured
     error_passes: List[Tuple[int, int]] = field(default_factory=list)  # (step, views): the score passes that ran
+    normal_weight: float = 0.0                    # TrainConfig.normal_weight as configured (0: the term was off)
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
@@ -125,6 +132,7 @@ class TrainLog:
                 "masked_views": int(self.masked_views), "filter3d": bool(self.filter3d),
                 "filter3d_refreshes": [int(s) for s in self.filter3d_refreshes],
                 "densify_by": self.densify_by, "error_passes": [[int(s), int(v)] for s, v in self.error_passes],
+                "normal_weight": float(self.normal_weight),
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -214,7 +222,8 @@ class TrainLoop:
         self.log = TrainLog(self.steps, np.zeros(0, np.float32), image_bytes=self.loader.total_bytes,
                             background=self.config.background,
                             masked_views=sum(m is not None for m in self.loader.masks),
-                            filter3d=bool(self.config.filter3d), densify_by=self.config.densify_by)
+                            filter3d=bool(self.config.filter3d), densify_by=self.config.densify_by,
+                            normal_weight=float(self.config.normal_weight))
         # error-driven densification: a host generator of its own picks the views of a score pass (the loader's draw
         # order does not change), and a fixed background colour goes to the device here, once
         self._score_rng, self._score_bg = None, None
@@ -497,6 +506,10 @@ def parser():
                    help="supervise the rendered depth with the dataset's depth maps, with this weight (0: off)")
     p.add_argument("--depth-weight-final", type=float, default=None, metavar="W",
                    help="move the depth weight exponentially from --depth-weight to this value over the run")
+    p.add_argument("--normal-weight", type=float, default=0.0, metavar="W",
+                   help="add the depth-normal consistency loss with this weight (0: off)")
+    p.add_argument("--normal-from-step", type=int, default=TrainConfig.normal_from_step, metavar="S",
+                   help="--normal-weight: the first step that carries the term")
     p.add_argument("--depth-mode", choices=("depth", "disparity"), default="depth",
                    help="compare depth / alpha, or alpha / depth (the maps then hold inverse depths)")
     p.add_argument("--downscale-schedule", default=None, metavar="STEP:FACTOR,...",
@@ -559,7 +572,8 @@ def main(argv=None) -> int:
                              use_masks=not args.no_masks, filter3d=args.filter3d, filter3d_every=args.filter3d_every,
                              densify_by=args.densify_by, densify_error_thresh=args.densify_error_thresh,
                              densify_error_views=args.densify_error_views, densify_growth=args.densify_growth,
-                             densify_max_splats=args.max_splats, revised_opacity=args.revised_opacity)
+                             densify_max_splats=args.max_splats, revised_opacity=args.revised_opacity,
+                             normal_weight=args.normal_weight, normal_from_step=args.normal_from_step)
         config.check()  # the configuration the run trains with, before the dataset is loaded
     except ValueError as e:
         p.error(str(e))

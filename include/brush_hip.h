@@ -796,6 +796,57 @@ int brush_render_feature_sums(const BrushUniforms *h_uniforms, const BrushAux *h
                               const void *maps /* [h,w,C] f32 or [h,w] u8 */, uint32_t map_kind, uint32_t C,
                               uint64_t *sums /* [N,C] */, uint32_t n, brush_stream_t stream);
 
+/* ---- normal maps and the depth-normal consistency loss (build extension; 2DGS, GOF, RaDe-GS and PGSR are the models) - */
+/* L_n = sum_i w_i (1 - n_i . N): n_i the normal of splat i, w_i = alpha_i T_i its blending weight, N the normal of the
+ * surface the rendered depth map implies.  Rendered through brush_render_features (C = 3) on the per-splat normals, the
+ * sum over the splats is A - Nr . N per pixel, A the alpha and Nr the rendered normal map of the same forward.
+ * Every per-element result is defined operation by operation in f32 (one rounding per operation, no contraction, IEEE
+ * division and square root); brush_amd/csrc/normal_loss.hip states the order once.  dot(a, b) = (a0 b0 + a1 b1) + a2 b2,
+ * W[r][c] = viewmat[4 c + r], t[r] = viewmat[12 + r] (column-major, as BrushUniforms stores it).
+ * brush_splat_normals: normals_out [N][3] f32, every row written (splats that will not be visible too).  k = the index
+ *   of the smallest log-scale (the lowest index among equals), a = column k of the rotation matrix of quats[g] (w, x, y,
+ *   z: the unit quaternion the forward is fed), n_c = W a, p_c = W mean + t, s = dot(n_c, p_c) > 0 ? -1 : +1; the row is
+ *   s n_c, a camera-space normal that faces the camera.
+ * brush_splat_normals_backward: k and s recomputed, v_a = s W^T v_normals[g], the VJP of the rotation matrix with v_a
+ *   in column k and zeros elsewhere is ADDED into v_quats [N][4]: the gradient at the 4-vector the forward was fed, the
+ *   convention of brush_render_backward's v_quats (BrushAdamConfig::rotation_grad_wrt_normalized).  k and s are
+ *   piecewise constant: nothing goes to the scales or the means.
+ * Both: one lane per splat, n == 0 returns BRUSH_OK without reading the pointers (uniforms excepted).
+ * brush_normal_loss: w, h, focal and pixel_center come from `uniforms`.  pred [h][w][4] f32 (alpha A read), depth
+ *   [h][w] f32 (the accumulated depth D of brush_render_forward_depth), normals_img [h][w][3] f32 (Nr).  A pixel COUNTS
+ *   when A >= alpha_min, D > 0 and both are finite; z = D / A, r = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1),
+ *   P = z r.  A pixel p is VALID when 1 <= x <= w - 2, 1 <= y <= h - 2, it and its four edge neighbours count and, with
+ *   tx = P(x+1,y) - P(x-1,y), ty = P(x,y+1) - P(x,y-1), c = ty x tx (a fronto-parallel plane gives (0, 0, -1)), |c|^2
+ *   is finite and > 0.  Nd = c / sqrt(|c|^2) -> depth_normals_out [h][w][3] (NULL to skip), zeros where invalid.
+ *   l(p) = A(p) - Nr(p) . Nd(p); loss = kappa sum_valid l, kappa = (float)(weight / (w h)) formed in double: the mean
+ *   runs over ALL pixels, as brush_depth_loss's.  stats[0] = (float)((double) kappa * sum (double) l), the sum in a fixed
+ *   order without atomics; stats[1] = (float)(valid pixels / (w h)); a non-NULL loss_accum receives += stats[0].
+ *   Gradients, each NULL to skip, every pixel of v_depth and v_normals_img written, zero outside their support:
+ *     v_normals_img(p) = -kappa Nd(p);  v_Nd = -kappa Nr(p);  v_c = (v_Nd - Nd (Nd . v_Nd)) / |c|
+ *     v_ty = tx x v_c,  v_tx = v_c x ty   (0 at invalid centres and off the frame)
+ *     v_P(q) = ((v_tx(x-1,y) - v_tx(x+1,y)) + v_ty(x,y-1)) - v_ty(x,y+1)       a gather: no float atomics
+ *     v_z(q) = v_P(q) . r(q);  v_depth(q) = v_z(q) / A(q) where q counts, else 0
+ *     v_pred[q].w += kappa [q valid] - v_z(q) D(q) / A(q)^2   where q is valid or beside a valid centre; every other word
+ *     of v_pred keeps its bits.
+ *   normals_img == NULL is the normals-only form: depth_normals_out and stats = {0, valid fraction}; the gradient
+ *   pointers and loss_accum must then be NULL.  pred / v_pred 16-byte aligned; no output may alias an input (the inputs
+ *   are read across tile seams); alpha_min > 0; w h in [1, 2^28).  workspace: brush_normal_loss_workspace_size(w, h)
+ *   bytes (8-byte aligned, at most 16 KiB), scratch.  Device pointers except `uniforms` and `cfg`.  No allocation, no
+ *   synchronisation: graph-capturable; the same inputs give the same bits on every call. */
+typedef struct BrushNormalLoss {
+    float weight, alpha_min;
+} BrushNormalLoss;
+int brush_splat_normals(const BrushUniforms *uniforms, const float *means, const float *log_scales, const float *quats,
+                        uint32_t n, float *normals_out /* [N,3] */, brush_stream_t stream);
+int brush_splat_normals_backward(const BrushUniforms *uniforms, const float *means, const float *log_scales,
+                                 const float *quats, uint32_t n, const float *v_normals /* [N,3] */,
+                                 float *v_quats /* [N,4], accumulated into */, brush_stream_t stream);
+int brush_normal_loss_workspace_size(uint32_t w, uint32_t h, size_t *bytes);
+int brush_normal_loss(const BrushUniforms *uniforms, const float *pred, const float *depth, const float *normals_img,
+                      const BrushNormalLoss *cfg, float *depth_normals_out, float *v_depth, float *v_normals_img,
+                      float *v_pred, float *stats, float *loss_accum, void *workspace, size_t workspace_bytes,
+                      brush_stream_t stream);
+
 /* ---- 3D smoothing filter (build extension; Mip-Splatting, Yu et al. 2024, is the model) ------------------------- */
 /* The world-space half of Mip-Splatting: every splat is low-passed at the highest rate any training view sampled it.
  * A splat carries a filter length f; the renderer sees the covariance Sigma + f^2 I and the opacity scaled by

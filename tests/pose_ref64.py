@@ -45,8 +45,16 @@ def view_of(u):
     return W, t
 
 
-def pose_terms64(u, means, log_scales, quats, v_xy, v_conic, v_z=None, v_comp=None):
+# Deliberate mistakes for the controls of tests/test_general_camera_cpu.py: each swaps W and W^T in one place, so it is
+# invisible where W is symmetric (the reference test camera's W = I) and wrong everywhere else.
+MUTATIONS = ("T=J.W^T",        # the backward's T = J W taken as J W^T
+             "v_J=v_T.W",      # the VJP through W of T = J W transposed: v_J = v_T W^T taken as v_T W
+             "v_t=W^T.sum")    # the translation gradient taken through W^T: W^T sum v_p, the world-frame sum v_means
+
+
+def pose_terms64(u, means, log_scales, quats, v_xy, v_conic, v_z=None, v_comp=None, mutate=None):
     """Per splat: (v_p parts [3 x [N,3]]: pixel, Jacobian, depth; J [N,2,3]; v_T [N,2,3]; mean [N,3])."""
+    assert mutate is None or mutate in MUTATIONS, mutate
     W, f, pc, img, p, scale, R, M, V = A._parts(u, means, log_scales, quats)
     n = p.shape[0]
     v_xy = np.asarray(v_xy, np.float64).reshape(n, 2)
@@ -69,9 +77,9 @@ def pose_terms64(u, means, log_scales, quats, v_xy, v_conic, v_z=None, v_comp=No
     a0, a1 = f[0] * v_xy[:, 0], f[1] * v_xy[:, 1]
     vpj = np.stack([a0 * rw, a1 * rw, -(a0 * p[:, 0] + a1 * p[:, 1]) * rw * rw], -1)
     J = A._jac(f, p, p[:, 0], p[:, 1])
-    T = J @ W
+    T = J @ (W.T if mutate == "T=J.W^T" else W)
     v_T = 2.0 * v_cov @ T @ V
-    v_J = v_T @ W.T
+    v_J = v_T @ (W if mutate == "v_J=v_T.W" else W.T)
     rz2, rz3 = 1 / z ** 2, 1 / z ** 3
     v_t = np.stack([-f[0] * rz2 * v_J[:, 0, 2], -f[1] * rz2 * v_J[:, 1, 2],
                     -f[0] * rz2 * v_J[:, 0, 0] + 2 * f[0] * p[:, 0] * rz3 * v_J[:, 0, 2]
@@ -82,23 +90,25 @@ def pose_terms64(u, means, log_scales, quats, v_xy, v_conic, v_z=None, v_comp=No
     return (vpj, v_t, vz), J, v_T, np.asarray(means, np.float64)
 
 
-def pose_grad64(u, means, log_scales, quats, v_xy, v_conic, v_z=None, v_comp=None, gids=None):
+def pose_grad64(u, means, log_scales, quats, v_xy, v_conic, v_z=None, v_comp=None, gids=None, mutate=None):
     """(v_viewmat [3,4], mag [3,4]).  v_xy [V,2], v_conic [V,3], v_z [V], v_comp [V] belong to the visible splats in
     compact order, `gids` [V] maps them to rows of means / log_scales / quats (None: the arrays are already per visible
-    splat).  Row r of the result is [d L / d W[r, :] | d L / d t[r]]."""
+    splat).  Row r of the result is [d L / d W[r, :] | d L / d t[r]].  `mutate`: one of MUTATIONS, for the controls."""
     if gids is not None:
         gids = np.asarray(gids).astype(np.int64)
         means, log_scales, quats = (np.asarray(a)[gids] for a in (means, log_scales, quats))
     out, mag = np.zeros((3, 4)), np.zeros((3, 4))
     if np.asarray(means).shape[0] == 0:
         return out, mag
-    parts, J, v_T, m = pose_terms64(u, means, log_scales, quats, v_xy, v_conic, v_z, v_comp)
+    parts, J, v_T, m = pose_terms64(u, means, log_scales, quats, v_xy, v_conic, v_z, v_comp, mutate)
     v_p = parts[0] + parts[1] + parts[2]
     a_p = np.abs(parts[0]) + np.abs(parts[1]) + np.abs(parts[2])
     out[:, :3] = np.einsum("na,nb->ab", v_p, m) + np.einsum("nra,nrb->ab", J, v_T)
     mag[:, :3] = np.einsum("na,nb->ab", a_p, np.abs(m)) + np.einsum("nra,nrb->ab", np.abs(J), np.abs(v_T))
     out[:, 3] = v_p.sum(0)
     mag[:, 3] = a_p.sum(0)
+    if mutate == "v_t=W^T.sum":
+        out[:, 3] = view_of(u)[0].T @ out[:, 3]
     return out, mag
 
 

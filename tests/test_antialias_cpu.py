@@ -18,11 +18,19 @@ def _uniforms(w, h, n):
     return pack_uniforms(cam, (w, h), 0, n)
 
 
-def _cases():
+CASES_SIZE = (160, 120)
+
+
+def cases_cloud():
+    return H.synthetic_cloud(4000, 0, seed=11, mean_mult=1.0)
+
+
+def _cases(u=None, cloud=None):
     """Splats of a synthetic cloud in front of the reference camera, clamp inactive, comp well inside (0, 1), scales
-    spread so that comp covers sub-pixel and large splats."""
-    cloud = H.synthetic_cloud(4000, 0, seed=11, mean_mult=1.0)
-    u = _uniforms(160, 120, cloud["means"].shape[0])
+    spread so that comp covers sub-pixel and large splats.  `u`, `cloud`: another camera's packed uniforms of a
+    CASES_SIZE frame and the cloud to take the splats from."""
+    cloud = cases_cloud() if cloud is None else cloud
+    u = _uniforms(*CASES_SIZE, cloud["means"].shape[0]) if u is None else u
     means = cloud["means"].astype(np.float64)
     ls = cloud["log_scales"].astype(np.float64)
     q = cloud["quats"].astype(np.float64)
@@ -51,7 +59,12 @@ def test_comp_vjp_matches_central_differences():
     inputs: truncation O(h^2) ~ 1e-12, cancellation ~ 1e-16 / 1e-6 = 1e-10 relative; the backward's 1e-6 added to comp
     in 0.5 / (comp + 1e-6) biases by at most 1e-6 / 0.02 = 5e-5 relative.  Tolerance: 2e-4 relative to the largest
     component of the splat's gradient, plus 1e-8 absolute."""
-    u, m, ls, q = _cases()
+    check_comp_vjp()
+
+
+def check_comp_vjp(u=None, cloud=None):
+    """The body of test_comp_vjp_matches_central_differences at the camera of the packed uniforms `u`."""
+    u, m, ls, q = _cases(u, cloud)
     rng = np.random.default_rng(3)
     v = rng.uniform(0.5, 1.5, m.shape[0])
     gm, gs, gq = A.comp_vjp64(u, m, ls, q, v)

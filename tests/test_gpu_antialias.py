@@ -95,18 +95,20 @@ def _args(t):
     return t["means"], t["xy"], t["log_scales"], t["quats"], t["sh"], t["raw_opac"]
 
 
-def _render(dev, cloud, w, h, det, aa, grad=False):
+def _render(dev, cloud, w, h, det, aa, grad=False, camera=None):
+    """`camera` (here and below): a brush_amd.Camera in place of the reference test camera."""
     import brush_amd
 
     t = _tensors(cloud, dev, grad)
-    img, aux = brush_amd.render_splats(_camera(w, h), (w, h), *_args(t), deterministic=det, antialiased=aa)
+    img, aux = brush_amd.render_splats(camera or _camera(w, h), (w, h), *_args(t), deterministic=det, antialiased=aa)
     return t, img, aux
 
 
-def _u(w, h, cloud):
+def _u(w, h, cloud, camera=None):
     from brush_amd.render import pack_uniforms, sh_degree_from_coeffs
 
-    return pack_uniforms(_camera(w, h), (w, h), sh_degree_from_coeffs(cloud["sh"].shape[1]), cloud["means"].shape[0])
+    return pack_uniforms(camera or _camera(w, h), (w, h), sh_degree_from_coeffs(cloud["sh"].shape[1]),
+                         cloud["means"].shape[0])
 
 
 def _np(t):
@@ -134,12 +136,16 @@ def _twin(cloud, aux):
 # ---------------------------------------------------------------------------- 1. per splat
 @pytest.mark.parametrize("kind", ["tiny_case", "basic_case", "ragged", "c1", "S1", "empty", "subpixel"])
 def test_word8_is_compensated_opacity_and_the_rest_unchanged(dev, kind):
+    check_word8(dev, kind, *_scene(kind))
+
+
+def check_word8(dev, kind, cloud, w, h, camera=None):
+    """The body of test_word8_is_compensated_opacity_and_the_rest_unchanged; returns the worst err / bound."""
     import torch
 
-    cloud, w, h = _scene(kind)
     with torch.no_grad():
-        _, _, a0 = _render(dev, cloud, w, h, False, False)
-        _, _, a1 = _render(dev, cloud, w, h, False, True)
+        _, _, a0 = _render(dev, cloud, w, h, False, False, camera=camera)
+        _, _, a1 = _render(dev, cloud, w, h, False, True, camera=camera)
     assert a1.antialiased and not a0.antialiased
     V = a1.read_num_visible()
     assert V == a0.read_num_visible()
@@ -147,9 +153,9 @@ def test_word8_is_compensated_opacity_and_the_rest_unchanged(dev, kind):
     assert _np(a0.projected_splats[:V, :8]).tobytes() == _np(a1.projected_splats[:V, :8]).tobytes()
     if kind == "empty":
         assert V == 0
-        return
+        return 0.0
     _, gid, o = _visible(a1)
-    u = _u(w, h, cloud)
+    u = _u(w, h, cloud, camera)
     want, bound = A.word8_bound(u, cloud["means"][gid], cloud["log_scales"][gid], cloud["quats"][gid],
                                 cloud["raw_opac"][gid])
     err = np.abs(o.astype(np.float64) - want)
@@ -159,6 +165,7 @@ def test_word8_is_compensated_opacity_and_the_rest_unchanged(dev, kind):
           f"intersections {a0.read_num_intersections()} -> {a1.read_num_intersections()}")
     assert (err <= bound).all(), (kind, float(err.max()), int((err > bound).sum()))
     assert a1.read_num_intersections() <= a0.read_num_intersections()
+    return float((err / bound).max())
 
 
 # ---------------------------------------------------------------------------- 2. image against the oracle's twin
@@ -175,21 +182,26 @@ def _check_against(kind, got, want, risk, tol):
     print(f"[{kind}] max|gpu - oracle twin| = {float(err.max()) if err.size else 0.0:.3e} "
           f"({int(risk.sum())} flip-risk px)")
     assert err.size == 0 or float(err.max()) <= tol, (kind, float(err.max()))
+    return (float(err.max()) if err.size else 0.0) / tol
 
 
 @pytest.mark.parametrize("det", [False, True])
 @pytest.mark.parametrize("kind", ["tiny_case", "basic_case", "ragged", "c1"])
 def test_image_matches_oracle_twin(dev, kind, det):
+    check_image_oracle_twin(dev, kind, det, *_scene(kind))
+
+
+def check_image_oracle_twin(dev, kind, det, cloud, w, h, camera=None):
+    """The body of test_image_matches_oracle_twin; returns the worst err / PIX_TOL."""
     import torch
 
-    cloud, w, h = _scene(kind)
     with torch.no_grad():
-        _, img, aux = _render(dev, cloud, w, h, det, True)
+        _, img, aux = _render(dev, cloud, w, h, det, True, camera=camera)
     tw = _twin(cloud, aux)
     o_out, o_aux = _oracle_twin(aux, tw)
     assert int(o_aux["num_visible"][0]) == aux.read_num_visible()
     risk = o_aux["flip_risk"].astype(bool)
-    _check_against(kind, _np(img), o_out, np.repeat(risk[..., None], 4, axis=2), PIX_TOL)
+    return _check_against(kind, _np(img), o_out, np.repeat(risk[..., None], 4, axis=2), PIX_TOL)
 
 
 @pytest.mark.parametrize("kind", ["tiny_case", "basic_case", "ragged", "c1"])
@@ -284,10 +296,10 @@ def _upstream(dev, w, h, seed):
     return (torch.rand((h, w, 4), generator=g) - 0.5).to(dev)
 
 
-def _grads(dev, cloud, w, h, det, v_out):
+def _grads(dev, cloud, w, h, det, v_out, camera=None):
     import torch
 
-    t, img, aux = _render(dev, cloud, w, h, det, True, grad=True)
+    t, img, aux = _render(dev, cloud, w, h, det, True, grad=True, camera=camera)
     ps = [t["means"], t["xy"], t["log_scales"], t["quats"], t["sh"], t["raw_opac"]]
     g = torch.autograd.grad([img], ps, [v_out])
     return dict(zip(GRADS, (_np(x) for x in g))), img, aux
@@ -299,11 +311,15 @@ def test_backward_against_oracle_twin(dev, kind, det):
     """Expected: the oracle's backward of the twin, plus dL/do * sigmoid * d comp / d theta (aa_ref64), with
     dL/do = v_raw' / (o (1 - o)); for the opacity v_raw = dL/do * comp * sigmoid (1 - sigmoid).  Tolerances of the
     golden gate (test_gpu_depth.py: test_backward_against_oracle)."""
+    check_backward_oracle_twin(dev, kind, det, *_scene(kind))
+
+
+def check_backward_oracle_twin(dev, kind, det, cloud, w, h, camera=None):
+    """The body of test_backward_against_oracle_twin; returns the worst err/tol per gradient."""
     from brush_amd.render import uniforms_to_numpy
 
-    cloud, w, h = _scene(kind)
     v_out = _upstream(dev, w, h, seed=6)
-    got, img, aux = _grads(dev, cloud, w, h, det, v_out)
+    got, img, aux = _grads(dev, cloud, w, h, det, v_out, camera=camera)
     tw = _twin(cloud, aux)
     ud = uniforms_to_numpy(aux)
     o_img, o_aux = O.render_forward(ud, tw["means"], tw["log_scales"], tw["quats"], tw["sh"], tw["raw_opac"])
@@ -313,7 +329,7 @@ def test_backward_against_oracle_twin(dev, kind, det):
     ot = A.sigmoid64(tw["raw_opac"][gid])
     dd = ot * (1.0 - ot)
     dldo = np.where(dd > 0, want["v_opac"][gid] / np.where(dd > 0, dd, 1.0), 0.0)
-    u = _u(w, h, cloud)
+    u = _u(w, h, cloud, camera)
     sig = A.sigmoid64(cloud["raw_opac"][gid])
     comp = A.comp64(u, cloud["means"][gid], cloud["log_scales"][gid], cloud["quats"][gid])
     vm, vs, vq = A.comp_vjp64(u, cloud["means"][gid], cloud["log_scales"][gid], cloud["quats"][gid], dldo * sig)
@@ -322,12 +338,15 @@ def test_backward_against_oracle_twin(dev, kind, det):
     want["v_quats"][gid] += vq
     want["v_opac"][gid] = dldo * comp * sig * (1.0 - sig)
     print(f"[{kind} det={det}] V={gid.size} comp min {comp.min() if gid.size else 1:.3g}")
+    ratios = {}
     for k in GRADS:
         scale = float(np.abs(want[k]).max())
         rtol = 1e-1 if k == "v_quats" else 1e-3  # the golden gate's own v_quats tolerance
         ok, err, bad = H.all_close_report(got[k], want[k], rtol, 1e-4 * scale + 1e-12)
         print(f"  {k}: max_abs_err {err:.3e} scale {scale:.3e}")
+        ratios[k] = float((np.abs(got[k] - want[k]) / (1e-4 * scale + 1e-12 + rtol * np.abs(want[k]))).max())
         assert ok, f"{kind} det={det} {k}: max_abs_err={err} bad={bad} scale={scale}"
+    return ratios
 
 
 def test_deterministic_backward_bitwise(dev):

@@ -26,9 +26,18 @@ def _uniforms(w, h, n):
 
 
 # ---------------------------------------------------------------------------- 1. restatement vs central differences
-def _functional_case():
-    cloud = H.synthetic_cloud(4000, 0, seed=11, mean_mult=1.0)
-    u = P.uniforms_ns(_uniforms(160, 120, cloud["means"].shape[0]))
+FUNCTIONAL_SIZE = (160, 120)
+
+
+def functional_cloud():
+    return H.synthetic_cloud(4000, 0, seed=11, mean_mult=1.0)
+
+
+def _functional_case(u=None, cloud=None):
+    """`u`: packed uniforms of a FUNCTIONAL_SIZE frame (default: the reference test camera's); `cloud`: the cloud the
+    splats are taken from (default: functional_cloud())."""
+    cloud = functional_cloud() if cloud is None else cloud
+    u = P.uniforms_ns(_uniforms(*FUNCTIONAL_SIZE, cloud["means"].shape[0]) if u is None else u)
     means = cloud["means"].astype(np.float64)
     ls = cloud["log_scales"].astype(np.float64)
     q = cloud["quats"].astype(np.float64)
@@ -50,7 +59,13 @@ def test_restatement_matches_central_differences(with_comp):
     backward's comp / (comp + 1e-6), so the functional's exact gradient is the backward's formula.  Central differences
     at h = 1e-5 of O(1..10) entries: truncation ~1e-10 f''', rounding ~1e-16 |F| / 1e-5: the bound asked is 1e-7
     relative to the largest entry."""
-    u, m, ls, q = _functional_case()
+    check_restatement(with_comp)
+
+
+def check_restatement(with_comp, u=None, cloud=None, mutate=None):
+    """The body of test_restatement_matches_central_differences at the camera of the packed uniforms `u`, on splats of
+    `cloud`; `mutate` names a deliberate mistake of pose_ref64.pose_grad64 (its MUTATIONS), for the controls."""
+    u, m, ls, q = _functional_case(u, cloud)
     n = m.shape[0]
     rng = np.random.default_rng(5)
     a = rng.normal(size=(n, 2))
@@ -76,7 +91,7 @@ def test_restatement_matches_central_differences(with_comp):
     _, S = A.cov2d64(u, m, ls, q)
     G = -(S @ B @ S)
     v_conic = np.stack([G[:, 0, 0], 2.0 * G[:, 0, 1], G[:, 1, 1]], -1)
-    got, mag = P.pose_grad64(u, m, ls, q, a, v_conic, v_z=c, v_comp=d)
+    got, mag = P.pose_grad64(u, m, ls, q, a, v_conic, v_z=c, v_comp=d, mutate=mutate)
     fd = np.zeros((3, 4))
     h = 1e-5
     for r in range(3):
@@ -94,6 +109,7 @@ def test_restatement_matches_central_differences(with_comp):
           f"{(np.abs(got - fd) / mag).max():.3e}")
     assert (mag >= np.abs(got) * (1 - 1e-12)).all()
     assert rel <= 1e-7, rel
+    return rel
 
 
 # ---------------------------------------------------------------------------- 2. the whole chain on the CPU oracle
@@ -136,7 +152,7 @@ def _oracle_image(u, cloud):
     return O.render_forward(u, cloud["means"], cloud["log_scales"], cloud["quats"], cloud["sh"], cloud["raw_opac"])
 
 
-def oracle_pose_grad(u, cloud, v_out_fn):
+def oracle_pose_grad(u, cloud, v_out_fn, mutate=None):
     """(image, v_viewmat [3,4], mag) of <image, v_out> on the CPU: oracle forward / backward, then pose_grad64 on the
     backward's compact sums.  v_out_fn(image) -> v_out."""
     img, aux = _oracle_image(u, cloud)
@@ -145,7 +161,7 @@ def oracle_pose_grad(u, cloud, v_out_fn):
     V = int(aux["num_visible"][0])
     gids = aux["global_from_compact_gid"][:V]
     got, mag = P.pose_grad64(P.uniforms_ns(u), cloud["means"], cloud["log_scales"], cloud["quats"],
-                             g["v_xy_local"][:V], g["v_conics"][:V], gids=gids)
+                             g["v_xy_local"][:V], g["v_conics"][:V], gids=gids, mutate=mutate)
     return img, got, mag
 
 
@@ -160,7 +176,12 @@ def test_whole_chain_against_oracle_finite_differences():
     difference: 2 * 64 eps32 sum|image . v_out| / (2h).  h = 1.6e-2 was chosen on the CPU (POSE_CHAIN_SCAN=1 prints the
     scan): there |analytic - fd| follows h^2 at a twelfth of the allowance and the floor is 3 % of the smallest of
     the six derivatives; at 1e-3 the floor would be half of it.  The scene (_smooth_scene) crosses no threshold."""
-    cloud, u, w, h = _smooth_scene()
+    check_whole_chain(*_smooth_scene())
+
+
+def check_whole_chain(cloud, u, w, h, mutate=None):
+    """The body of test_whole_chain_against_oracle_finite_differences on a scene and the oracle uniforms of its
+    camera."""
     M0 = np.asarray(u["viewmat"], np.float64).reshape(4, 4).T
     img_chk, aux_chk = _oracle_image(u, cloud)
     assert int(aux_chk["num_visible"][0]) == cloud["means"].shape[0]
@@ -172,7 +193,7 @@ def test_whole_chain_against_oracle_finite_differences():
     yy, xx = np.meshgrid((np.arange(h) - h / 2) / (h / 2), (np.arange(w) - w / 2) / (w / 2), indexing="ij")
     basis = np.stack([np.ones_like(xx), xx, yy, xx * yy, xx * xx, yy * yy], -1)
     v_out = (basis @ rng.uniform(-0.5, 0.5, (6, 4))).astype(np.float32)
-    img0, g34, mag = oracle_pose_grad(u, cloud, lambda im: v_out)
+    img0, g34, mag = oracle_pose_grad(u, cloud, lambda im: v_out, mutate=mutate)
     floor_unit = 64 * EPS32 * float(np.abs(img0.astype(np.float64) * v_out).sum())
 
     def fd(j, step):
@@ -386,9 +407,12 @@ def test_pose_fit_rehearsal_on_the_oracle():
     """The run tests/test_gpu_pose.py repeats on the GPU: splats fixed, the target is the render at the true pose, the
     start is the perturbed pose (pose_ref64.FIT_*), Adam on the twist through the oracle forward / backward and
     pose_grad64.  It must end below one tenth of its initial rotation and translation error."""
+    check_pose_fit_rehearsal(*_oracle_scene())
+
+
+def check_pose_fit_rehearsal(cloud, u, w, h):
     import torch
 
-    cloud, u, w, h = _oracle_scene()
     M_true = np.asarray(u["viewmat"], np.float64).reshape(4, 4).T
     target = _oracle_image(u, cloud)[0].astype(np.float64)
     npix = float(w * h)

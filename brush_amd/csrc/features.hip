@@ -13,69 +13,39 @@
 //                                   repeatable in both aux modes.  The map is an f32 image or a u8 label image whose
 //                                   channel c is `label == c`.
 //
-// gfx950 layout: the forward's, as error_score.hip restates it (DESIGN §9 lists the duplication as an open lever).  One
-// wave64 per 8x8 quadrant, four waves per tile, the XCD-contiguous block remap, records staged per wave in LDS in batches
-// of 64 and read back as wave-uniform broadcasts, quad_may_pass() skipping a (record, quadrant) on the scalar unit, no
-// s_barrier, no LDS atomics.  Channels go in passes of CP = 4, 8 or 16 (one launch per pass, the entry picks the widths):
-// the pass's accumulators (forward) or pixel values (transpose) live in VGPRs.  The forward's staged record grows by the
-// pass's feature slice, gathered by the lane that stages the record; the transpose reduces the pass's CP products over
-// the wave with a transposing tree (permlane32_swap, permlane16_swap, DPP row rotates) that leaves channel c in lane c,
-// and one no-return atomic instruction with the pass's lanes active on consecutive words of the splat's row sends them:
-// the L2 executes a contiguous segment at full rate.
-#include "raster_common.hpp"
+// gfx950 layout: the walk's (replay_walk.hpp).  Channels go in passes of CP = 4, 8 or 16 (one launch per pass, the entry
+// picks the widths): the pass's accumulators (forward) or pixel values (transpose) live in VGPRs.  The forward's staged
+// record grows by the pass's feature slice, gathered by the lane that stages the record; the transpose reduces the
+// pass's CP products over the wave with a transposing tree (permlane32_swap, permlane16_swap, DPP row rotates) that
+// leaves channel c in lane c, and one no-return atomic instruction with the pass's lanes active on consecutive words of
+// the splat's row sends them: the L2 executes a contiguous segment at full rate.
+#include "replay_walk.hpp"
 
 namespace brush {
 namespace {
 
-constexpr float kQ24 = 16777216.0f;  // the fixed point of the summed product: 2^24
-
-// One staged record of the forward replay: 32 bytes of geometry and the pass's CP features.
+// One staged record of the forward replay: the walk's 32 bytes of geometry (its own two words unused) and the pass's CP
+// features.  The transpose stages the plain ReplayRec with the global id in b.z, through the shared walk.
 template <int CP>
-struct FeatRec {
-    float4 a;  // mean.x, mean.y, conic.x, conic.y
-    float4 b;  // conic.z, opacity, -, -
+struct FeatRec : ReplayRec {
     float4 f[CP / 4];
 };
 static_assert(sizeof(FeatRec<16>) * kTilesPerBlock * kBatch == 24576, "the widest pass: 24 KB of LDS per workgroup");
 
-// One staged record of the transpose: ErrorRec's 32 bytes.
-struct GradRec {
-    float4 a;  // mean.x, mean.y, conic.x, conic.y
-    float4 b;  // conic.z, opacity, global id (bits), -
-};
-static_assert(sizeof(GradRec) * kTilesPerBlock * kBatch == 8192, "one GradRec per wave and batch slot");
-
 // ---- k_feature_quad ---------------------------------------------------------------------------------------------------
-// The forward's walk (k_rasterize_quad, float image) with the same expressions per pixel: sigma, power, alpha_u, the
-// 0.999 clamp, the test `power <= 0 && alpha_u >= 1/255`, next_T, the `next_T <= 1e-4` stop WITHOUT adding the entry and
-// the NaN pixel centre after a stop, so that T evolves as it did in the forward.  Per added entry and channel k of the
-// pass, acc[k] = fmaf(features[g, c0 + k], fac, acc[k]) under the pixel's own predicate, as the forward accumulates its
-// colour.  Every inside pixel stores out[p, c0 .. c0 + cn) once (zeros where nothing was added); nothing outside a ragged
-// frame is read or written.  VEC: C is a multiple of 4 and both bases are 16-byte aligned, so slices move as float4.
+// The walk of replay_walk.hpp, written out: the staged record grows by the feature slice and a splat can be vetoed.
+// Per added entry and channel k of the pass, acc[k] = fmaf(features[g, c0 + k], fac, acc[k]) under the pixel's own predicate, as
+// the forward accumulates its colour.  Every inside pixel stores out[p, c0 .. c0 + cn) once (zeros where nothing was
+// added); nothing outside a ragged frame is read or written.  VEC: C is a multiple of 4 and both bases are 16-byte
+// aligned, so slices move as float4.
 template <int CP, bool VEC>
 __global__ __launch_bounds__(kRasterThreads) void k_feature_quad(
     uint32_t w, uint32_t h, uint32_t tbx, uint32_t num_tiles, const uint32_t *__restrict__ gid_from_isect,
     const uint32_t *__restrict__ tile_bins, uint32_t cap, const float *__restrict__ projected,
     const uint32_t *__restrict__ global_from_compact, const uint32_t *__restrict__ num_visible, uint32_t n_splats,
     const float *__restrict__ features, uint32_t C, uint32_t c0, uint32_t cn, float *__restrict__ out) {
-    __shared__ FeatRec<CP> lds_all[kTilesPerBlock][kBatch];
-    const uint32_t q = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    FeatRec<CP> *lds = lds_all[q];
-    const uint32_t tile_id = xcd_contiguous_block();
-    if (tile_id >= num_tiles) return;
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint32_t qx0 = (tile_id % tbx) * kTileWidth + (q & 1u) * 8u, qy0 = (tile_id / tbx) * kTileWidth + (q >> 1) * 8u;
-    if (qx0 >= w || qy0 >= h) return;  // quadrant entirely outside a ragged frame
-    const uint32_t px = qx0 + (lane & 7u), py = qy0 + (lane >> 3);
-    const float bx = (float)qx0 + 0.5f, by = (float)qy0 + 0.5f;
-    const bool inside = px < w && py < h;
-    const float pcy = (float)py + 0.5f;  // rasterize.wgsl:32
-    float pcx = inside ? (float)px + 0.5f : __builtin_nanf("");
-
-    const uint64_t inside_mask = ballot64(inside);
-    uint64_t live = inside_mask;
-    uint32_t walked = 0;
-    float T = 1.0f;
+    BRUSH_REPLAY_PROLOGUE(FeatRec<CP>);
+    BRUSH_REPLAY_WALK_STATE;
     float acc[CP];
 #pragma unroll
     for (int k = 0; k < CP; k++) acc[k] = 0.0f;
@@ -235,8 +205,8 @@ __device__ __forceinline__ T transpose_sum(const T (&p)[CP], uint32_t lane) {
 // ---- k_feature_grad_quad ------------------------------------------------------------------------------------------------
 enum : int { kGradF32 = 0, kSumsF32 = 1, kSumsLabelU8 = 2 };
 
-// The same walk.  Per lane, once, in front of it: the pixel's CP values of the pass (0 outside a ragged frame and past
-// cn):
+// The same walk (replay_walk.hpp).  Per lane, once, in front of the walk: the pixel's CP values of the pass (0 outside
+// a ragged frame and past cn):
 //   kGradF32      v[k] = map[p, c0 + k], arbitrary
 //   kSumsF32      v[k] = min(max(map[p, c0 + k], 0), 1): a NaN and every negative value are 0, everything above 1 is 1
 //   kSumsLabelU8  v[k] = labels[p] == c0 + k ? 1 : 0   (a label >= C belongs to no class)
@@ -252,20 +222,7 @@ __global__ __launch_bounds__(kRasterThreads) void k_feature_grad_quad(
     const uint32_t *__restrict__ global_from_compact, const uint32_t *__restrict__ num_visible, uint32_t n_splats,
     const void *__restrict__ map, uint32_t C, uint32_t c0, uint32_t cn, float *__restrict__ dst_f,
     unsigned long long *__restrict__ dst_q) {
-    __shared__ GradRec lds_all[kTilesPerBlock][kBatch];
-    const uint32_t q = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    GradRec *lds = lds_all[q];
-    const uint32_t tile_id = xcd_contiguous_block();
-    if (tile_id >= num_tiles) return;
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint32_t qx0 = (tile_id % tbx) * kTileWidth + (q & 1u) * 8u, qy0 = (tile_id / tbx) * kTileWidth + (q >> 1) * 8u;
-    if (qx0 >= w || qy0 >= h) return;  // quadrant entirely outside a ragged frame
-    const uint32_t px = qx0 + (lane & 7u), py = qy0 + (lane >> 3);
-    const float bx = (float)qx0 + 0.5f, by = (float)qy0 + 0.5f;
-    const bool inside = px < w && py < h;
-    const float pcy = (float)py + 0.5f;  // rasterize.wgsl:32
-    float pcx = inside ? (float)px + 0.5f : __builtin_nanf("");
-
+    BRUSH_REPLAY_PROLOGUE(ReplayRec);
     float v[CP];
 #pragma unroll
     for (int k = 0; k < CP; k++) v[k] = 0.0f;
@@ -296,103 +253,36 @@ __global__ __launch_bounds__(kRasterThreads) void k_feature_grad_quad(
         }
     }
 
-    const uint64_t inside_mask = ballot64(inside);
-    uint64_t live = inside_mask;
-    uint32_t walked = 0;
-    float T = 1.0f;
-    const uint32_t nvis = min(*num_visible, n_splats);
-    // a finished forward leaves r0 <= r1 <= min(num_intersections, cap); nothing beyond the list's capacity is read
-    const uint32_t r0 = tile_bins[tile_id * 2], r1 = min(tile_bins[tile_id * 2 + 1], cap);
-    for (uint32_t batch_start = r0; batch_start < r1 && live != 0ull; batch_start += kBatch) {
-        const uint32_t remaining = min(kBatch, r1 - batch_start);
-        bool may = false;
-        float rec[6];
-        uint32_t gid = kInvalid;
-        if (lane < remaining) {
-            const uint32_t cgid = gid_from_isect[batch_start + lane];
-            if (cgid < nvis) {  // every entry of a finished forward's list is
-                const float *p = projected + (size_t)cgid * BRUSH_PROJECTED_FLOATS;
+    BRUSH_REPLAY_WALK_STATE;
+    BRUSH_REPLAY_WALK_BEGIN(true, 6, (void)0, __uint_as_float(gid), 0.f)
+    const float fac = hit ? alpha * T : 0.0f;
+    BRUSH_REPLAY_WALK_DIE(false)
+    BRUSH_REPLAY_WALK_ADD()
+    if (ballot64(hit) != 0ull) {
+        const uint32_t g = __builtin_amdgcn_readfirstlane(__float_as_uint(b.z));
+        if constexpr (MODE == kGradF32) {
+            float p[CP];
 #pragma unroll
-                for (int k = 0; k < 5; k++) rec[k] = p[k];
-                rec[5] = p[8];  // the opacity the splat is drawn with (antialiased mode: already compensated)
-                gid = global_from_compact[cgid];
-                may = quad_may_pass(rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], bx, by);
-            }
-        }
-        uint64_t mask = ballot64(may);
-        if (mask == 0ull) continue;
-        wave_sync();  // the previous batch's broadcasts are done (LDS is in order per wave)
-        if (may) {
-            lds[lane].a = make_float4(rec[0], rec[1], rec[2], rec[3]);
-            lds[lane].b = make_float4(rec[4], rec[5], __uint_as_float(gid), 0.f);
-        }
-        wave_sync();
-        while (mask != 0ull) {
-            const uint32_t t = (uint32_t)__builtin_ctzll(mask);
-            mask &= mask - 1ull;
-            const float4 a = lds[t].a;
-            const float4 b = lds[t].b;
-            const float opac = b.y;
-            // rasterize.wgsl:80-99, the forward's association (rasterize.hip)
-            const float dx = a.x - pcx, dy = a.y - pcy;
-            const float sigma = fmaf(0.5f, fmaf(a.z * dx, dx, (b.x * dy) * dy), (a.w * dy) * dx);
-            const float power = sigma * kNegLog2e;
-            const float alpha_u = opac * __builtin_amdgcn_exp2f(power);
-            const bool pass = power <= 0.0f && alpha_u >= 1.0f / 255.0f;  // never true for a stopped pixel (NaN)
-            const float alpha = vmin(0.999f, alpha_u);
-            const float next_T = T * (1.0f - alpha);
-            const bool stop = pass && next_T <= 1e-4f;  // :88-91: stop WITHOUT adding this entry
-            const bool hit = pass && !stop;
-            const float fac = hit ? alpha * T : 0.0f;
-            if (stop) pcx = __builtin_nanf("");
-            if (hit) T = next_T;
-            if (ballot64(hit) != 0ull) {
-                const uint32_t g = __builtin_amdgcn_readfirstlane(__float_as_uint(b.z));
-                if constexpr (MODE == kGradF32) {
-                    float p[CP];
+            for (int k = 0; k < CP; k++) p[k] = hit ? fac * v[k] : 0.0f;  // (0 inf = NaN stays out of other rows)
+            const float s = transpose_sum<CP>(p, lane);
+            if (lane < cn && g < n_splats && s != 0.0f) unsafeAtomicAdd(dst_f + (size_t)g * C + c0 + lane, s);
+        } else {
+            uint32_t p[CP];
+            // fac v: one f32 rounding; the scale by 2^24 is exact (fac v <= 1)
 #pragma unroll
-                    for (int k = 0; k < CP; k++) p[k] = hit ? fac * v[k] : 0.0f;  // (0 inf = NaN stays out of other rows)
-                    const float s = transpose_sum<CP>(p, lane);
-                    if (lane < cn && g < n_splats && s != 0.0f) unsafeAtomicAdd(dst_f + (size_t)g * C + c0 + lane, s);
-                } else {
-                    uint32_t p[CP];
-                    // fac v: one f32 rounding; the scale by 2^24 is exact (fac v <= 1)
-#pragma unroll
-                    for (int k = 0; k < CP; k++) p[k] = (uint32_t)__builtin_rintf((fac * v[k]) * kQ24);
-                    const uint32_t s = transpose_sum<CP>(p, lane);
-                    if (lane < cn && g < n_splats && s != 0u)
-                        atomicAdd(dst_q + (size_t)g * C + c0 + lane, (unsigned long long)s);
-                }
-            }
-            // all pixels stopped?  one compare every 4th record, as the forward
-            if ((++walked & 3u) == 0u) {
-                live = ~__builtin_amdgcn_fcmp(pcx, pcx, 8 /* FCMP_UNO */) & inside_mask;
-                if (live == 0ull) break;
-            }
+            for (int k = 0; k < CP; k++) p[k] = (uint32_t)__builtin_rintf((fac * v[k]) * kQ24);
+            const uint32_t s = transpose_sum<CP>(p, lane);
+            if (lane < cn && g < n_splats && s != 0u) atomicAdd(dst_q + (size_t)g * C + c0 + lane, (unsigned long long)s);
         }
     }
+    BRUSH_REPLAY_WALK_END
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------
-struct WalkArgs {
-    uint32_t w, h, tbx, tiles, n;
-    const BrushAux *aux;
-    hipStream_t s;
-};
-
-// The argument, alignment and tile-bound checks the replay entries share (brush_render_error_scores').
-bool walk_args(const BrushUniforms *h_uniforms, const BrushAux *h_aux, uint32_t C, uint32_t n, brush_stream_t stream,
-               WalkArgs &o) {
-    if (!h_uniforms || !h_aux || C < 1u || C > BRUSH_FEATURE_MAX_CHANNELS) return false;
-    const BrushUniforms &u = *h_uniforms;
-    const BrushAux &aux = *h_aux;
-    const uint32_t w = u.img_size[0], h = u.img_size[1], tbx = u.tile_bounds[0], tby = u.tile_bounds[1];
-    if (!checked_pixels(w, h) || tbx != ceil_div(w, kTileWidth) || tby != ceil_div(h, kTileWidth)) return false;
-    if (!aux.projected_splats || !aux.tile_bins || !aux.compact_gid_from_isect || !aux.global_from_compact_gid ||
-        !aux.num_visible || aux.max_intersects == 0)
-        return false;
-    o = WalkArgs{w, h, tbx, tbx * tby, n, h_aux, static_cast<hipStream_t>(stream)};
-    return true;
+// The channel-count bound of the three entries, then the checks every replay entry makes.
+bool feature_args(const BrushUniforms *h_uniforms, const BrushAux *h_aux, uint32_t C, uint32_t n, brush_stream_t stream,
+                  WalkArgs &o) {
+    return C >= 1u && C <= BRUSH_FEATURE_MAX_CHANNELS && walk_args(h_uniforms, h_aux, n, stream, o);
 }
 
 // Width of the pass that starts with `rem` channels left: 16 while more than 8 remain, then 8, then 4.
@@ -400,27 +290,14 @@ uint32_t pass_width(uint32_t rem) { return rem > 8u ? 16u : rem > 4u ? 8u : 4u; 
 
 template <int CP>
 void launch_forward(const WalkArgs &a, const float *features, uint32_t C, uint32_t c0, uint32_t cn, float *out) {
-    // one workgroup (4 quadrant waves) per tile; a multiple of 8 for the XCD remap
-    const dim3 grid(ceil_div(a.tiles, 8u) * 8u), block(kRasterThreads);
-    const BrushAux &x = *a.aux;
     const bool vec = (C & 3u) == 0u && !misaligned(features, 16) && !misaligned(out, 16);
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, a.s, a.w, a.h, a.tbx, a.tiles, x.compact_gid_from_isect, x.tile_bins,
-                           x.max_intersects, x.projected_splats, x.global_from_compact_gid, x.num_visible, a.n, features,
-                           C, c0, cn, out);
-    };
-    vec ? go(k_feature_quad<CP, true>) : go(k_feature_quad<CP, false>);
+    walk_launch(vec ? k_feature_quad<CP, true> : k_feature_quad<CP, false>, a, features, C, c0, cn, out);
 }
 
 template <int CP, int MODE>
 void launch_grad(const WalkArgs &a, const void *map, uint32_t C, uint32_t c0, uint32_t cn, float *dst_f,
                  uint64_t *dst_q) {
-    const dim3 grid(ceil_div(a.tiles, 8u) * 8u), block(kRasterThreads);
-    const BrushAux &x = *a.aux;
-    hipLaunchKernelGGL((k_feature_grad_quad<CP, MODE>), grid, block, 0, a.s, a.w, a.h, a.tbx, a.tiles,
-                       x.compact_gid_from_isect, x.tile_bins, x.max_intersects, x.projected_splats,
-                       x.global_from_compact_gid, x.num_visible, a.n, map, C, c0, cn, dst_f,
-                       reinterpret_cast<unsigned long long *>(dst_q));
+    walk_launch(k_feature_grad_quad<CP, MODE>, a, map, C, c0, cn, dst_f, reinterpret_cast<unsigned long long *>(dst_q));
 }
 
 template <int MODE>
@@ -442,7 +319,7 @@ using namespace brush;
 extern "C" int brush_render_features(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *features,
                                      uint32_t C, float *out, uint32_t n, brush_stream_t stream) {
     WalkArgs a;
-    if (!out || (!features && n != 0) || !walk_args(h_uniforms, h_aux, C, n, stream, a)) return BRUSH_ERR_INVALID_ARG;
+    if (!out || (!features && n != 0) || !feature_args(h_uniforms, h_aux, C, n, stream, a)) return BRUSH_ERR_INVALID_ARG;
     if (misaligned(features, 4) || misaligned(out, 4)) return BRUSH_ERR_INVALID_ARG;
     // n == 0 launches too: every pixel is written on every call (no list is read then)
     for (uint32_t c0 = 0; c0 < C;) {
@@ -459,7 +336,7 @@ extern "C" int brush_render_features(const BrushUniforms *h_uniforms, const Brus
 extern "C" int brush_render_features_backward(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *v_out,
                                               uint32_t C, float *v_features, uint32_t n, brush_stream_t stream) {
     WalkArgs a;
-    if (!v_out || !v_features || !walk_args(h_uniforms, h_aux, C, n, stream, a)) return BRUSH_ERR_INVALID_ARG;
+    if (!v_out || !v_features || !feature_args(h_uniforms, h_aux, C, n, stream, a)) return BRUSH_ERR_INVALID_ARG;
     if (misaligned(v_out, 4) || misaligned(v_features, 4)) return BRUSH_ERR_INVALID_ARG;
     if (n == 0) return BRUSH_OK;  // no splat, no row
     grad_passes<kGradF32>(a, v_out, C, v_features, nullptr);
@@ -471,7 +348,7 @@ extern "C" int brush_render_feature_sums(const BrushUniforms *h_uniforms, const 
                                          uint32_t map_kind, uint32_t C, uint64_t *sums, uint32_t n,
                                          brush_stream_t stream) {
     WalkArgs a;
-    if (!maps || !sums || map_kind > BRUSH_FEATURE_MAP_LABEL_U8 || !walk_args(h_uniforms, h_aux, C, n, stream, a))
+    if (!maps || !sums || map_kind > BRUSH_FEATURE_MAP_LABEL_U8 || !feature_args(h_uniforms, h_aux, C, n, stream, a))
         return BRUSH_ERR_INVALID_ARG;
     if ((map_kind == BRUSH_FEATURE_MAP_F32 && misaligned(maps, 4)) || misaligned(sums, 8)) return BRUSH_ERR_INVALID_ARG;
     if (n == 0) return BRUSH_OK;  // no splat, no row

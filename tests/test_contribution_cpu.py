@@ -333,7 +333,7 @@ def test_contribution_kernel_static_lds_and_no_spills(lib):
     (name, r), = res.items()
     assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, name
     assert r["group_segment_fixed_size"] == 8192, name
-    src = open(os.path.join(ROOT, "brush_amd", "csrc", "contribution.hip")).read()
-    assert "static_assert(sizeof(ContribRec) * kTilesPerBlock * kBatch == 8192" in src
+    walk = open(os.path.join(ROOT, "brush_amd", "csrc", "replay_walk.hpp")).read()  # the staged record is the shared walk's
+    assert "static_assert(sizeof(ReplayRec) * kTilesPerBlock * kBatch == 8192" in walk
     # a kernel of its own: the forward's instantiations stay three (tests/test_host_cpu.py counts them)
     assert "k_rasterize" not in name

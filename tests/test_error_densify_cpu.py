@@ -323,7 +323,7 @@ def test_error_kernels_static_lds_and_no_spills(lib):
     for name, r in res.items():
         assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, name
         assert r["group_segment_fixed_size"] == (8192 if name in quad else 0), name
-    src = open(os.path.join(ROOT, "brush_amd", "csrc", "error_score.hip")).read()
-    assert "static_assert(sizeof(ErrorRec) * kTilesPerBlock * kBatch == 8192" in src
+    walk = open(os.path.join(ROOT, "brush_amd", "csrc", "replay_walk.hpp")).read()  # the staged record is the shared walk's
+    assert "static_assert(sizeof(ReplayRec) * kTilesPerBlock * kBatch == 8192" in walk
     assert "k_rasterize" not in quad[0] and "k_contribution" not in quad[0]
     assert len(kd.resources(_lib.LIB_PATH, r"k_contribution_quad")) == 1

@@ -309,7 +309,7 @@ def test_entries_validate_before_any_device_work(lib):
 
 def test_feature_kernels_static_lds_and_no_spills(lib):
     """k_feature_quad: passes of 4, 8 and 16 channels, each with and without 16-byte slices, the static LDS of
-    4 waves x 64 records x (32 + 4 CP) bytes; k_feature_grad_quad: three widths x three modes, ErrorRec's 8192 bytes;
+    4 waves x 64 records x (32 + 4 CP) bytes; k_feature_grad_quad: three widths x three modes, ReplayRec's 8192 bytes;
     no spills and no scratch anywhere; registers far from the 128 of the 256-thread bound."""
     spec = importlib.util.spec_from_file_location("kernel_diff", os.path.join(ROOT, "tools", "kernel_diff.py"))
     kd = importlib.util.module_from_spec(spec)
@@ -327,5 +327,25 @@ def test_feature_kernels_static_lds_and_no_spills(lib):
     assert all(res[n]["group_segment_fixed_size"] == 8192 for n in grad)
     src = open(os.path.join(ROOT, "brush_amd", "csrc", "features.hip")).read()
     assert "static_assert(sizeof(FeatRec<16>) * kTilesPerBlock * kBatch == 24576" in src
-    assert "static_assert(sizeof(GradRec) * kTilesPerBlock * kBatch == 8192" in src
+    walk = open(os.path.join(ROOT, "brush_amd", "csrc", "replay_walk.hpp")).read()  # the staged record is the shared walk's
+    assert "static_assert(sizeof(ReplayRec) * kTilesPerBlock * kBatch == 8192" in walk
     assert len(kd.resources(_lib.LIB_PATH, r"k_error_quad")) == 1  # the replays it generalises are their own kernels
+
+
+def test_the_compositing_walk_is_written_in_one_place():
+    """The forward's walk (the `quad_may_pass(` ballot, the FCMP_UNO liveness check) stands in the compositing kernels'
+    own files and in the replay walk's header, nowhere else.  Exempt, by name: the kernel whose walk stays written out
+    (its staged record and its veto are its own)."""
+    csrc = os.path.join(ROOT, "brush_amd", "csrc")
+    allowed = {"rasterize.hip", "rasterize_bwd.hip", "raster_common.hpp", "replay_walk.hpp"}
+    written_out = {"features.hip": ("k_feature_quad",)}
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if name in allowed or not os.path.isfile(path):
+            continue
+        src = open(path, errors="replace").read()
+        for kernel in written_out.get(name, ()):  # cut it out: from its name to the brace that closes it in column 0
+            start = src.index("void %s(" % kernel)
+            src = src[:start] + src[src.index("\n}\n", start):]
+        for needle in ("quad_may_pass(", "FCMP_UNO"):
+            assert needle not in src, (name, needle)

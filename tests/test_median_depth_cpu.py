@@ -5,6 +5,7 @@ brush_render_median_depth and brush_tsdf_integrate_ex without a device, and the 
 import ctypes as C
 import importlib.util
 import os
+import re
 
 import numpy as np
 import pytest
@@ -320,6 +321,10 @@ def test_median_kernel_static_lds_and_no_spills(lib):
     assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, name
     assert r["group_segment_fixed_size"] == 8192, name
     src = open(os.path.join(ROOT, "brush_amd", "csrc", "median_depth.hip")).read()
-    assert "static_assert(sizeof(MedianRec) * kTilesPerBlock * kBatch == 8192" in src
+    walk = open(os.path.join(ROOT, "brush_amd", "csrc", "replay_walk.hpp")).read()  # the staged record is the shared walk's
+    assert "static_assert(sizeof(ReplayRec) * kTilesPerBlock * kBatch == 8192" in walk
     assert "s_barrier" not in src.split("#include")[1] and "atomic" not in src.split("#include")[1]
+    # the loop the kernel runs is the shared walk's: its code (comments cut) has neither as well
+    code = re.sub(r"/\*.*?\*/", "", "\n".join(l.split("//")[0] for l in walk.split("#pragma once")[1].splitlines()))
+    assert "s_barrier" not in code and "atomic" not in code
     assert len(kd.resources(_lib.LIB_PATH, r"k_tsdf_integrate")) == 2

@@ -65,6 +65,13 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 (brush_amd/normal_loss.py; build extension, 2DGS, GOF, RaDe-GS and PGSR are the models;
                                 Splats.render_normals, TrainConfig.normal_weight,
                                 `python -m brush_amd.train_loop --normal-weight`)
+  render_distortion / distortion_from_aux / distortion_compact_grads_from_aux / distortion_loss_into /
+  distortion_config          <- the depth-distortion term sum w_i w_j (m_i - m_j)^2 per pixel (depth or 2DGS's NDC mapping)
+                                from a replay of the compositing walk, and its gradient into the geometry, blending
+                                weights included, added into the render backward's compact rows by a second replay
+                                (brush_amd/distortion.py; build extension, 2DGS, GOF, RaDe-GS and gsplat's 2DGS path are
+                                the models; Splats.render_distortion, TrainConfig.distortion_weight,
+                                `python -m brush_amd.train_loop --distortion-weight`)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -86,6 +93,8 @@ from .depth_loss import depth_loss, depth_loss_into  # noqa: F401
 from .compose import as_background, compose, compose_backward, compose_forward  # noqa: F401  (as depth_loss above)
 from .normal_loss import (depth_normals, normal_consistency_loss, normal_loss_into, render_normals,  # noqa: F401
                           splat_normals)
+from .distortion import (distortion_compact_grads_from_aux, distortion_config, distortion_from_aux,  # noqa: F401
+                         distortion_loss_into, render_distortion)
 from .pyramid import area_resize, downscaled_size, nearest_resize  # noqa: F401
 from .filter3d import apply_filter3d, filter3d_rates  # noqa: F401
 from .undistort import (Distortion, fit_scale, undistort_dataset, undistort_depth, undistort_image,  # noqa: F401

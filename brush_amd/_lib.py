@@ -19,6 +19,8 @@ DEPTH_LOSS_DEPTH = 0   # BrushDepthLoss.mode: BRUSH_DEPTH_LOSS_DEPTH
 DEPTH_LOSS_DISPARITY = 1  # BRUSH_DEPTH_LOSS_DISPARITY
 DEPTH_GT_U16 = 0       # BrushDepthLoss.gt_dtype: BRUSH_DEPTH_GT_U16
 DEPTH_GT_F32 = 1       # BRUSH_DEPTH_GT_F32
+DISTORTION_DEPTH = 0   # BrushDistortion.mode: BRUSH_DISTORTION_DEPTH
+DISTORTION_NDC = 1     # BRUSH_DISTORTION_NDC
 TSDF_DEPTH_METRIC = 1  # brush_tsdf_integrate_ex flags: BRUSH_TSDF_DEPTH_METRIC
 UNIFORM_WORDS = 28
 NUM_VISIBLE_WORD = 25
@@ -109,6 +111,11 @@ class BrushDepthLoss(C.Structure):
 class BrushNormalLoss(C.Structure):
     """Per-call configuration of brush_normal_loss (include/brush_hip.h: BrushNormalLoss)."""
     _fields_ = [("weight", C.c_float), ("alpha_min", C.c_float)]
+
+
+class BrushDistortion(C.Structure):
+    """Per-call configuration of the depth-distortion entries (include/brush_hip.h: BrushDistortion), 12 bytes."""
+    _fields_ = [("mode", C.c_uint32), ("near_z", C.c_float), ("far_z", C.c_float)]
 
 
 class BrushUndistort(C.Structure):
@@ -255,6 +262,13 @@ _SYMBOLS = [
     ("brush_normal_loss_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     ("brush_normal_loss", C.c_int,
      [C.POINTER(BrushUniforms), _P, _P, _P, C.POINTER(BrushNormalLoss), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_render_distortion", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.POINTER(BrushDistortion), C.c_uint32, _P, _P]),
+    ("brush_distortion_compact_grads", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, C.POINTER(BrushDistortion), _P, _P, C.c_uint32, _P, _P]),
+    ("brush_render_backward_distortion", C.c_int,
+     [C.POINTER(BrushUniforms), C.POINTER(BrushAux), _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P,
+      C.POINTER(BrushDistortion), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     ("brush_filter3d_view_chunk", C.c_uint32, []),
     ("brush_filter3d_rates", C.c_int,
      [_P, C.c_uint32, _P, C.c_uint32, C.c_float, C.c_float, C.c_float, _P, _P]),

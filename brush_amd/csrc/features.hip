@@ -16,10 +16,11 @@
 // gfx950 layout: the walk's (replay_walk.hpp).  Channels go in passes of CP = 4, 8 or 16 (one launch per pass, the entry
 // picks the widths): the pass's accumulators (forward) or pixel values (transpose) live in VGPRs.  The forward's staged
 // record grows by the pass's feature slice, gathered by the lane that stages the record; the transpose reduces the
-// pass's CP products over the wave with a transposing tree (permlane32_swap, permlane16_swap, DPP row rotates) that
-// leaves channel c in lane c, and one no-return atomic instruction with the pass's lanes active on consecutive words of
-// the splat's row sends them: the L2 executes a contiguous segment at full rate.
+// pass's CP products over the wave with the transposing tree of transpose_sum.hpp (permlane32_swap, permlane16_swap, DPP
+// row rotates) that leaves channel c in lane c, and one no-return atomic instruction with the pass's lanes active on
+// consecutive words of the splat's row sends them: the L2 executes a contiguous segment at full rate.
 #include "replay_walk.hpp"
+#include "transpose_sum.hpp"
 
 namespace brush {
 namespace {
@@ -148,58 +149,6 @@ __global__ __launch_bounds__(kRasterThreads) void k_feature_quad(
                 if ((uint32_t)k < cn) dst[k] = acc[k];
         }
     }
-}
-
-// ---- the transposing wave reduction -------------------------------------------------------------------------------------
-// CP registers per lane in, one out: lane c < CP ends with the sum over the wave of p[c].  T is float (F32 mode; the
-// association differs from lane to lane, which the mode's order dependence covers) or uint32_t (exact).
-__device__ __forceinline__ uint32_t bits_of(float v) { return __float_as_uint(v); }
-__device__ __forceinline__ uint32_t bits_of(uint32_t v) { return v; }
-template <typename T>
-__device__ __forceinline__ T from_bits(uint32_t u);
-template <>
-__device__ __forceinline__ float from_bits<float>(uint32_t u) { return __uint_as_float(u); }
-template <>
-__device__ __forceinline__ uint32_t from_bits<uint32_t>(uint32_t u) { return u; }
-// lanes 0-31 <- a[l] + a[l+32], lanes 32-63 <- b[l-32] + b[l]
-template <typename T>
-__device__ __forceinline__ T fold32(T a, T b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(bits_of(a), bits_of(b), false, false);
-    return from_bits<T>(r[0]) + from_bits<T>(r[1]);
-}
-// even rows of 16 <- a[row] + a[row+1], odd rows <- b[row-1] + b[row]
-template <typename T>
-__device__ __forceinline__ T fold16(T a, T b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(bits_of(a), bits_of(b), false, false);
-    return from_bits<T>(r[0]) + from_bits<T>(r[1]);
-}
-template <int CTRL, typename T>
-__device__ __forceinline__ T dpp_rot_add(T v) {
-    return v + from_bits<T>((uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits_of(v), CTRL, 0xf, 0xf, true));
-}
-// Sum of a row of 16 lanes, in every lane of the row.
-template <typename T>
-__device__ __forceinline__ T row_all_sum(T v) {
-    v = dpp_rot_add<0x128>(v);  // row_ror:8
-    v = dpp_rot_add<0x124>(v);  // row_ror:4
-    v = dpp_rot_add<0x122>(v);  // row_ror:2
-    v = dpp_rot_add<0x121>(v);  // row_ror:1
-    return v;
-}
-template <int CP, typename T>
-__device__ __forceinline__ T transpose_sum(const T (&p)[CP], uint32_t lane) {
-    constexpr int R = CP / 4;  // registers left after the two swaps: row r of register k holds channel k + r R
-    T x[CP / 2], y[R];
-#pragma unroll
-    for (int k = 0; k < CP / 2; k++) x[k] = fold32(p[k], p[k + CP / 2]);
-#pragma unroll
-    for (int k = 0; k < R; k++) y[k] = row_all_sum(fold16(x[k], x[k + R]));
-    T val = y[0];
-#pragma unroll
-    for (int k = 1; k < R; k++) val = (lane & (uint32_t)(R - 1)) == (uint32_t)k ? y[k] : val;
-    // lane 16 r + j (j < R) holds channel r R + j; lane c fetches channel c (the crossbar of ds_bpermute, no LDS memory)
-    const uint32_t src = (16u * (lane / (uint32_t)R) + (lane % (uint32_t)R)) & 63u;
-    return from_bits<T>((uint32_t)__builtin_amdgcn_ds_bpermute((int)(src * 4u), (int)bits_of(val)));
 }
 
 // ---- k_feature_grad_quad ------------------------------------------------------------------------------------------------

@@ -184,4 +184,14 @@ hipError_t launch_view_grad(const ViewParams &vp, const float *means, const floa
                             bool has_depth /* v_z of brush_render_backward_depth is present */, bool antialiased,
                             void *pose_ws, float *v_viewmat, hipStream_t s);
 
+// distortion.hip
+// The gradient replay of the depth-distortion term: ADDS its per-record VJP into the compact rows (words 0-4, 8, 9) of a
+// default-mode backward, between the compositing backward and launch_project_backward.  Validates its own arguments and
+// returns a BrushStatus (BRUSH_ERR_INVALID_ARG in deterministic mode).  distortion_args_ok: the same checks without the
+// launch, for an entry that has other launches in front of this one.
+bool distortion_args_ok(const BrushAux *h_aux, const BrushDistortion *cfg, const float *stats, const float *v_distortion);
+int launch_distortion_grad(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *compact_depth,
+                           const BrushDistortion *cfg, const float *stats, const float *v_distortion, uint32_t n,
+                           float *v_compact, brush_stream_t stream);
+
 }  // namespace brush

@@ -371,14 +371,23 @@ static int composite_backward(const BrushUniforms &u, const BrushAux &aux, const
     return BRUSH_OK;
 }
 
+// The depth-distortion term of brush_render_backward_distortion (distortion.hip).
+struct DistortionTerm {
+    const BrushDistortion *cfg;
+    const float *stats, *v;
+};
+
 static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *means,
                                 const float *log_scales, const float *quats, const float *raw_opacity, uint32_t n,
                                 const float *out_img, const float *v_out, float *v_means, float *v_xy,
                                 float *v_scales, float *v_quats, float *v_sh, float *v_opac, const AdamFuse *adam,
                                 void *workspace, size_t workspace_bytes, brush_stream_t stream,
                                 const float *compact_depth = nullptr, const float *v_depth = nullptr,
-                                float *v_viewmat = nullptr, void *pose_ws = nullptr) {
+                                float *v_viewmat = nullptr, void *pose_ws = nullptr,
+                                const DistortionTerm *dist = nullptr) {
     if (!uniforms_ok(h_uniforms) || !aux_ok(h_aux, true) || !out_img || !v_out || !workspace)
+        return BRUSH_ERR_INVALID_ARG;
+    if (dist && (!v_depth || adam || v_viewmat || !distortion_args_ok(h_aux, dist->cfg, dist->stats, dist->v)))
         return BRUSH_ERR_INVALID_ARG;
     if ((compact_depth != nullptr) != (v_depth != nullptr) || (v_depth && adam)) return BRUSH_ERR_INVALID_ARG;
     if ((v_viewmat != nullptr) != (pose_ws != nullptr)) return BRUSH_ERR_INVALID_ARG;
@@ -413,6 +422,11 @@ static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux 
     if (const int rc = composite_backward(u, aux, out_img, v_out, n, ws, &det, fill, &filled, s, compact_depth, v_depth))
         return rc;
     if (stop_behind(BRUSH_STAGE_BWD_ZERO) || stop_behind(BRUSH_STAGE_RASTERIZE_BWD)) return BRUSH_OK;
+    // depth distortion: its per-record VJP joins the compact rows the compositing backward has just summed
+    if (dist)
+        if (const int rc = launch_distortion_grad(h_uniforms, h_aux, compact_depth, dist->cfg, dist->stats, dist->v, n,
+                                                  ws.v_compact, stream))
+            return rc;
     // camera-pose gradient: ahead of the parameter VJP, whose fused Adam forms overwrite `means` in place
     if (v_viewmat)
         BRUSH_HIP_CHECK(launch_view_grad(vp, means, log_scales, quats, raw_opacity, aux.num_visible, n,
@@ -495,6 +509,21 @@ extern "C" int brush_render_backward_depth(const BrushUniforms *h_uniforms, cons
     return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
                                 v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream,
                                 compact_depth, v_depth);
+}
+
+extern "C" int brush_render_backward_distortion(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
+                                                const float *means, const float *log_scales, const float *quats,
+                                                const float *raw_opacity, uint32_t n, const float *out_img,
+                                                const float *v_out, const float *compact_depth, const float *v_depth,
+                                                const BrushDistortion *cfg, const float *stats,
+                                                const float *v_distortion, float *v_means, float *v_xy, float *v_scales,
+                                                float *v_quats, float *v_sh, float *v_opac, void *workspace,
+                                                size_t workspace_bytes, brush_stream_t stream) {
+    if (!compact_depth || !v_depth) return BRUSH_ERR_INVALID_ARG;
+    const DistortionTerm dist{cfg, stats, v_distortion};
+    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
+                                v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream,
+                                compact_depth, v_depth, nullptr, nullptr, &dist);
 }
 
 extern "C" int brush_pose_grad_workspace_size(uint32_t n, size_t *bytes) {

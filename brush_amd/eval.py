@@ -9,7 +9,7 @@ Command line (prints one line per view, then the means):
     python -m brush_amd.eval SPLATS DATASET [--format auto|nerf|colmap] [--eval-split-every K]
                              [--max-resolution R] [--num-frames K] [--seed S] [--window 11] [--json OUT]
                              [--depth-metrics] [--depth-mode depth|disparity] [--downscale 1,2,4,8]
-                             [--depth-dir DIR [--depth-median]] [--normal-dir DIR]
+                             [--depth-dir DIR [--depth-median]] [--normal-dir DIR] [--distortion-dir DIR]
                              [--background white|black|R,G,B] [--no-masks]
 
 --background white scores over a white background (the protocol of the NeRF-synthetic numbers in the literature): the
@@ -20,6 +20,10 @@ render and the image's straight RGBA are composed over the colour first (brush_a
 rendered map of the splats' normals divided by its length where alpha >= 0.5 (0 elsewhere), and <stem>_normal_depth.npy,
 the normals of the surface the rendered depth map implies (0 where a pixel or a neighbour is not covered); both f32
 [h,w,3], facing the camera (z < 0).
+
+--distortion-dir DIR writes the depth-distortion map of every eval view (brush_amd/distortion.py):
+<stem>_distortion.npy, sum over the pairs of a pixel's splats of w_i w_j (z_i - z_j)^2, f32 [h,w]: large where a ray
+crosses a thick or doubled surface.
 
 --downscale 1,2,4,8 is Mip-Splatting's multi-scale protocol: the views are scored once per scale, rendered at 1 / scale
 of their size against the image area-filtered to that size on the device (brush_amd/pyramid.py); one block of lines per
@@ -321,6 +325,24 @@ def write_normal_maps(splats, views, out_dir: str, antialiased: bool = False):
     return paths
 
 
+def write_distortion_maps(splats, views, out_dir: str, antialiased: bool = False):
+    """For each view: <stem>_distortion.npy, the depth-distortion map sum w_i w_j (z_i - z_j)^2 of the view
+    (Splats.render_distortion, mode "depth"), f32 [h,w].  Returns the written paths."""
+    import os
+
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    with torch.no_grad():
+        for v in views:
+            h, w = int(v.image.shape[0]), int(v.image.shape[1])
+            _, _, dist, _ = splats.render_distortion(v.camera, (w, h), antialiased=antialiased)
+            stem = os.path.splitext(os.path.basename(v.name))[0]
+            path = os.path.join(out_dir, stem + "_distortion.npy")
+            np.save(path, dist.cpu().numpy().astype(np.float32))
+            paths.append(path)
+    return paths
+
+
 def zoomed_camera(camera, img_size, zoom: float):
     """`camera` with `zoom` times its focal lengths on an image of the same size and the same principal point: the
     central 1 / zoom of the view, magnified (a zoom-in no training view sampled, which is what the 3D smoothing filter
@@ -405,6 +427,9 @@ def parser():
     p.add_argument("--depth-median", action="store_true",
                    help="--depth-dir: also write every eval view's median depth (<view stem>_depth_median.npy: the z "
                         "of the splat at which the accumulated opacity first reaches one half, 0 where it never does)")
+    p.add_argument("--distortion-dir", default=None,
+                   help="also write every eval view's depth-distortion map (<view stem>_distortion.npy, f32 [h,w]) to "
+                        "this directory")
     p.add_argument("--normal-dir", default=None,
                    help="also write every eval view's rendered normal map (<view stem>_normal.npy, unit where alpha >= "
                         "0.5, else 0) and the normals its depth map implies (<view stem>_normal_depth.npy) to this "
@@ -519,6 +544,9 @@ def main(argv=None) -> int:
         write_depth_maps(splats, [s.view for s in stats.samples], args.depth_dir, median=args.depth_median)
     if args.normal_dir:
         write_normal_maps(splats, [s.view for s in stats.samples], args.normal_dir, antialiased=args.antialiased)
+    if args.distortion_dir:
+        write_distortion_maps(splats, [s.view for s in stats.samples], args.distortion_dir,
+                              antialiased=args.antialiased)
     if args.zoom is not None:
         for path in write_zoomed_renders(splats, [s.view for s in stats.samples], args.zoom, args.image_dir,
                                          antialiased=args.antialiased, background=background):

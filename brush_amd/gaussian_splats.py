@@ -204,6 +204,18 @@ class Splats(torch.nn.Module):
         return render_normals(camera, img_size, self.means, self.log_scales, norm_rot, self.sh_coeffs,
                               self.raw_opacity, antialiased=antialiased, max_intersects=max_intersects)
 
+    def render_distortion(self, camera: Camera, img_size, *, mode: str = "depth", near: float = 0.2, far=None,
+                          antialiased: bool = False, max_intersects=None):
+        """render_depth() plus the depth-distortion map (distortion.render_distortion): (img [h,w,4], depth [h,w],
+        distortion [h,w], aux), all three differentiable with respect to every parameter, through the blending weights
+        too.  ValueError in deterministic mode."""
+        from .distortion import render_distortion
+
+        norm_rot = self._synced_norm_rotation()
+        return render_distortion(camera, img_size, self.means, self.log_scales, norm_rot, self.sh_coeffs,
+                                 self.raw_opacity, mode=mode, near=near, far=far, antialiased=antialiased,
+                                 max_intersects=max_intersects)
+
     def render_pose(self, camera: Camera, img_size, viewmat, max_intersects=None, antialiased: bool = False,
                     depth: bool = False):
         """render() / render_depth() through the explicit world-to-camera matrix `viewmat` (float32 [4,4] CPU tensor),

@@ -180,6 +180,22 @@ class TrainConfig:
     normal_weight: float = 0.0
     normal_from_step: int = 7000
     normal_alpha_min: float = 0.5
+    # Build extension: the depth-distortion term of the same trainers (brush_amd/distortion.py), the second of their two
+    # self-supervised regularisers.  From step distortion_from_step on (3000 is 2DGS's schedule: a hyper-parameter
+    # default, not a measured number) a step adds distortion_weight * mean over all pixels of
+    # L(p) = sum over pairs of w_i w_j (m_i - m_j)^2 to the loss, w the blending weights of the pixel's entries and m
+    # their depths (distortion_mode "depth") or 2DGS's NDC mapping of them ("ndc", with distortion_near and the required
+    # distortion_far).  Needs no extra data; masked by gt_mask.  NOTHING IS FROZEN: the gradient reaches means, scales,
+    # rotations and opacities through the blending weights and the depths (a replay adds the term's per-record VJP into
+    # the render backward's compact rows, brush_render_backward_distortion).  Single-view, separate-call path; refused
+    # with `poses` (the pose would get no gradient through the term) and in deterministic mode (no compact rows there);
+    # float atomics: a trajectory with the term on is not bitwise reproducible.  0 (the default) or a step before
+    # distortion_from_step is the step without the option, same path, bit for bit.  DESIGN §8 row 23.
+    distortion_weight: float = 0.0
+    distortion_from_step: int = 3000
+    distortion_mode: str = "depth"
+    distortion_near: float = 0.2
+    distortion_far: Optional[float] = None
 
     def check(self, multi_rank: bool = False):
         """A ValueError naming the first thing wrong with the configuration, before anything touches a dataset or a
@@ -194,6 +210,7 @@ class TrainConfig:
         if self.depth_weight < 0 or (self.depth_weight_final or 0.0) < 0:
             raise ValueError("TrainConfig.depth_weight / depth_weight_final must be >= 0")
         self.check_normal()
+        self.check_distortion()
         self.check_downscale_schedule()
         prune_at = self.check_contribution_prune()
         if prune_at and self.strategy == "mcmc":
@@ -228,6 +245,23 @@ class TrainConfig:
             raise ValueError(f"TrainConfig.normal_from_step must be an integer >= 0, got {s!r}")
         if isinstance(a, bool) or not isinstance(a, (int, float)) or not (math.isfinite(a) and a > 0.0):
             raise ValueError(f"TrainConfig.normal_alpha_min must be finite and > 0, got {a!r}")
+
+    def check_distortion(self):
+        """A ValueError naming what is wrong with the depth-distortion fields."""
+        from .distortion import distortion_config
+
+        w, s = self.distortion_weight, self.distortion_from_step
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not (math.isfinite(w) and w >= 0.0):
+            raise ValueError(f"TrainConfig.distortion_weight must be finite and >= 0, got {w!r}")
+        if isinstance(s, bool) or not isinstance(s, int) or s < 0:
+            raise ValueError(f"TrainConfig.distortion_from_step must be an integer >= 0, got {s!r}")
+        if w > 0.0 and self.pose_opt:
+            raise ValueError("TrainConfig.distortion_weight cannot be combined with pose_opt: the pose would get no "
+                             "gradient through the term")
+        try:
+            distortion_config(self.distortion_mode, self.distortion_near, self.distortion_far)
+        except ValueError as e:
+            raise ValueError(f"TrainConfig.distortion_mode / distortion_near / distortion_far: {e}") from None
 
     def check_densify(self):
         """A ValueError naming what is wrong with the densification fields."""
@@ -687,6 +721,11 @@ class SplatTrainer:
         """Whether the coming step carries the normal-consistency term (TrainConfig.normal_weight / normal_from_step)."""
         return self.config.normal_weight > 0.0 and self.iter >= self.config.normal_from_step
 
+    def _distortion_active(self) -> bool:
+        """Whether the coming step carries the depth-distortion term (TrainConfig.distortion_weight /
+        distortion_from_step)."""
+        return self.config.distortion_weight > 0.0 and self.iter >= self.config.distortion_from_step
+
     def _check_step(self, grad_sync, exchange, view_index, poses, exposures, gt_depth):
         """Refuses the combinations of step's arguments and the configuration that no path serves, before anything is
         touched (neither the trainer's state nor the splats are looked at)."""
@@ -699,11 +738,20 @@ class SplatTrainer:
             for on, what in ((self.filter3d is not None, "the 3D filter"),
                              (gt_depth is not None, "depth supervision"),
                              (self._normal_active(), "the normal-consistency term"),
+                             (self._distortion_active(), "the distortion term (TrainConfig.distortion_weight)"),
                              (c.strategy == "mcmc", "the mcmc strategy"),
                              (poses is not None, "pose refinement"),
                              (exposures is not None, "exposure compensation")):
                 if on:
                     raise ValueError(f"{what} is single-view: it cannot be combined with exchange / grad_sync")
+        if self._distortion_active():
+            # what the term's gradient replay cannot serve
+            for on, what in ((poses is not None, "pose refinement (`poses`): the pose would get no gradient through "
+                                                 "the term"),
+                             (R.deterministic_default(), "deterministic mode: it keeps one gradient row per "
+                                                         "intersection, the term adds into per-splat rows")):
+                if on:
+                    raise ValueError(f"TrainConfig.distortion_weight cannot be combined with {what}")
         if c.densify_by == "error":
             # what the score pass cannot serve (TrainConfig.check refuses the configured forms of the same rows)
             for on, what in ((c.strategy == "mcmc", "the mcmc strategy"),
@@ -774,8 +822,9 @@ class SplatTrainer:
         self._store_rotation(splats, next_rot)
 
     def _update_separate(self, cfg, size, params, norm_rot, fwd, want_stats, pose, stream, effective, depth_grad,
-                         grad_sync, batch_views, scene_extent, normal_grad=None):
-        """Separate calls: the dense backward, then whatever works on dense gradients (the splat-normal VJP of an active
+                         grad_sync, batch_views, scene_extent, normal_grad=None, distortion_grad=None):
+        """Separate calls: the dense backward (distortion_grad: None, or (cfg, stats, v_distortion) of an active
+        distortion term: brush_render_backward_distortion with depth_grad's depth gradient), then whatever works on dense gradients (the splat-normal VJP of an active
         normal-consistency term, the 3D filter's VJP, grad_sync, the refinement statistics, the mcmc regularisers), then
         brush_adam_step on every splat.  normal_grad: None or the [N,3] gradient at the per-splat normals."""
         c = self.config
@@ -784,8 +833,13 @@ class SplatTrainer:
         u, aux, pred, v_pred = fwd
         n, ncoef, l = means.shape[0], int(sh.shape[1]), _lib.lib()
         eff_scales, eff_opac = effective
-        grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
-                                        depth=depth_grad, pose=pose)
+        if distortion_grad is not None:
+            from .distortion import backward_distortion
+            grads, block = backward_distortion(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
+                                               depth_grad[0], depth_grad[1], *distortion_grad)
+        else:
+            grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
+                                            depth=depth_grad, pose=pose)
         if normal_grad is not None:  # the rendered normal map's gradient -> the quaternions the forward was fed
             from .normal_loss import splat_normals_backward_into
             splat_normals_backward_into(u, means, log_scales, norm_rot, normal_grad, grads["v_quats"])
@@ -874,7 +928,14 @@ class SplatTrainer:
         transpose gives the gradient at the per-splat normals and brush_splat_normals_backward adds it into v_quats
         behind the render backward.  The replay's blending weights are frozen; with `poses` the pose gets no gradient
         through the normals; the transpose's float atomics make the trajectory order dependent in its last bits, in
-        deterministic mode too.  Before normal_from_step, or with weight 0, the step is the one without the option."""
+        deterministic mode too.  Before normal_from_step, or with weight 0, the step is the one without the option.
+        TrainConfig.distortion_weight > 0 from step distortion_from_step on (the depth-distortion term, single-view,
+        separate-call path, refused with `poses` and in deterministic mode): the view is rendered with its depth
+        output; after the colour, depth and normal terms brush_render_distortion replays that forward,
+        distortion_loss_into adds the term (weight / batch_views, masked by `gt_mask`) into the step's loss, and the
+        backward is brush_render_backward_distortion with the one summed depth gradient of the other terms (a zero map
+        without them): the term's gradient goes through the blending weights and the depths into every geometric
+        parameter.  Before distortion_from_step, or with weight 0, the step is the one without the option."""
         c = self.config
         self._check_step(grad_sync, exchange, view_index, poses, exposures, gt_depth)
         use_mcmc = c.strategy == "mcmc"
@@ -882,8 +943,9 @@ class SplatTrainer:
         depth_w = self._depth_weight() if gt_depth is not None else 0.0
         use_depth = depth_w > 0.0
         use_normal = self._normal_active()
+        use_dist = self._distortion_active()
         path = optimizer_path(exchange is not None, grad_sync is not None, self.fused_backward, use_mcmc,
-                              use_depth or use_normal, filt is not None)
+                              use_depth or use_normal or use_dist, filt is not None)
         h, w = int(gt_image.shape[0]), int(gt_image.shape[1])
         n, ncoef = splats.num_splats(), int(splats.sh_coeffs.shape[1])
         if self.moment1.numel() != n * (11 + 3 * ncoef):
@@ -914,7 +976,7 @@ class SplatTrainer:
             viewmat = poses.viewmat(view_index, camera).numpy()
             pose = R.pose_buffers(n, means.device)
         # (depth map, compact depth)
-        depth_bufs = R._depth_buffers(n, (w, h), means.device) if use_depth or use_normal else None
+        depth_bufs = R._depth_buffers(n, (w, h), means.device) if use_depth or use_normal or use_dist else None
         # the renderer sees the effective log-scales and opacities; everything else keeps reading the raw ones
         effective = (log_scales, raw_opac)
         if filt is not None:
@@ -944,6 +1006,16 @@ class SplatTrainer:
             depth_grad = (depth_bufs[1], v_depth)
             normal_grad = torch.zeros((n, 3), dtype=torch.float32, device=means.device)
             feature_grads_from_aux(u, aux, v_normals_img, normal_grad)
+        distortion_grad = None
+        if use_dist:  # a replay of the same forward; the backward adds its VJP into the compact rows
+            from .distortion import distortion_config, distortion_from_aux, distortion_loss_into
+            dcfg = distortion_config(c.distortion_mode, c.distortion_near, c.distortion_far)
+            dstats = distortion_from_aux(u, aux, depth_bufs[1], dcfg)
+            v_dist, _ = distortion_loss_into(dstats, torch.empty((h, w), dtype=torch.float32, device=means.device),
+                                             weight=c.distortion_weight / batch_views, mask=gt_mask, loss_accum=loss)
+            distortion_grad = (dcfg, dstats, v_dist)
+            if depth_grad is None:  # no other term made a depth gradient
+                depth_grad = (depth_bufs[1], torch.zeros((h, w), dtype=torch.float32, device=means.device))
         do_refine = self.will_refine()
         pre_step = None
         # refinement clones / splits the parameters *before* the optimizer step (train.rs:361-372)
@@ -968,7 +1040,7 @@ class SplatTrainer:
                 self._update_fused(splats, cfg, (w, h), params, norm_rot, fwd, want_stats, pose, stream)
             else:
                 self._update_separate(cfg, (w, h), params, norm_rot, fwd, want_stats, pose, stream, effective,
-                                      depth_grad, grad_sync, batch_views, scene_extent, normal_grad)
+                                      depth_grad, grad_sync, batch_views, scene_extent, normal_grad, distortion_grad)
         if pose is not None:
             poses.push(view_index, pose[0])
         self.opt_time += 1

@@ -17,6 +17,7 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--strategy default|mcmc] [--cap-max 1000000] [--exposure-opt] [--export-exposures EXP.json]
         [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
         [--normal-weight W] [--normal-from-step S]
+        [--distortion-weight W] [--distortion-from-step S] [--distortion-mode depth|ndc] [--distortion-far Z]
         [--downscale-schedule STEP:FACTOR,...] [--num-downscales K] [--resolution-schedule S]
         [--contribution-prune-at STEP,...] [--contribution-prune-min 0.01]
         [--background white|black|random|R,G,B] [--no-masks] [--filter3d] [--filter3d-every 100]
@@ -58,6 +59,13 @@ brush_amd/depth_loss.py).  --depth-weight-final W2 moves the weight exponentiall
 --normal-from-step on (TrainConfig.normal_weight, brush_amd/normal_loss.py): W times the mean over all pixels of
 alpha - Nr . Nd, Nr the rendered map of the splats' normals, Nd the normal the rendered depth map implies.  It needs no
 extra data; a run with it is not bitwise reproducible (float atomics in the gradient of Nr).
+
+--distortion-weight W > 0 adds the depth-distortion term of the same trainers from step --distortion-from-step on
+(TrainConfig.distortion_weight, brush_amd/distortion.py): W times the mean over all pixels of
+sum over pairs of w_i w_j (m_i - m_j)^2, w the blending weights of a pixel's splats and m their depths
+(--distortion-mode depth) or 2DGS's NDC mapping of them (ndc, with --distortion-far).  Its gradient goes through the
+blending weights into the geometry.  No extra data; not with --pose-opt, not in deterministic mode, not bitwise
+reproducible (float atomics).
 
 --strategy mcmc trains with a fixed splat budget of --cap-max (TrainConfig.strategy, brush_amd/mcmc.py) instead of the
 clone / split / prune refinement.
@@ -121,6 +129,7 @@ class TrainLog:
     densify_by: str = "grad"                      # TrainConfig.densify_by as configured
     error_passes: List[Tuple[int, int]] = field(default_factory=list)  # (step, views): the score passes that ran
     normal_weight: float = 0.0                    # TrainConfig.normal_weight as configured (0: the term was off)
+    distortion_weight: float = 0.0                # TrainConfig.distortion_weight as configured (0: the term was off)
 
     def to_json(self) -> dict:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
@@ -132,7 +141,7 @@ class TrainLog:
                 "masked_views": int(self.masked_views), "filter3d": bool(self.filter3d),
                 "filter3d_refreshes": [int(s) for s in self.filter3d_refreshes],
                 "densify_by": self.densify_by, "error_passes": [[int(s), int(v)] for s, v in self.error_passes],
-                "normal_weight": float(self.normal_weight),
+                "normal_weight": float(self.normal_weight), "distortion_weight": float(self.distortion_weight),
                 "evals": [dataclasses.asdict(r) for r in self.evals], "losses": [float(x) for x in self.losses]}
 
 
@@ -223,7 +232,8 @@ class TrainLoop:
                             background=self.config.background,
                             masked_views=sum(m is not None for m in self.loader.masks),
                             filter3d=bool(self.config.filter3d), densify_by=self.config.densify_by,
-                            normal_weight=float(self.config.normal_weight))
+                            normal_weight=float(self.config.normal_weight),
+                            distortion_weight=float(self.config.distortion_weight))
         # error-driven densification: a host generator of its own picks the views of a score pass (the loader's draw
         # order does not change), and a fixed background colour goes to the device here, once
         self._score_rng, self._score_bg = None, None
@@ -510,6 +520,16 @@ def parser():
                    help="add the depth-normal consistency loss with this weight (0: off)")
     p.add_argument("--normal-from-step", type=int, default=TrainConfig.normal_from_step, metavar="S",
                    help="--normal-weight: the first step that carries the term")
+    p.add_argument("--distortion-weight", type=float, default=0.0, metavar="W",
+                   help="add the depth-distortion term with this weight (0: off)")
+    p.add_argument("--distortion-from-step", type=int, default=TrainConfig.distortion_from_step, metavar="S",
+                   help="--distortion-weight: the first step that carries the term")
+    p.add_argument("--distortion-mode", choices=("depth", "ndc"), default="depth",
+                   help="--distortion-weight: compare camera-space depths, or 2DGS's NDC mapping of them")
+    p.add_argument("--distortion-near", type=float, default=TrainConfig.distortion_near, metavar="Z",
+                   help="--distortion-mode ndc: the near plane of the mapping")
+    p.add_argument("--distortion-far", type=float, default=None, metavar="Z",
+                   help="--distortion-mode ndc: the far plane of the mapping (required there)")
     p.add_argument("--depth-mode", choices=("depth", "disparity"), default="depth",
                    help="compare depth / alpha, or alpha / depth (the maps then hold inverse depths)")
     p.add_argument("--downscale-schedule", default=None, metavar="STEP:FACTOR,...",
@@ -573,7 +593,10 @@ def main(argv=None) -> int:
                              densify_by=args.densify_by, densify_error_thresh=args.densify_error_thresh,
                              densify_error_views=args.densify_error_views, densify_growth=args.densify_growth,
                              densify_max_splats=args.max_splats, revised_opacity=args.revised_opacity,
-                             normal_weight=args.normal_weight, normal_from_step=args.normal_from_step)
+                             normal_weight=args.normal_weight, normal_from_step=args.normal_from_step,
+                             distortion_weight=args.distortion_weight, distortion_from_step=args.distortion_from_step,
+                             distortion_mode=args.distortion_mode, distortion_near=args.distortion_near,
+                             distortion_far=args.distortion_far)
         config.check()  # the configuration the run trains with, before the dataset is loaded
     except ValueError as e:
         p.error(str(e))

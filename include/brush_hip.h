@@ -847,6 +847,49 @@ int brush_normal_loss(const BrushUniforms *uniforms, const float *pred, const fl
                       float *v_pred, float *stats, float *loss_accum, void *workspace, size_t workspace_bytes,
                       brush_stream_t stream);
 
+/* ---- depth-distortion term (build extension; 2DGS, GOF, RaDe-GS and gsplat's 2DGS path are the models) ---------- */
+/* L(p) = sum over the unordered pairs (i, j) of the entries the forward added to pixel p of w_i w_j (m_i - m_j)^2, with
+ * w_i = alpha_i T_i the blending weight, z_i = compact_depth[cgid_i] and m_i = mu(z_i):
+ *   BRUSH_DISTORTION_DEPTH  mu(z) = z
+ *   BRUSH_DISTORTION_NDC    mu(z) = far_z / (far_z - near_z) (1 - near_z / z), 0 < near_z < far_z finite   (2DGS's mapping)
+ * All three entries replay a FINISHED brush_render_forward_depth (its uniforms, aux and compact_depth) on the forward's
+ * own walk (0.999 clamp, 1/255 test, the `next_T <= 1e-4` stop without adding); brush_amd/csrc/distortion.hip states
+ * the arithmetic.  Device pointers except `uniforms`, `aux` and `cfg`; no allocation, no synchronisation:
+ * graph-capturable; n == 0 and empty lists are legal.
+ * brush_render_distortion: stats [h][w][4] f32 (16-byte aligned) = (L, W, M1, M2) per pixel, the totals of L and of w,
+ *   w c, w c^2 with c_i = m_i - m of the pixel's first entry (L does not change under a shift of every m).  Every pixel
+ *   is written, zeros where nothing was added; no atomics, the same inputs give the same bits.
+ * brush_distortion_compact_grads: the bare gradient launch.  v_distortion [h][w] f32 is the gradient at L(p), stats
+ *   what brush_render_distortion wrote for the same cfg.  v_compact [n][16] f32, rows by COMPACT id in the layout of the
+ *   compositing backward's accumulators, is ADDED into with float atomics: words 0, 1 (v_xy), 2-4 (v_conic), 8 (v_opacity
+ *   of the drawn opacity) and 9 (v_z); words 5-7 and 10-15 and the rows of splats in no list keep their bits.  Nothing
+ *   flows through an alpha the forward clamped at 0.999.  Order dependent in its last bits.
+ * brush_render_backward_distortion: brush_render_backward_depth plus the term: the compositing backward as that entry
+ *   runs it, brush_distortion_compact_grads on the workspace's compact rows, then the unchanged parameter backward, so
+ *   means, scales, rotations, opacities (the antialiased compensation too) receive the term's gradient; v_sh receives
+ *   none.  compact_depth and v_depth are required (a zero map if nothing else supervises the depth).  Same workspace,
+ *   same aliasing rules and same outputs as brush_render_backward_depth.
+ * BRUSH_AUX_DETERMINISTIC: both gradient entries return BRUSH_ERR_INVALID_ARG (that mode keeps one row per intersection
+ *   and sums them in a fixed order: there is no compact row to add into). */
+#define BRUSH_DISTORTION_DEPTH 0u
+#define BRUSH_DISTORTION_NDC 1u
+typedef struct BrushDistortion {
+    uint32_t mode;
+    float near_z, far_z; /* NDC mode only */
+} BrushDistortion;
+int brush_render_distortion(const BrushUniforms *uniforms, const BrushAux *aux, const float *compact_depth,
+                            const BrushDistortion *cfg, uint32_t n, float *stats /* [h,w,4] */, brush_stream_t stream);
+int brush_distortion_compact_grads(const BrushUniforms *uniforms, const BrushAux *aux, const float *compact_depth,
+                                   const BrushDistortion *cfg, const float *stats, const float *v_distortion /* [h,w] */,
+                                   uint32_t n, float *v_compact /* [n][16], ADDED into */, brush_stream_t stream);
+int brush_render_backward_distortion(const BrushUniforms *uniforms, const BrushAux *aux, const float *means,
+                                     const float *log_scales, const float *quats, const float *raw_opacity, uint32_t n,
+                                     const float *out_img, const float *v_out, const float *compact_depth,
+                                     const float *v_depth, const BrushDistortion *cfg, const float *stats,
+                                     const float *v_distortion, float *v_means, float *v_xy, float *v_scales,
+                                     float *v_quats, float *v_sh, float *v_opac, void *workspace, size_t workspace_bytes,
+                                     brush_stream_t stream);
+
 /* ---- 3D smoothing filter (build extension; Mip-Splatting, Yu et al. 2024, is the model) ------------------------- */
 /* The world-space half of Mip-Splatting: every splat is low-passed at the highest rate any training view sampled it.
  * A splat carries a filter length f; the renderer sees the covariance Sigma + f^2 I and the opacity scaled by

@@ -93,17 +93,6 @@ def contributions_from_aux(uniforms, aux, img: Optional[torch.Tensor], out: Cont
     return out
 
 
-def _camera_and_size(view, downscale: int):
-    from .pyramid import downscaled_size
-
-    if isinstance(view, (tuple, list)):
-        cam, (w, h) = view[0], view[1]
-    else:  # a dataset.SceneView
-        cam, (h, w) = view.camera, view.image.shape[:2]
-    w, h = int(w), int(h)
-    return cam, (downscaled_size(w, h, downscale) if downscale > 1 else (w, h))
-
-
 def splat_contributions(splats, views, *, antialiased: bool = False, downscale: int = 1,
                         check: bool = True) -> Contributions:
     """The contributions of `splats` over `views`, each a dataset.SceneView (rendered at its image's size) or a
@@ -114,19 +103,12 @@ def splat_contributions(splats, views, *, antialiased: bool = False, downscale: 
     from .pyramid import check_factor
 
     downscale = check_factor(downscale)
-    splats.sync()  # once, as Splats.render does per call
-    dev = splats.means.device
-    n = splats.num_splats()
-    bufs = ContributionBuffers(n, dev)
+    parts = splats.frozen()  # one sync, as Splats.render does per call
+    bufs = ContributionBuffers(splats.num_splats(), parts[0].device)
     with torch.no_grad():
-        means, log_scales = splats.means.detach().contiguous(), splats.log_scales.detach().contiguous()
-        rot = splats.rotation.detach()
-        norm_rot = (rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))).contiguous()
-        sh, raw_opac = splats.sh_coeffs.detach().contiguous(), splats.raw_opacity.detach().contiguous()
         for v in views:
-            cam, size = _camera_and_size(v, downscale)
-            img, aux, u = R._forward_impl(cam, size, means, log_scales, norm_rot, sh, raw_opac, False, None,
-                                          expect_backward=False, antialiased=antialiased)
+            cam, size, _, _ = R.view_parts(v, downscale=downscale)
+            img, aux, u = R.forward_frozen(parts, cam, size, antialiased)
             contributions_from_aux(u, aux, img, bufs, check)
     c, bad = bufs.read()
     if check and bad != 0:

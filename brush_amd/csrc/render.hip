@@ -124,6 +124,41 @@ BwdWs carve_bwd(void *ws, uint32_t n, uint32_t cap, bool det) {
     return b;
 }
 
+// The depth-distortion term of brush_render_backward_distortion (distortion.hip).
+struct DistortionTerm {
+    const BrushDistortion *cfg;
+    const float *stats, *v;
+};
+
+// One backward call as its entry describes it, filled by field name ({}: everything absent).  render_backward_impl
+// reads all of it, brush_render_backward_records the part in front of the gradients.
+struct BackwardCall {
+    const BrushUniforms *uniforms;
+    const BrushAux *aux;
+    const float *means, *log_scales, *quats, *raw_opacity;
+    uint32_t n;
+    const float *out_img, *v_out;
+    float *v_means, *v_xy, *v_scales, *v_quats, *v_sh, *v_opac;  // dense gradients (the fused forms: v_xy only)
+    const AdamFuse *adam;                                        // fused forms: the optimizer step of the VJP kernel
+    void *workspace;
+    size_t workspace_bytes;
+    brush_stream_t stream;
+    // optional terms, each all there or all absent
+    const float *compact_depth, *v_depth;  // depth
+    float *v_viewmat;                      // pose
+    void *pose_ws;
+    const DistortionTerm *dist;
+};
+
+// What open_backward leaves for the kernels behind the compositing backward.
+struct BackwardOpen {
+    BwdWs ws;
+    ViewParams vp;
+    DetSumsArgs det;
+    bool filled;  // the compositing kernel zero-filled the dense gradients in passing
+    hipStream_t s;
+};
+
 inline bool aux_det(const BrushAux &a) { return (a.flags & BRUSH_AUX_DETERMINISTIC) != 0; }
 
 bool aux_ok(const BrushAux *a, bool need_final_index) {
@@ -335,19 +370,20 @@ extern "C" uint32_t brush_rgba8_row_pitch(uint32_t width) { return (width + 63u)
 // accumulators, add with hardware float atomics.  Deterministic mode: one stored row per intersection, then the
 // fixed-order per-splat sums (no zero-fill, no atomics).  Fills `det` for the consumer kernel.
 // `fill` (may be inactive): zero-fill the compositing kernel carries in passing; *filled says whether it ran.
-static int composite_backward(const BrushUniforms &u, const BrushAux &aux, const float *out_img, const float *v_out,
-                              uint32_t n, const BwdWs &ws, DetSumsArgs *det, const ZeroFill &fill, bool *filled,
-                              hipStream_t s, const float *compact_depth = nullptr, const float *v_depth = nullptr) {
+static int composite_backward(const BackwardCall &c, const BrushUniforms &u, const BwdWs &ws, DetSumsArgs *det,
+                              const ZeroFill &fill, bool *filled, hipStream_t s) {
+    const BrushAux &aux = *c.aux;
     const uint32_t w = u.img_size[0], h = u.img_size[1], tbx = u.tile_bounds[0], tby = u.tile_bounds[1];
     *filled = fill.active() && tbx * tby != 0u;  // (no tiles: no launch)
     if (ws.rows) {
         // no zero-fill stage in this mode: no launch, no event
         BRUSH_HIP_CHECK(launch_rasterize_backward(w, h, tbx, tby, aux.compact_gid_from_isect, aux.tile_bins,
-                                                  aux.projected_splats, aux.final_index, out_img, v_out, ws.v_compact,
-                                                  aux.isect_unsorted_pos, ws.rows, fill, s, compact_depth, v_depth));
+                                                  aux.projected_splats, aux.final_index, c.out_img, c.v_out,
+                                                  ws.v_compact, aux.isect_unsorted_pos, ws.rows, fill, s,
+                                                  c.compact_depth, c.v_depth));
         BRUSH_HIP_CHECK(launch_sum_isect_rows(ws.rows, aux.num_intersections, aux.cum_tiles_hit, aux.max_intersects,
                                               ws.v_compact, ws.partials, s));
-        if (v_depth)  // after the rows' sums: those write word 9 of their rows as 0
+        if (c.v_depth)  // after the rows' sums: those write word 9 of their rows as 0
             BRUSH_HIP_CHECK(launch_sum_isect_depth(ws.rows, aux.num_intersections, aux.cum_tiles_hit,
                                                    aux.max_intersects, ws.v_compact, ws.partials, s));
         mark_bwd(s, 2);
@@ -360,55 +396,51 @@ static int composite_backward(const BrushUniforms &u, const BrushAux &aux, const
     // compact-order accumulators are atomically added to: zero the first V rows (render.rs:505-507) — unless the
     // forward of this render already did (BrushAux::bwd_accum + BRUSH_AUX_ACCUM_ZEROED)
     if (!(aux.flags & BRUSH_AUX_ACCUM_ZEROED)) {
-        BRUSH_HIP_CHECK(launch_zero_compact_grads(aux.num_visible, n, ws.v_compact, s));
+        BRUSH_HIP_CHECK(launch_zero_compact_grads(aux.num_visible, c.n, ws.v_compact, s));
         mark_bwd(s, 1);
     }
     if (stop_behind(BRUSH_STAGE_BWD_ZERO)) return BRUSH_OK;
     BRUSH_HIP_CHECK(launch_rasterize_backward(w, h, tbx, tby, aux.compact_gid_from_isect, aux.tile_bins,
-                                              aux.projected_splats, aux.final_index, out_img, v_out, ws.v_compact,
-                                              nullptr, nullptr, fill, s, compact_depth, v_depth));
+                                              aux.projected_splats, aux.final_index, c.out_img, c.v_out, ws.v_compact,
+                                              nullptr, nullptr, fill, s, c.compact_depth, c.v_depth));
     mark_bwd(s, 2);
     return BRUSH_OK;
 }
 
-// The depth-distortion term of brush_render_backward_distortion (distortion.hip).
-struct DistortionTerm {
-    const BrushDistortion *cfg;
-    const float *stats, *v;
-};
-
-static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *means,
-                                const float *log_scales, const float *quats, const float *raw_opacity, uint32_t n,
-                                const float *out_img, const float *v_out, float *v_means, float *v_xy,
-                                float *v_scales, float *v_quats, float *v_sh, float *v_opac, const AdamFuse *adam,
-                                void *workspace, size_t workspace_bytes, brush_stream_t stream,
-                                const float *compact_depth = nullptr, const float *v_depth = nullptr,
-                                float *v_viewmat = nullptr, void *pose_ws = nullptr,
-                                const DistortionTerm *dist = nullptr) {
-    if (!uniforms_ok(h_uniforms) || !aux_ok(h_aux, true) || !out_img || !v_out || !workspace)
+// The opening every backward shares: the checks of what every BackwardCall holds (an entry makes its own first: all
+// refusals come before any HIP call, and an invalid argument is reported whatever the workspace's size), the
+// workspace, the view parameters, and the compositing backward with `fill` carried in passing.
+static int open_backward(const BackwardCall &c, const ZeroFill &fill, BackwardOpen *o) {
+    if (!uniforms_ok(c.uniforms) || !aux_ok(c.aux, true) || !c.out_img || !c.v_out || !c.workspace)
         return BRUSH_ERR_INVALID_ARG;
-    if (dist && (!v_depth || adam || v_viewmat || !distortion_args_ok(h_aux, dist->cfg, dist->stats, dist->v)))
-        return BRUSH_ERR_INVALID_ARG;
-    if ((compact_depth != nullptr) != (v_depth != nullptr) || (v_depth && adam)) return BRUSH_ERR_INVALID_ARG;
-    if ((v_viewmat != nullptr) != (pose_ws != nullptr)) return BRUSH_ERR_INVALID_ARG;
-    if (n > 0 && (!means || !log_scales || !quats || !raw_opacity || !v_xy)) return BRUSH_ERR_INVALID_ARG;
-    if (n > 0 && !adam && (!v_means || !v_scales || !v_quats || !v_sh || !v_opac)) return BRUSH_ERR_INVALID_ARG;
-    const BrushAux &aux = *h_aux;
-    const BwdWs ws = carve_bwd(workspace, n, aux.max_intersects, aux_det(aux));
-    if (workspace_bytes < ws.bytes) return BRUSH_ERR_WORKSPACE_SMALL;
-    if ((aux.flags & BRUSH_AUX_ACCUM_ZEROED) && !aux_det(aux) && aux.bwd_accum != ws.v_compact) return BRUSH_ERR_INVALID_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c.n > 0 && (!c.means || !c.log_scales || !c.quats || !c.raw_opacity)) return BRUSH_ERR_INVALID_ARG;
+    const BrushAux &aux = *c.aux;
+    o->ws = carve_bwd(c.workspace, c.n, aux.max_intersects, aux_det(aux));
+    if (c.workspace_bytes < o->ws.bytes) return BRUSH_ERR_WORKSPACE_SMALL;
+    if ((aux.flags & BRUSH_AUX_ACCUM_ZEROED) && !aux_det(aux) && aux.bwd_accum != o->ws.v_compact) return BRUSH_ERR_INVALID_ARG;
+    o->s = static_cast<hipStream_t>(c.stream);
+    BrushUniforms u = *c.uniforms;
+    u.total_splats = c.n;
+    o->vp = make_view_params(u, c.n);
+    mark_bwd(o->s, 0);
+    return composite_backward(c, u, o->ws, &o->det, fill, &o->filled, o->s);
+}
 
-    BrushUniforms u = *h_uniforms;
-    u.total_splats = n;
-    const ViewParams vp = make_view_params(u, n);
+static int render_backward_impl(const BackwardCall &c) {
+    if (c.dist && (!c.v_depth || c.adam || c.v_viewmat || !distortion_args_ok(c.aux, c.dist->cfg, c.dist->stats, c.dist->v)))
+        return BRUSH_ERR_INVALID_ARG;
+    if ((c.compact_depth != nullptr) != (c.v_depth != nullptr) || (c.v_depth && c.adam)) return BRUSH_ERR_INVALID_ARG;
+    if ((c.v_viewmat != nullptr) != (c.pose_ws != nullptr)) return BRUSH_ERR_INVALID_ARG;
+    if (c.n > 0 && !c.v_xy) return BRUSH_ERR_INVALID_ARG;
+    if (c.n > 0 && !c.adam && (!c.v_means || !c.v_scales || !c.v_quats || !c.v_sh || !c.v_opac)) return BRUSH_ERR_INVALID_ARG;
 
     // Dense gradients (render.rs:539-547,573-575 zero-fill them with launches of their own): the VALU-bound compositing
     // kernel stores the zeros in passing, the VJP kernel behind it writes the visible splats' rows only.
     ZeroFill fill{};
-    if (!adam && n > 0) {
-        const size_t nn = n, C = (size_t)(u.sh_degree + 1) * (u.sh_degree + 1);
-        float *const arrays[kFillSegs] = {v_sh, v_means, v_scales, v_quats, v_opac, v_xy};
+    if (!c.adam && c.n > 0 && uniforms_ok(c.uniforms)) {  // (refused uniforms: the opening says so)
+        const BrushUniforms &u = *c.uniforms;
+        const size_t nn = c.n, C = (size_t)(u.sh_degree + 1) * (u.sh_degree + 1);
+        float *const arrays[kFillSegs] = {c.v_sh, c.v_means, c.v_scales, c.v_quats, c.v_opac, c.v_xy};
         const size_t floats[kFillSegs] = {nn * C * 3, nn * 3, nn * 3, nn * 4, nn, nn * 2};
         (void)make_zero_fill(&fill, arrays, floats, kFillSegs);  // (unaligned / oversized arrays: zeros stay in the VJP kernel)
         // a frame of a few tiles has a few waves: more than 1 MiB of zeros per tile would turn the compositing launch
@@ -416,31 +448,30 @@ static int render_backward_impl(const BrushUniforms *h_uniforms, const BrushAux 
         const uint64_t tiles = (uint64_t)u.tile_bounds[0] * u.tile_bounds[1];
         if (fill.first_block[kFillSegs] > 1024ull * (tiles ? tiles : 1ull)) fill = ZeroFill{};
     }
-    mark_bwd(s, 0);
-    DetSumsArgs det;
-    bool filled = false;
-    if (const int rc = composite_backward(u, aux, out_img, v_out, n, ws, &det, fill, &filled, s, compact_depth, v_depth))
-        return rc;
+    BackwardOpen o;
+    if (const int rc = open_backward(c, fill, &o)) return rc;
     if (stop_behind(BRUSH_STAGE_BWD_ZERO) || stop_behind(BRUSH_STAGE_RASTERIZE_BWD)) return BRUSH_OK;
+    const BrushAux &aux = *c.aux;
+    const bool antialiased = (aux.flags & BRUSH_AUX_ANTIALIASED) != 0;
     // depth distortion: its per-record VJP joins the compact rows the compositing backward has just summed
-    if (dist)
-        if (const int rc = launch_distortion_grad(h_uniforms, h_aux, compact_depth, dist->cfg, dist->stats, dist->v, n,
-                                                  ws.v_compact, stream))
+    if (c.dist)
+        if (const int rc = launch_distortion_grad(c.uniforms, c.aux, c.compact_depth, c.dist->cfg, c.dist->stats,
+                                                  c.dist->v, c.n, o.ws.v_compact, c.stream))
             return rc;
     // camera-pose gradient: ahead of the parameter VJP, whose fused Adam forms overwrite `means` in place
-    if (v_viewmat)
-        BRUSH_HIP_CHECK(launch_view_grad(vp, means, log_scales, quats, raw_opacity, aux.num_visible, n,
-                                         aux.global_from_compact_gid, ws.v_compact, det, v_depth != nullptr,
-                                         (aux.flags & BRUSH_AUX_ANTIALIASED) != 0, pose_ws, v_viewmat, s));
+    if (c.v_viewmat)
+        BRUSH_HIP_CHECK(launch_view_grad(o.vp, c.means, c.log_scales, c.quats, c.raw_opacity, aux.num_visible, c.n,
+                                         aux.global_from_compact_gid, o.ws.v_compact, o.det, c.v_depth != nullptr,
+                                         antialiased, c.pose_ws, c.v_viewmat, o.s));
     // GatherGrads + ProjectBackwards fused, dense outputs written once (render.rs:534-594)
-    BRUSH_HIP_CHECK(launch_project_backward(vp, means, log_scales, quats, raw_opacity, aux.compact_from_global_gid,
-                                            ws.v_compact, v_means, v_xy, v_scales, v_quats, v_sh, v_opac, adam, det,
-                                            filled, s, (aux.flags & BRUSH_AUX_ANTIALIASED) != 0));
+    BRUSH_HIP_CHECK(launch_project_backward(o.vp, c.means, c.log_scales, c.quats, c.raw_opacity,
+                                            aux.compact_from_global_gid, o.ws.v_compact, c.v_means, c.v_xy, c.v_scales,
+                                            c.v_quats, c.v_sh, c.v_opac, c.adam, o.det, o.filled, o.s, antialiased));
     // depth: z = viewmat row 2 . [mean, 1] carries v_z into v_means
-    if (v_depth)
-        BRUSH_HIP_CHECK(launch_depth_means_grad(vp, aux.num_visible, n, aux.global_from_compact_gid, ws.v_compact, det,
-                                                v_means, s));
-    mark_bwd(s, 3);
+    if (c.v_depth)
+        BRUSH_HIP_CHECK(launch_depth_means_grad(o.vp, aux.num_visible, c.n, aux.global_from_compact_gid, o.ws.v_compact,
+                                                o.det, c.v_means, o.s));
+    mark_bwd(o.s, 3);
     return BRUSH_OK;
 }
 
@@ -495,8 +526,12 @@ extern "C" int brush_render_backward(const BrushUniforms *h_uniforms, const Brus
                                      uint32_t n, const float *out_img, const float *v_out, float *v_means,
                                      float *v_xy, float *v_scales, float *v_quats, float *v_sh, float *v_opac,
                                      void *workspace, size_t workspace_bytes, brush_stream_t stream) {
-    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
-                                v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream);
+    BackwardCall c{};
+    c.uniforms = h_uniforms, c.aux = h_aux, c.means = means, c.log_scales = log_scales, c.quats = quats;
+    c.raw_opacity = raw_opacity, c.n = n, c.out_img = out_img, c.v_out = v_out;
+    c.v_means = v_means, c.v_xy = v_xy, c.v_scales = v_scales, c.v_quats = v_quats, c.v_sh = v_sh, c.v_opac = v_opac;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    return render_backward_impl(c);
 }
 
 extern "C" int brush_render_backward_depth(const BrushUniforms *h_uniforms, const BrushAux *h_aux, const float *means,
@@ -506,9 +541,13 @@ extern "C" int brush_render_backward_depth(const BrushUniforms *h_uniforms, cons
                                            float *v_xy, float *v_scales, float *v_quats, float *v_sh, float *v_opac,
                                            void *workspace, size_t workspace_bytes, brush_stream_t stream) {
     if (!compact_depth || !v_depth) return BRUSH_ERR_INVALID_ARG;
-    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
-                                v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream,
-                                compact_depth, v_depth);
+    BackwardCall c{};
+    c.uniforms = h_uniforms, c.aux = h_aux, c.means = means, c.log_scales = log_scales, c.quats = quats;
+    c.raw_opacity = raw_opacity, c.n = n, c.out_img = out_img, c.v_out = v_out;
+    c.v_means = v_means, c.v_xy = v_xy, c.v_scales = v_scales, c.v_quats = v_quats, c.v_sh = v_sh, c.v_opac = v_opac;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.compact_depth = compact_depth, c.v_depth = v_depth;
+    return render_backward_impl(c);
 }
 
 extern "C" int brush_render_backward_distortion(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
@@ -521,9 +560,13 @@ extern "C" int brush_render_backward_distortion(const BrushUniforms *h_uniforms,
                                                 size_t workspace_bytes, brush_stream_t stream) {
     if (!compact_depth || !v_depth) return BRUSH_ERR_INVALID_ARG;
     const DistortionTerm dist{cfg, stats, v_distortion};
-    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
-                                v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream,
-                                compact_depth, v_depth, nullptr, nullptr, &dist);
+    BackwardCall c{};
+    c.uniforms = h_uniforms, c.aux = h_aux, c.means = means, c.log_scales = log_scales, c.quats = quats;
+    c.raw_opacity = raw_opacity, c.n = n, c.out_img = out_img, c.v_out = v_out;
+    c.v_means = v_means, c.v_xy = v_xy, c.v_scales = v_scales, c.v_quats = v_quats, c.v_sh = v_sh, c.v_opac = v_opac;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.compact_depth = compact_depth, c.v_depth = v_depth, c.dist = &dist;
+    return render_backward_impl(c);
 }
 
 extern "C" int brush_pose_grad_workspace_size(uint32_t n, size_t *bytes) {
@@ -541,9 +584,13 @@ extern "C" int brush_render_backward_pose(const BrushUniforms *h_uniforms, const
                                           void *pose_workspace, size_t pose_workspace_bytes, brush_stream_t stream) {
     if (!v_viewmat || !pose_workspace) return BRUSH_ERR_INVALID_ARG;
     if (pose_workspace_bytes < pose_grad_workspace_bytes(n)) return BRUSH_ERR_WORKSPACE_SMALL;
-    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats, raw_opacity, n, out_img, v_out, v_means,
-                                v_xy, v_scales, v_quats, v_sh, v_opac, nullptr, workspace, workspace_bytes, stream,
-                                compact_depth, v_depth, v_viewmat, pose_workspace);
+    BackwardCall c{};
+    c.uniforms = h_uniforms, c.aux = h_aux, c.means = means, c.log_scales = log_scales, c.quats = quats;
+    c.raw_opacity = raw_opacity, c.n = n, c.out_img = out_img, c.v_out = v_out;
+    c.v_means = v_means, c.v_xy = v_xy, c.v_scales = v_scales, c.v_quats = v_quats, c.v_sh = v_sh, c.v_opac = v_opac;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.compact_depth = compact_depth, c.v_depth = v_depth, c.v_viewmat = v_viewmat, c.pose_ws = pose_workspace;
+    return render_backward_impl(c);
 }
 
 static int render_backward_adam_impl(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
@@ -561,9 +608,13 @@ static int render_backward_adam_impl(const BrushUniforms *h_uniforms, const Brus
                         grad_2d_accum, xy_grad_counts, h_uniforms->img_size[0], h_uniforms->img_size[1],
                         h_uniforms->sh_degree, &af))
         return BRUSH_ERR_INVALID_ARG;
-    return render_backward_impl(h_uniforms, h_aux, means, log_scales, quats_fed, raw_opacity, n, out_img, v_out,
-                                nullptr, v_xy, nullptr, nullptr, nullptr, nullptr, &af, workspace, workspace_bytes,
-                                stream, nullptr, nullptr, v_viewmat, pose_ws);
+    BackwardCall c{};
+    c.uniforms = h_uniforms, c.aux = h_aux, c.means = means, c.log_scales = log_scales, c.quats = quats_fed;
+    c.raw_opacity = raw_opacity, c.n = n, c.out_img = out_img, c.v_out = v_out;
+    c.v_xy = v_xy, c.adam = &af;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.v_viewmat = v_viewmat, c.pose_ws = pose_ws;
+    return render_backward_impl(c);
 }
 
 extern "C" int brush_render_backward_adam(const BrushUniforms *h_uniforms, const BrushAux *h_aux,
@@ -600,28 +651,18 @@ extern "C" int brush_render_backward_records(const BrushUniforms *h_uniforms, co
                                              uint32_t n, const float *out_img, const float *v_out, float *records,
                                              uint32_t max_rows, void *workspace, size_t workspace_bytes,
                                              brush_stream_t stream) {
-    if (!uniforms_ok(h_uniforms) || !aux_ok(h_aux, true) || !out_img || !v_out || !workspace)
-        return BRUSH_ERR_INVALID_ARG;
-    if (n > 0 && (!means || !log_scales || !quats || !raw_opacity || (max_rows > 0 && !records)))
-        return BRUSH_ERR_INVALID_ARG;
-    if (misaligned(records, 16)) return BRUSH_ERR_INVALID_ARG;
-    if (h_aux->flags & BRUSH_AUX_ANTIALIASED) return BRUSH_ERR_INVALID_ARG;  // out of scope (brush_hip.h)
-    const BrushAux &aux = *h_aux;
-    const BwdWs ws = carve_bwd(workspace, n, aux.max_intersects, aux_det(aux));
-    if (workspace_bytes < ws.bytes) return BRUSH_ERR_WORKSPACE_SMALL;
-    if ((aux.flags & BRUSH_AUX_ACCUM_ZEROED) && !aux_det(aux) && aux.bwd_accum != ws.v_compact) return BRUSH_ERR_INVALID_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    BrushUniforms u = *h_uniforms;
-    u.total_splats = n;
-    const ViewParams vp = make_view_params(u, n);
-    mark_bwd(s, 0);
-    DetSumsArgs det;
-    bool filled = false;
-    if (const int rc = composite_backward(u, aux, out_img, v_out, n, ws, &det, ZeroFill{}, &filled, s)) return rc;
-    BRUSH_HIP_CHECK(launch_project_backward_records(vp, means, log_scales, quats, raw_opacity, aux.num_visible,
-                                                    aux.global_from_compact_gid, ws.v_compact, records, max_rows, det,
-                                                    s));
-    mark_bwd(s, 3);
+    if ((n > 0 && max_rows > 0 && !records) || misaligned(records, 16)) return BRUSH_ERR_INVALID_ARG;
+    if (h_aux && (h_aux->flags & BRUSH_AUX_ANTIALIASED)) return BRUSH_ERR_INVALID_ARG;  // out of scope (brush_hip.h)
+    BackwardCall c{};
+    c.uniforms = h_uniforms, c.aux = h_aux, c.means = means, c.log_scales = log_scales, c.quats = quats;
+    c.raw_opacity = raw_opacity, c.n = n, c.out_img = out_img, c.v_out = v_out;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    BackwardOpen o;
+    if (const int rc = open_backward(c, ZeroFill{}, &o)) return rc;
+    BRUSH_HIP_CHECK(launch_project_backward_records(o.vp, means, log_scales, quats, raw_opacity, h_aux->num_visible,
+                                                    h_aux->global_from_compact_gid, o.ws.v_compact, records, max_rows,
+                                                    o.det, o.s));
+    mark_bwd(o.s, 3);
     return BRUSH_OK;
 }
 

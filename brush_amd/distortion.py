@@ -28,6 +28,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from . import render as R
+from .render import check_tensor
 
 MODES = {"depth": _lib.DISTORTION_DEPTH, "ndc": _lib.DISTORTION_NDC}
 DEFAULT_NEAR = 0.2
@@ -63,12 +65,6 @@ def _frame(uniforms, compact_depth):
     return h, w, n, dev
 
 
-def _check_map(t, shape, dev, what):
-    if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev \
-            or not t.is_contiguous():
-        raise ValueError(f"{what} must be a contiguous float32 {list(shape)} tensor on {dev}")
-
-
 def _refuse_deterministic(aux):
     if aux.deterministic:
         raise ValueError("the distortion term has no deterministic mode: that mode keeps one gradient row per "
@@ -86,7 +82,7 @@ def distortion_from_aux(uniforms, aux, compact_depth: torch.Tensor, cfg: Optiona
     if out is None:
         out = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
     else:
-        _check_map(out, (h, w, 4), dev, "out")
+        check_tensor(out, torch.float32, (h, w, 4), "out", dev)
     s = aux._as_struct()
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().brush_render_distortion(C.byref(uniforms), C.byref(s), compact_depth.data_ptr(),
@@ -102,8 +98,8 @@ def distortion_compact_grads_from_aux(uniforms, aux, compact_depth: torch.Tensor
     returns it.  `stats`: distortion_from_aux of the same forward and cfg.  ValueError in deterministic mode."""
     h, w, n, dev = _frame(uniforms, compact_depth)
     _refuse_deterministic(aux)
-    _check_map(stats, (h, w, 4), dev, "stats")
-    _check_map(v_distortion, (h, w), dev, "v_distortion")
+    check_tensor(stats, torch.float32, (h, w, 4), "stats", dev)
+    check_tensor(v_distortion, torch.float32, (h, w), "v_distortion", dev)
     if not isinstance(v_compact, torch.Tensor) or v_compact.dim() != 2 or v_compact.shape[1] != COMPACT_STRIDE \
             or v_compact.shape[0] < max(n, 1) or v_compact.dtype != torch.float32 or v_compact.device != dev \
             or not v_compact.is_contiguous():
@@ -122,67 +118,10 @@ def backward_distortion(u, aux, means, log_scales, quats, raw_opacity, ncoef, ou
     """brush_render_backward_distortion on one finished depth forward: render._backward_impl's results (the dict of
     dense gradients and their block) for the gradients `v_out` [h,w,4] on the image, `v_depth` [h,w] on the accumulated
     depth and `v_distortion` [h,w] on L together."""
-    from . import render as R
-
     _refuse_deterministic(aux)
-    n, dev = means.shape[0], means.device
-    w, h = int(u.img_size[0]), int(u.img_size[1])
-    _check_map(stats, (h, w, 4), dev, "stats")
-    layout, total = R.grad_block_layout(n, ncoef)
-    if block is None:
-        block = torch.empty((max(total, 1),), dtype=torch.float32, device=dev)
-    assert block.numel() >= total and block.dtype == torch.float32 and block.is_contiguous()
-    g = {}
-    for name, shape in (("v_means", (n, 3)), ("v_scales", (n, 3)), ("v_quats", (n, 4)), ("v_opac", (n,)),
-                        ("v_sh", (n, ncoef, 3)), ("v_xy", (n, 2))):
-        off, sz = layout[name]
-        g[name] = block[off:off + sz].view(shape)
-    nbytes = _lib.size_query("brush_bwd_workspace_size_flags", n, w, h, int(u.sh_degree), int(aux.max_intersects),
-                             aux.workspace_flags)
-    v_out, v_depth, v_distortion = v_out.contiguous(), v_depth.contiguous(), v_distortion.contiguous()
-    ws, s = aux.backward_workspace(nbytes, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().brush_render_backward_distortion(
-            C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(), quats.data_ptr(), raw_opacity.data_ptr(),
-            n, out_img.data_ptr(), v_out.data_ptr(), compact_depth.data_ptr(), v_depth.data_ptr(), C.byref(cfg),
-            stats.data_ptr(), v_distortion.data_ptr(), g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
-            g["v_scales"].data_ptr(), g["v_quats"].data_ptr(), g["v_sh"].data_ptr(), g["v_opac"].data_ptr(),
-            ws.data_ptr(), nbytes, _lib.current_stream(dev)), "brush_render_backward_distortion")
-    return g, block
-
-
-class _RenderSplatsDistortionFn(torch.autograd.Function):
-    """render_splats_depth with the distortion map as a third output; five parents (no xy dummy)."""
-
-    @staticmethod
-    def forward(ctx, means, log_scales, quats, sh_coeffs, raw_opacity, holder):
-        from . import render as R
-
-        depth = R._depth_buffers(means.shape[0], holder["img_size"], means.device)
-        out, aux, u = R._forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
-                                      raw_opacity, False, holder["max_intersects"], deterministic=False, depth=depth,
-                                      antialiased=holder["antialiased"])
-        stats = distortion_from_aux(u, aux, depth[1], holder["cfg"])
-        holder["aux"], holder["uniforms"], holder["stats"] = aux, u, stats
-        ctx.u, ctx.aux, ctx.ncoef, ctx.cfg = u, aux, sh_coeffs.shape[1], holder["cfg"]
-        ctx.save_for_backward(means, log_scales, quats, raw_opacity, out, depth[1], stats)
-        return out, depth[0], stats[..., 0].clone()
-
-    @staticmethod
-    def backward(ctx, v_output, v_depth, v_dist):
-        means, log_scales, quats, raw_opacity, out, compact_depth, stats = ctx.saved_tensors
-        hw = out.shape[:2]
-
-        def zeros():
-            return torch.zeros(hw, dtype=torch.float32, device=out.device)
-
-        # a zero (or absent) gradient on an output is passed as zeros
-        v_output = torch.zeros_like(out) if v_output is None else v_output.to(torch.float32)
-        v_depth = zeros() if v_depth is None else v_depth.to(torch.float32)
-        v_dist = zeros() if v_dist is None else v_dist.to(torch.float32)
-        g, _ = backward_distortion(ctx.u, ctx.aux, means, log_scales, quats, raw_opacity, ctx.ncoef, out, v_output,
-                                   compact_depth, v_depth, ctx.cfg, stats, v_dist)
-        return g["v_means"], g["v_scales"], g["v_quats"], g["v_sh"], g["v_opac"], None
+    check_tensor(stats, torch.float32, (int(u.img_size[1]), int(u.img_size[0]), 4), "stats", means.device)
+    return R._backward_impl(u, aux, means, log_scales, quats, raw_opacity, ncoef, out_img, v_out, block,
+                            depth=(compact_depth, v_depth), distortion=(cfg, stats, v_distortion))
 
 
 def render_distortion(camera, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, *, mode: str = "depth",
@@ -194,26 +133,14 @@ def render_distortion(camera, img_size, means, log_scales, quats, sh_coeffs, raw
     the blending weights too; `sh_coeffs` receives zeros from the distortion.  mode, near, far: distortion_config (`far`
     is required for "ndc").  Raises ValueError in deterministic mode (render.DETERMINISTIC / BRUSH_DETERMINISTIC).
     `quats` must be unit quaternions, as for render_splats."""
-    from . import render as R
-
     cfg = distortion_config(mode, near, far)
     R._check_inputs(means, None, log_scales, quats, sh_coeffs, raw_opacity)
     if R.deterministic_default():
         raise ValueError("render_distortion has no deterministic mode: that mode keeps one gradient row per "
                          "intersection, the term adds into per-splat rows")
-    tracked = torch.is_grad_enabled() and any(
-        t.requires_grad for t in (means, log_scales, quats, sh_coeffs, raw_opacity))
-    if not tracked:
-        with torch.no_grad():
-            bufs = R._depth_buffers(means.shape[0], img_size, means.device)
-            img, aux, u = R._forward_impl(camera, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, False,
-                                          max_intersects, deterministic=False, expect_backward=False, depth=bufs,
-                                          antialiased=antialiased)
-            stats = distortion_from_aux(u, aux, bufs[1], cfg)
-        return img, bufs[0], stats[..., 0].clone(), aux
-    holder = {"cam": camera, "img_size": img_size, "max_intersects": max_intersects, "antialiased": bool(antialiased),
-              "cfg": cfg}
-    img, depth, dist = _RenderSplatsDistortionFn.apply(means, log_scales, quats, sh_coeffs, raw_opacity, holder)
+    (img, depth, dist), holder = R._render_op(camera, img_size, means, None, log_scales, quats, sh_coeffs, raw_opacity,
+                                              max_intersects=max_intersects, deterministic=False,
+                                              antialiased=antialiased, distortion=cfg)
     return img, depth, dist, holder["aux"]
 
 
@@ -227,7 +154,7 @@ def distortion_loss_into(stats: torch.Tensor, v_distortion_out: torch.Tensor, *,
     if not isinstance(stats, torch.Tensor) or stats.dim() != 3 or stats.shape[2] != 4 or stats.dtype != torch.float32:
         raise ValueError("stats must be the float32 [h,w,4] result of distortion_from_aux")
     h, w, dev = int(stats.shape[0]), int(stats.shape[1]), stats.device
-    _check_map(v_distortion_out, (h, w), dev, "v_distortion_out")
+    check_tensor(v_distortion_out, torch.float32, (h, w), "v_distortion_out", dev)
     weight = float(weight)
     if not (math.isfinite(weight) and weight >= 0.0):
         raise ValueError(f"weight must be finite and >= 0, got {weight!r}")

@@ -134,35 +134,6 @@ def error_scores_from_aux(uniforms, aux, error_map: torch.Tensor, bufs: ErrorSco
     return bufs
 
 
-def _view_parts(view, dev, downscale: int, use_masks: bool):
-    """(camera, gt, mask) of one view on the device.  A (Camera, gt, mask or None) triple of device tensors is taken as
-    it is (its size is the render's); a dataset.SceneView is uploaded and, with downscale > 1, resized as the training
-    loader resizes it."""
-    import numpy as np
-
-    if isinstance(view, (tuple, list)):
-        cam, gt, mask = view
-        return cam, gt, (mask if use_masks else None)
-    from .pyramid import area_resize, nearest_resize
-
-    img = np.require(view.image, requirements=["C"])
-    if img.ndim != 3 or img.dtype != np.uint8 or img.shape[2] not in (3, 4):
-        raise ValueError(f"{view.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
-    gt = torch.from_numpy(np.array(img, copy=True)).to(dev)
-    mask = getattr(view, "mask", None) if use_masks else None
-    if mask is not None:
-        if mask.dtype != np.uint8 or tuple(mask.shape) != tuple(img.shape[:2]):
-            raise ValueError(f"{view.name}: the view's mask must be uint8 [h,w] = {tuple(img.shape[:2])}, got "
-                             f"{mask.dtype} {mask.shape}")
-        mask = torch.from_numpy(np.array(mask, copy=True, order="C")).to(dev)
-    if downscale > 1:
-        gt = area_resize(gt, factor=downscale)
-        if mask is not None:
-            mask = nearest_resize(mask.to(torch.int16).view(torch.uint16),
-                                  factor=downscale).view(torch.int16).to(torch.uint8)
-    return view.camera, gt, mask
-
-
 def splat_error_scores(splats, views, *, antialiased: bool = False, downscale: int = 1, background=None,
                        use_masks: bool = True, error: Optional[Callable] = None) -> ErrorScoreBuffers:
     """The error shares of `splats` over `views`, each a dataset.SceneView (uploaded here; `downscale` = f > 1: at
@@ -181,20 +152,14 @@ def splat_error_scores(splats, views, *, antialiased: bool = False, downscale: i
     downscale = check_factor(downscale)
     if isinstance(background, str) and background == "random":
         raise ValueError("an error pass has no 'random' background: score over a fixed colour")
-    splats.sync()  # once, as Splats.render does per call
-    dev = splats.means.device
+    parts = splats.frozen()  # one sync, as Splats.render does per call
+    dev = parts[0].device
     bufs = ErrorScoreBuffers(splats.num_splats(), dev)
     bg = as_background(background, dev)
     with torch.no_grad():
-        means, log_scales = splats.means.detach().contiguous(), splats.log_scales.detach().contiguous()
-        rot = splats.rotation.detach()
-        norm_rot = (rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))).contiguous()
-        sh, raw_opac = splats.sh_coeffs.detach().contiguous(), splats.raw_opacity.detach().contiguous()
         for v in views:
-            cam, gt, mask = _view_parts(v, dev, downscale, use_masks)
-            h, w = int(gt.shape[0]), int(gt.shape[1])
-            pred, aux, u = R._forward_impl(cam, (w, h), means, log_scales, norm_rot, sh, raw_opac, False, None,
-                                           expect_backward=False, antialiased=antialiased)
+            cam, size, gt, mask = R.view_parts(v, dev, downscale=downscale, gt=True, mask=use_masks)
+            pred, aux, u = R.forward_frozen(parts, cam, size, antialiased)
             if bg is not None:
                 pred, gt = compose_forward(pred, gt, background=bg, mask=mask)
             if error is None:

@@ -29,6 +29,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .render import check_tensor
 
 Q24 = float(1 << 24)  # the fixed point of a sum (brush_render_feature_sums)
 MAX_CHANNELS = 64     # BRUSH_FEATURE_MAX_CHANNELS
@@ -55,13 +56,6 @@ def _check_rows(t, dtype, what: str, dev=None) -> int:
     return _check_channels(t.shape[1])
 
 
-def _check_image(t, dtype, shape, what: str, dev):
-    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
-            or t.device != dev):
-        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else repr(t)
-        raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got {got}")
-
-
 def _ptr(t):
     return t.data_ptr() if t.numel() else None
 
@@ -77,7 +71,7 @@ def features_from_aux(uniforms, aux, features: torch.Tensor, out: Optional[torch
     if out is None:
         out = torch.empty((h, w, c), dtype=torch.float32, device=dev)
     else:
-        _check_image(out, torch.float32, (h, w, c), "out", dev)
+        check_tensor(out, torch.float32, (h, w, c), "out", dev)
     s = aux._as_struct()
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().brush_render_features(C.byref(uniforms), C.byref(s), _ptr(features), c, out.data_ptr(),
@@ -94,7 +88,7 @@ def feature_grads_from_aux(uniforms, aux, v_out: torch.Tensor, v_features: torch
     c = _check_rows(v_features, torch.float32, "v_features")
     dev = v_features.device
     h, w = _frame(uniforms)
-    _check_image(v_out, torch.float32, (h, w, c), "v_out", dev)
+    check_tensor(v_out, torch.float32, (h, w, c), "v_out", dev)
     if v_features.shape[0] == 0:
         return v_features
     s = aux._as_struct()
@@ -116,10 +110,10 @@ def feature_sums_from_aux(uniforms, aux, maps_or_labels: torch.Tensor, sums: tor
     h, w = _frame(uniforms)
     m = maps_or_labels
     if isinstance(m, torch.Tensor) and m.dtype == torch.uint8:
-        _check_image(m, torch.uint8, (h, w), "a label image", dev)
+        check_tensor(m, torch.uint8, (h, w), "a label image", dev)
         kind = MAP_LABEL_U8
     else:
-        _check_image(m, torch.float32, (h, w, c), "maps", dev)
+        check_tensor(m, torch.float32, (h, w, c), "maps", dev)
         kind = MAP_F32
     if sums.shape[0] == 0:
         return sums
@@ -232,20 +226,6 @@ def _device_map(m, dev, num_classes):
     return m.contiguous(), None
 
 
-def _view_camera_mask(view, dev, use_masks: bool):
-    """(camera, mask or None) of a (Camera, gt, mask or None) device triple or a dataset.SceneView (its mask is uploaded
-    here)."""
-    import numpy as np
-
-    if isinstance(view, (tuple, list)):
-        cam, _, mask = view
-        return cam, (mask if use_masks else None)
-    mask = getattr(view, "mask", None) if use_masks else None
-    if mask is not None:
-        mask = torch.from_numpy(np.array(mask, copy=True, order="C")).to(dev)
-    return view.camera, mask
-
-
 def splat_feature_sums(splats, views, maps, *, antialiased: bool = False, use_masks: bool = True,
                        num_classes: Optional[int] = None) -> FeatureSums:
     """The exact per-splat sums of `maps` over `views`, with the geometry frozen.  views: dataset.SceneViews or
@@ -266,17 +246,13 @@ def splat_feature_sums(splats, views, maps, *, antialiased: bool = False, use_ma
             raise ValueError(f"at most {MAX_CHANNELS} classes per pass, got {int(num_classes)}: remap the labels "
                              f"into [0, {MAX_CHANNELS}) (or lift them in groups)")
         num_classes = _check_channels(num_classes)
-    splats.sync()  # once, as Splats.render does per call
-    dev = splats.means.device
+    parts = splats.frozen()  # one sync, as Splats.render does per call
+    dev = parts[0].device
     n = splats.num_splats()
     sums = weight = None
     with torch.no_grad():
-        means, log_scales = splats.means.detach().contiguous(), splats.log_scales.detach().contiguous()
-        rot = splats.rotation.detach()
-        norm_rot = (rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))).contiguous()
-        sh, raw_opac = splats.sh_coeffs.detach().contiguous(), splats.raw_opacity.detach().contiguous()
         for view, m in zip(views, maps):
-            cam, mask = _view_camera_mask(view, dev, use_masks)
+            cam, _, _, mask = R.view_parts(view, dev, mask=use_masks)
             fmap, labels = _device_map(m, dev, num_classes)
             h, w = (int(x) for x in (labels if fmap is None else fmap).shape[:2])
             c = num_classes if fmap is None else _check_channels(fmap.shape[2])
@@ -296,8 +272,7 @@ def splat_feature_sums(splats, views, maps, *, antialiased: bool = False, use_ma
                     labels = torch.where(on, labels, torch.full_like(labels, IGNORE_LABEL))
                 else:
                     fmap = torch.where(on.unsqueeze(2), fmap, torch.zeros_like(fmap))
-            _, aux, u = R._forward_impl(cam, (w, h), means, log_scales, norm_rot, sh, raw_opac, False, None,
-                                        expect_backward=False, antialiased=antialiased)
+            _, aux, u = R.forward_frozen(parts, cam, (w, h), antialiased)
             feature_sums_from_aux(u, aux, labels if fmap is None else fmap, sums)
             feature_sums_from_aux(u, aux, ones, weight)
     if sums is None:

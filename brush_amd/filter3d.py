@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .render import view_parts
 
 VIEW_WORDS = C.sizeof(_lib.BrushFilterView) // 4  # 24: one record as float32 words
 MIN_RAW_OPACITY = -87.33654  # BRUSH_FILTER3D_MIN_RAW_OPACITY: the floor of the effective raw opacity
@@ -29,13 +30,6 @@ def view_chunk() -> int:
     return int(_lib.lib().brush_filter3d_view_chunk())
 
 
-def _camera_and_size(view):
-    if hasattr(view, "camera") and hasattr(view, "image"):
-        return view.camera, (int(view.image.shape[1]), int(view.image.shape[0]))
-    cam, (w, h) = view
-    return cam, (int(w), int(h))
-
-
 def view_records(views: Sequence) -> np.ndarray:
     """The views as brush_filter3d_rates reads them: a float32 [V, 24] host array (BrushFilterView per row; the two
     sizes are uint32 words).  `views`: SceneViews (camera and image size) or (Camera, (w, h)) pairs; sizes and
@@ -43,7 +37,7 @@ def view_records(views: Sequence) -> np.ndarray:
     rec = np.zeros((len(views), VIEW_WORDS), dtype=np.float32)
     words = rec.view(np.uint32)
     for i, view in enumerate(views):
-        cam, (w, h) = _camera_and_size(view)
+        cam, (w, h) = view_parts(view)[:2]
         if w < 1 or h < 1:
             raise ValueError(f"view {i}: the image size must be positive, got {(w, h)}")
         rec[i, :16] = np.asarray(cam.world_to_local(), dtype=np.float32).T.reshape(16)

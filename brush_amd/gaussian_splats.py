@@ -157,6 +157,14 @@ class Splats(torch.nn.Module):
         rot = self.rotation
         return rot / torch.sqrt(torch.sum(rot * rot, dim=1, keepdim=True))
 
+    @torch.no_grad()
+    def frozen(self):
+        """The splats as a view pass over many views feeds them, after one sync(): detached contiguous (means,
+        log_scales, rotation / |rotation|, sh_coeffs, raw_opacity), render._forward_impl's order."""
+        norm_rot = self._synced_norm_rotation()
+        return tuple(t.detach().contiguous() for t in (self.means, self.log_scales, norm_rot, self.sh_coeffs,
+                                                       self.raw_opacity))
+
     def render(self, camera: Camera, img_size, render_u32_buffer: bool = False, max_intersects=None,
                antialiased: bool = False):
         """gaussian_splats.rs:167-188; `antialiased`: render.render_splats."""

@@ -283,20 +283,9 @@ def render_normals(camera, img_size, means, log_scales, quats, sh_coeffs, raw_op
     from .features import _FeatureImageFn
 
     R._check_inputs(means, None, log_scales, quats, sh_coeffs, raw_opacity)
-    tracked = torch.is_grad_enabled() and any(
-        t.requires_grad for t in (means, log_scales, quats, sh_coeffs, raw_opacity))
-    if not tracked:
-        with torch.no_grad():
-            bufs = R._depth_buffers(means.shape[0], img_size, means.device)
-            img, aux, u = R._forward_impl(camera, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, False,
-                                          max_intersects, expect_backward=False, depth=bufs, antialiased=antialiased)
-            depth = bufs[0]
-    else:
-        xy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
-        holder = {"cam": camera, "img_size": img_size, "max_intersects": max_intersects, "deterministic": None,
-                  "antialiased": bool(antialiased)}
-        img, depth = R._RenderSplatsDepthFn.apply(means, xy, log_scales, quats, sh_coeffs, raw_opacity, holder)
-        aux, u = holder["aux"], holder["uniforms"]
+    (img, depth), holder = R._render_op(camera, img_size, means, None, log_scales, quats, sh_coeffs, raw_opacity,
+                                        max_intersects=max_intersects, antialiased=antialiased, depth=True)
+    aux, u = holder["aux"], holder["uniforms"]
     normals = splat_normals(u, means, log_scales, quats)
     if means.shape[0] == 0:
         h, w = int(u.img_size[1]), int(u.img_size[0])

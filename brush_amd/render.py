@@ -275,11 +275,16 @@ def grad_block_layout(n: int, ncoef: int):
 def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, ncoef, out_img, v_out,
                    block: Optional[torch.Tensor] = None,
                    depth: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                   pose: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
-    """depth: (compact_depth [N], v_depth [h,w]) of a depth render: brush_render_backward_depth.
+                   pose: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, distortion=None):
+    """The one call site of the dense render backward: (dict of the six dense gradients, their block).
+    depth: (compact_depth [N], v_depth [h,w]) of a depth render: brush_render_backward_depth.
     pose: (v_viewmat [12] f32, workspace) device buffers (pose_buffers): brush_render_backward_pose, with or without
-    `depth`; v_viewmat stays on the device, nothing here synchronises."""
-    l = _lib.lib()
+    `depth`; v_viewmat stays on the device, nothing here synchronises.
+    distortion: (cfg, stats, v_distortion [h,w]) of distortion.distortion_from_aux on the same depth forward:
+    brush_render_backward_distortion (needs `depth`, excludes `pose`; distortion.backward_distortion holds the term's own
+    refusals)."""
+    if distortion is not None and (depth is None or pose is not None):
+        raise ValueError("the distortion term needs depth=(compact_depth, v_depth) and has no pose form")
     n = means.shape[0]
     dev = means.device
     w, h = int(u.img_size[0]), int(u.img_size[1])
@@ -300,59 +305,122 @@ def _backward_impl(u, aux: RenderAux, means, log_scales, quats, raw_opacity, nco
                              aux.workspace_flags)
     v_out = v_out.contiguous()
     ws, s = aux.backward_workspace(nbytes, dev)
+    # common head, [depth pair], [distortion triple], six gradients, workspace, [pose triple], stream: the terms that
+    # are present select the entry
+    entry = "brush_render_backward"
+    args = [C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(), quats.data_ptr(), raw_opacity.data_ptr(),
+            n, out_img.data_ptr(), v_out.data_ptr()]
+    if depth is not None:
+        v_depth = depth[1].contiguous()
+        args += [depth[0].data_ptr(), v_depth.data_ptr()]
+        entry = "brush_render_backward_depth"
+    elif pose is not None:
+        args += [None, None]
+    if distortion is not None:
+        v_distortion = distortion[2].contiguous()
+        args += [C.byref(distortion[0]), distortion[1].data_ptr(), v_distortion.data_ptr()]
+        entry = "brush_render_backward_distortion"
+    args += [g["v_means"].data_ptr(), g["v_xy"].data_ptr(), g["v_scales"].data_ptr(), g["v_quats"].data_ptr(),
+             g["v_sh"].data_ptr(), g["v_opac"].data_ptr(), ws.data_ptr(), nbytes]
+    if pose is not None:
+        args += [pose[0].data_ptr(), pose[1].data_ptr(), pose[1].numel()]
+        entry = "brush_render_backward_pose"
     with torch.cuda.device(dev):
-        stream = _lib.current_stream()
-        if pose is not None:
-            compact_depth, v_depth = (None, None) if depth is None else (depth[0], depth[1].contiguous())
-            _lib.check(l.brush_render_backward_pose(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
-                                                    quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
-                                                    v_out.data_ptr(),
-                                                    None if depth is None else compact_depth.data_ptr(),
-                                                    None if depth is None else v_depth.data_ptr(),
-                                                    g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
-                                                    g["v_scales"].data_ptr(), g["v_quats"].data_ptr(),
-                                                    g["v_sh"].data_ptr(), g["v_opac"].data_ptr(), ws.data_ptr(),
-                                                    nbytes, pose[0].data_ptr(), pose[1].data_ptr(),
-                                                    pose[1].numel(), stream), "brush_render_backward_pose")
-        elif depth is not None:
-            compact_depth, v_depth = depth[0], depth[1].contiguous()
-            _lib.check(l.brush_render_backward_depth(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
-                                                     quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
-                                                     v_out.data_ptr(), compact_depth.data_ptr(), v_depth.data_ptr(),
-                                                     g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
-                                                     g["v_scales"].data_ptr(), g["v_quats"].data_ptr(),
-                                                     g["v_sh"].data_ptr(), g["v_opac"].data_ptr(), ws.data_ptr(),
-                                                     nbytes, stream), "brush_render_backward_depth")
-        else:
-            _lib.check(l.brush_render_backward(C.byref(u), C.byref(s), means.data_ptr(), log_scales.data_ptr(),
-                                               quats.data_ptr(), raw_opacity.data_ptr(), n, out_img.data_ptr(),
-                                               v_out.data_ptr(), g["v_means"].data_ptr(), g["v_xy"].data_ptr(),
-                                               g["v_scales"].data_ptr(), g["v_quats"].data_ptr(), g["v_sh"].data_ptr(),
-                                               g["v_opac"].data_ptr(), ws.data_ptr(), nbytes, stream),
-                       "brush_render_backward")
+        _lib.check(getattr(_lib.lib(), entry)(*args, _lib.current_stream()), entry)
     return g, block
 
 
+def _depth_buffers(n: int, img_size, device):
+    w, h = int(img_size[0]), int(img_size[1])
+    return _empty((h, w), torch.float32, device), _empty((max(n, 1),), torch.float32, device)
+
+
+def pose_buffers(n: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(v_viewmat [12] f32, scratch of brush_pose_grad_workspace_size(n) bytes) for one pose backward."""
+    nbytes = _lib.size_query("brush_pose_grad_workspace_size", int(n))
+    return (_empty((12,), torch.float32, device),
+            _empty((max(nbytes, 8) // 8,), torch.float64, device).view(torch.uint8))
+
+
+def _forward_outputs(holder, means, log_scales, quats, sh_coeffs, raw_opacity, viewmat, tracked: bool):
+    """The forward of every render op, tracked or not: ([img, depth?, distortion?], [compact_depth?, stats?]).  Leaves
+    holder["aux"] and holder["uniforms"] (for replays of this forward, normal_loss.py) and, with a distortion config,
+    holder["stats"]."""
+    cfg = holder["distortion"]
+    depth = _depth_buffers(means.shape[0], holder["img_size"], means.device) if holder["depth"] or cfg is not None \
+        else None
+    out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs, raw_opacity,
+                                holder["render_u32"], holder["max_intersects"], deterministic=holder["deterministic"],
+                                expect_backward=None if tracked else False, depth=depth,
+                                antialiased=holder["antialiased"],
+                                viewmat=None if viewmat is None else viewmat.detach().numpy())
+    holder["aux"], holder["uniforms"] = aux, u
+    outs, kept = [out], []
+    if depth is not None:
+        outs.append(depth[0])
+        kept.append(depth[1])
+    if cfg is not None:
+        from .distortion import distortion_from_aux
+
+        holder["stats"] = stats = distortion_from_aux(u, aux, depth[1], cfg)
+        outs.append(stats[..., 0].clone())
+        kept.append(stats)
+    return outs, kept
+
+
 class _RenderSplatsFn(torch.autograd.Function):
-    """Parents in the order of render.rs:420-427: means, xy_dummy, log_scales, quats, sh, raw_opacity."""
+    """The one render op.  Parents in the order of render.rs:420-427: means, xy_dummy, log_scales, quats, sh,
+    raw_opacity, then the world-to-camera matrix (a CPU tensor) of the pose op; a parent that is None receives None.
+    Outputs: img, then the accumulated depth (holder["depth"], or a distortion config), then the distortion map
+    (holder["distortion"]: a BrushDistortion)."""
 
     @staticmethod
-    def forward(ctx, means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder):
-        out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
-                                    raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
-                                    antialiased=holder["antialiased"])
-        holder["aux"] = aux
-        ctx.u, ctx.aux, ctx.ncoef = u, aux, sh_coeffs.shape[1]
-        ctx.save_for_backward(means, log_scales, quats, raw_opacity, out)
-        ctx.mark_non_differentiable()
-        return out
+    def forward(ctx, means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat, holder):
+        outs, kept = _forward_outputs(holder, means, log_scales, quats, sh_coeffs, raw_opacity, viewmat, True)
+        ctx.u, ctx.aux, ctx.ncoef, ctx.cfg = holder["uniforms"], holder["aux"], sh_coeffs.shape[1], holder["distortion"]
+        ctx.has_xy, ctx.has_pose = xy_dummy is not None, viewmat is not None
+        ctx.save_for_backward(means, log_scales, quats, raw_opacity, outs[0], *kept)
+        return outs[0] if len(outs) == 1 else tuple(outs)
 
     @staticmethod
-    def backward(ctx, v_output):
-        means, log_scales, quats, raw_opacity, out = ctx.saved_tensors
-        g, _ = _backward_impl(ctx.u, ctx.aux, means, log_scales, quats, raw_opacity, ctx.ncoef, out,
-                              v_output.to(torch.float32))
-        return g["v_means"], g["v_xy"], g["v_scales"], g["v_quats"], g["v_sh"], g["v_opac"], None
+    def backward(ctx, v_output, v_depth=None, v_dist=None):
+        means, log_scales, quats, raw_opacity, out, *kept = ctx.saved_tensors
+
+        def on_map(v):  # a zero (or absent) gradient on an output is passed as zeros
+            return torch.zeros(out.shape[:2], dtype=torch.float32, device=out.device) if v is None \
+                else v.to(torch.float32)
+
+        v_output = torch.zeros_like(out) if v_output is None else v_output.to(torch.float32)
+        depth = (kept[0], on_map(v_depth)) if kept else None
+        distortion = None if ctx.cfg is None else (ctx.cfg, kept[1], on_map(v_dist))
+        pose = pose_buffers(means.shape[0], means.device) if ctx.has_pose else None
+        g, _ = _backward_impl(ctx.u, ctx.aux, means, log_scales, quats, raw_opacity, ctx.ncoef, out, v_output,
+                              depth=depth, pose=pose, distortion=distortion)
+        v_viewmat = None
+        if pose is not None:
+            v_viewmat = torch.zeros((4, 4), dtype=torch.float32)
+            v_viewmat[:3] = pose[0].cpu().view(3, 4)  # 48 bytes: the op's one synchronisation
+        return (g["v_means"], g["v_xy"] if ctx.has_xy else None, g["v_scales"], g["v_quats"], g["v_sh"], g["v_opac"],
+                v_viewmat, None)
+
+
+def _render_op(cam, img_size, means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat=None, *,
+               max_intersects=None, deterministic=None, antialiased=False, depth=False, distortion=None,
+               render_u32=False):
+    """([img, depth?, distortion?], holder) of one render (the caller has checked its inputs): through _RenderSplatsFn
+    when autograd follows a parent, else the UnTracked branch (render.rs:453-460): plain forward, no state kept."""
+    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic,
+              "antialiased": bool(antialiased), "depth": bool(depth), "distortion": distortion,
+              "render_u32": bool(render_u32)}
+    tracked = torch.is_grad_enabled() and not render_u32 and any(
+        t is not None and t.requires_grad
+        for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat))
+    if not tracked:
+        with torch.no_grad():
+            outs, _ = _forward_outputs(holder, means, log_scales, quats, sh_coeffs, raw_opacity, viewmat, False)
+        return outs, holder
+    outs = _RenderSplatsFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat, holder)
+    return (list(outs) if isinstance(outs, tuple) else [outs]), holder
 
 
 def render_splats(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Optional[torch.Tensor],
@@ -374,52 +442,10 @@ def render_splats(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Opt
     (the cull's screen-bounds prefilter bounds the covariance without reading the quaternion, csrc/project.hip).
     """
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
-    tracked = torch.is_grad_enabled() and not render_u32_buffer and any(
-        t is not None and t.requires_grad for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity))
-    if not tracked:
-        # UnTracked branch (render.rs:453-460): plain forward, no state kept.
-        with torch.no_grad():
-            out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity,
-                                        render_u32_buffer, max_intersects, deterministic=deterministic,
-                                        expect_backward=False, antialiased=antialiased)
-        return out, aux
-    if xy_grad_dummy is None:
-        xy_grad_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
-    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic,
-              "antialiased": bool(antialiased)}
-    out = _RenderSplatsFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder)
+    (out,), holder = _render_op(cam, img_size, means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity,
+                                max_intersects=max_intersects, deterministic=deterministic, antialiased=antialiased,
+                                render_u32=render_u32_buffer)
     return out, holder["aux"]
-
-
-def _depth_buffers(n: int, img_size, device):
-    w, h = int(img_size[0]), int(img_size[1])
-    return _empty((h, w), torch.float32, device), _empty((max(n, 1),), torch.float32, device)
-
-
-class _RenderSplatsDepthFn(torch.autograd.Function):
-    """render_splats with the accumulated depth as a second output; same six parents."""
-
-    @staticmethod
-    def forward(ctx, means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder):
-        depth = _depth_buffers(means.shape[0], holder["img_size"], means.device)
-        out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
-                                    raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
-                                    depth=depth, antialiased=holder["antialiased"])
-        holder["aux"], holder["uniforms"] = aux, u  # (the uniforms: for replays of this forward, normal_loss.py)
-        ctx.u, ctx.aux, ctx.ncoef = u, aux, sh_coeffs.shape[1]
-        ctx.save_for_backward(means, log_scales, quats, raw_opacity, out, depth[1])
-        return out, depth[0]
-
-    @staticmethod
-    def backward(ctx, v_output, v_depth):
-        means, log_scales, quats, raw_opacity, out, compact_depth = ctx.saved_tensors
-        # a zero (or absent) gradient on one output is passed as zeros
-        v_output = torch.zeros_like(out) if v_output is None else v_output.to(torch.float32)
-        v_depth = torch.zeros(out.shape[:2], dtype=torch.float32, device=out.device) if v_depth is None \
-            else v_depth.to(torch.float32)
-        g, _ = _backward_impl(ctx.u, ctx.aux, means, log_scales, quats, raw_opacity, ctx.ncoef, out, v_output,
-                              depth=(compact_depth, v_depth))
-        return g["v_means"], g["v_xy"], g["v_scales"], g["v_quats"], g["v_sh"], g["v_opac"], None
 
 
 def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Optional[torch.Tensor],
@@ -435,28 +461,10 @@ def render_splats_depth(cam: Camera, img_size, means: torch.Tensor, xy_grad_dumm
     Quaternion contract (unit `quats`; the reference's results for |q| <= 1.1): as render_splats.
     """
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
-    tracked = torch.is_grad_enabled() and any(
-        t is not None and t.requires_grad for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity))
-    if not tracked:
-        with torch.no_grad():
-            depth = _depth_buffers(means.shape[0], img_size, means.device)
-            out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, False,
-                                        max_intersects, deterministic=deterministic, expect_backward=False,
-                                        depth=depth, antialiased=antialiased)
-        return out, depth[0], aux
-    if xy_grad_dummy is None:
-        xy_grad_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
-    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic,
-              "antialiased": bool(antialiased)}
-    out, depth = _RenderSplatsDepthFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, holder)
+    (out, depth), holder = _render_op(cam, img_size, means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity,
+                                      max_intersects=max_intersects, deterministic=deterministic,
+                                      antialiased=antialiased, depth=True)
     return out, depth, holder["aux"]
-
-
-def pose_buffers(n: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(v_viewmat [12] f32, scratch of brush_pose_grad_workspace_size(n) bytes) for one pose backward."""
-    nbytes = _lib.size_query("brush_pose_grad_workspace_size", int(n))
-    return (_empty((12,), torch.float32, device),
-            _empty((max(nbytes, 8) // 8,), torch.float64, device).view(torch.uint8))
 
 
 def _check_viewmat(viewmat) -> torch.Tensor:
@@ -468,43 +476,6 @@ def _check_viewmat(viewmat) -> torch.Tensor:
     if viewmat.shape != (4, 4) or viewmat.dtype != torch.float32:
         raise ValueError(f"viewmat must be float32 [4,4], got {viewmat.dtype} {tuple(viewmat.shape)}")
     return viewmat
-
-
-class _RenderSplatsPoseFn(torch.autograd.Function):
-    """render_splats / render_splats_depth with the world-to-camera matrix as a seventh parent (a CPU tensor)."""
-
-    @staticmethod
-    def forward(ctx, means, xy_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat, holder):
-        depth = _depth_buffers(means.shape[0], holder["img_size"], means.device) if holder["depth"] else None
-        out, aux, u = _forward_impl(holder["cam"], holder["img_size"], means, log_scales, quats, sh_coeffs,
-                                    raw_opacity, False, holder["max_intersects"], deterministic=holder["deterministic"],
-                                    depth=depth, antialiased=holder["antialiased"],
-                                    viewmat=viewmat.detach().numpy())
-        holder["aux"] = aux
-        ctx.u, ctx.aux, ctx.ncoef, ctx.has_depth = u, aux, sh_coeffs.shape[1], depth is not None
-        if depth is not None:
-            ctx.save_for_backward(means, log_scales, quats, raw_opacity, out, depth[1])
-            return out, depth[0]
-        ctx.save_for_backward(means, log_scales, quats, raw_opacity, out)
-        return out
-
-    @staticmethod
-    def backward(ctx, v_output, v_depth=None):
-        if ctx.has_depth:
-            means, log_scales, quats, raw_opacity, out, compact_depth = ctx.saved_tensors
-            v_output = torch.zeros_like(out) if v_output is None else v_output.to(torch.float32)
-            v_depth = torch.zeros(out.shape[:2], dtype=torch.float32, device=out.device) if v_depth is None \
-                else v_depth.to(torch.float32)
-            depth = (compact_depth, v_depth)
-        else:
-            means, log_scales, quats, raw_opacity, out = ctx.saved_tensors
-            v_output, depth = v_output.to(torch.float32), None
-        pose = pose_buffers(means.shape[0], means.device)
-        g, _ = _backward_impl(ctx.u, ctx.aux, means, log_scales, quats, raw_opacity, ctx.ncoef, out, v_output,
-                              depth=depth, pose=pose)
-        v_viewmat = torch.zeros((4, 4), dtype=torch.float32)
-        v_viewmat[:3] = pose[0].cpu().view(3, 4)  # 48 bytes: the op's one synchronisation
-        return g["v_means"], g["v_xy"], g["v_scales"], g["v_quats"], g["v_sh"], g["v_opac"], v_viewmat, None
 
 
 def render_splats_pose(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy: Optional[torch.Tensor],
@@ -525,25 +496,60 @@ def render_splats_pose(cam: Camera, img_size, means: torch.Tensor, xy_grad_dummy
     Quaternion contract (unit `quats`; the reference's results for |q| <= 1.1): as render_splats.
     """
     _check_inputs(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity)
-    viewmat = _check_viewmat(viewmat)
-    tracked = torch.is_grad_enabled() and any(
-        t is not None and t.requires_grad
-        for t in (means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat))
-    if not tracked:
-        with torch.no_grad():
-            bufs = _depth_buffers(means.shape[0], img_size, means.device) if depth else None
-            out, aux, _ = _forward_impl(cam, img_size, means, log_scales, quats, sh_coeffs, raw_opacity, False,
-                                        max_intersects, deterministic=deterministic, expect_backward=False,
-                                        depth=bufs, antialiased=antialiased, viewmat=viewmat.numpy())
-        return (out, bufs[0], aux) if depth else (out, aux)
-    if xy_grad_dummy is None:
-        xy_grad_dummy = torch.zeros((means.shape[0], 2), dtype=torch.float32, device=means.device)
-    holder = {"cam": cam, "img_size": img_size, "max_intersects": max_intersects, "deterministic": deterministic,
-              "antialiased": bool(antialiased), "depth": bool(depth)}
-    res = _RenderSplatsPoseFn.apply(means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity, viewmat, holder)
-    if depth:
-        return res[0], res[1], holder["aux"]
-    return res, holder["aux"]
+    outs, holder = _render_op(cam, img_size, means, xy_grad_dummy, log_scales, quats, sh_coeffs, raw_opacity,
+                              _check_viewmat(viewmat), max_intersects=max_intersects, deterministic=deterministic,
+                              antialiased=antialiased, depth=depth)
+    return (*outs, holder["aux"])
+
+
+# ---- the frozen-splat view pass of contribution.py, error_score.py and features.py ------------------------------------
+def forward_frozen(parts, cam: Camera, size, antialiased: bool = False):
+    """One forward of Splats.frozen()'s `parts` with no backward to come: (img, aux, uniforms) as _forward_impl."""
+    return _forward_impl(cam, size, *parts, False, None, expect_backward=False, antialiased=antialiased)
+
+
+def view_parts(view, dev=None, *, downscale: int = 1, gt: bool = False, mask: bool = False):
+    """One view taken apart: (camera, (w, h), gt, mask).  A (Camera, (w, h)) pair: that size, at
+    pyramid.downscaled_size with downscale > 1.  A (Camera, gt, mask or None) triple of device tensors is taken as it is
+    (its size is gt's).  A dataset.SceneView: its image's size (downscaled likewise); with `gt` the image is uploaded
+    to `dev` (and checked: uint8 [h,w,3|4], the mask against it), with `mask` its mask, and with downscale > 1 both are
+    resized as the training loader resizes them.  What is not asked for comes back as None."""
+    from .pyramid import area_resize, downscaled_size, nearest_resize
+
+    if isinstance(view, (tuple, list)):
+        if len(view) == 3:
+            cam, g, m = view
+            size = None if g is None else (int(g.shape[1]), int(g.shape[0]))  # (features.py takes gt = None)
+            return cam, size, (g if gt else None), (m if mask else None)
+        cam, (w, h) = view
+        w, h = int(w), int(h)
+        return cam, (downscaled_size(w, h, downscale) if downscale > 1 else (w, h)), None, None
+    img, g = view.image, None
+    if gt:
+        img = np.require(img, requirements=["C"])
+        if img.ndim != 3 or img.dtype != np.uint8 or img.shape[2] not in (3, 4):
+            raise ValueError(f"{view.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
+        g = torch.from_numpy(np.array(img, copy=True)).to(dev)
+    h, w = (int(x) for x in img.shape[:2])
+    m = getattr(view, "mask", None) if mask else None
+    if m is not None:
+        if gt and (m.dtype != np.uint8 or tuple(m.shape) != (h, w)):
+            raise ValueError(f"{view.name}: the view's mask must be uint8 [h,w] = {(h, w)}, got {m.dtype} {m.shape}")
+        m = torch.from_numpy(np.array(m, copy=True, order="C")).to(dev)
+    if downscale > 1:
+        g = None if g is None else area_resize(g, factor=downscale)
+        if m is not None:
+            m = nearest_resize(m.to(torch.int16).view(torch.uint16), factor=downscale).view(torch.int16).to(torch.uint8)
+        w, h = downscaled_size(w, h, downscale)
+    return view.camera, (w, h), g, m
+
+
+def check_tensor(t, dtype, shape, what: str, dev):
+    """ValueError unless `t` is a contiguous `dtype` tensor of `shape` on `dev`."""
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
+            or t.device != dev):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else repr(t)
+        raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got {got}")
 
 
 def rgba8_row_pitch(width: int) -> int:

@@ -833,13 +833,8 @@ class SplatTrainer:
         u, aux, pred, v_pred = fwd
         n, ncoef, l = means.shape[0], int(sh.shape[1]), _lib.lib()
         eff_scales, eff_opac = effective
-        if distortion_grad is not None:
-            from .distortion import backward_distortion
-            grads, block = backward_distortion(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
-                                               depth_grad[0], depth_grad[1], *distortion_grad)
-        else:
-            grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
-                                            depth=depth_grad, pose=pose)
+        grads, block = R._backward_impl(u, aux, means, eff_scales, norm_rot, eff_opac, ncoef, pred, v_pred,
+                                        depth=depth_grad, pose=pose, distortion=distortion_grad)
         if normal_grad is not None:  # the rendered normal map's gradient -> the quaternions the forward was fed
             from .normal_loss import splat_normals_backward_into
             splat_normals_backward_into(u, means, log_scales, norm_rot, normal_grad, grads["v_quats"])

@@ -221,7 +221,7 @@ class TsdfVolume:
         `depth`: "expected" (the default) fuses D / alpha; "median" fuses the median depth at `level`
         (Splats.render_median_depth: the z of the splat at which the accumulated opacity first reaches `level`), which
         does not blend a silhouette's foreground with what lies behind it."""
-        from .filter3d import _camera_and_size
+        from .render import view_parts
         from .median_depth import check_level
 
         if depth not in ("expected", "median"):
@@ -236,7 +236,7 @@ class TsdfVolume:
                 chunk = views[base:base + k]
                 imgs, depths, masks = [], [], []
                 for v in chunk:
-                    cam, size = _camera_and_size(v)
+                    cam, size = view_parts(v)[:2]
                     if depth == "median":
                         img, _, dmap, _, _ = splats.render_median_depth(cam, size, level=level, antialiased=antialiased)
                     else:

@@ -10,6 +10,11 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
   se3_exp / apply_delta / PoseTable  <- camera-frame twists and the per-view pose optimiser (brush_amd/pose.py)
   apply_exposure / ExposureTable     <- per-view affine colour maps (exposure compensation) and their device-side
                                 optimiser (brush_amd/exposure.py; build extension, 3DGS's exposure compensation)
+  apply_bilagrid / bilagrid_identity / bilagrid_tv / BilagridTable  <- per-view bilateral grids: a lattice of affine
+                                colour maps indexed by pixel position and luminance, sliced through the render before
+                                the loss, the total-variation prior and the device-side optimiser (brush_amd/bilagrid.py;
+                                build extension, gsplat's use_bilateral_grid is the model; TrainConfig.bilagrid_opt,
+                                `python -m brush_amd.train_loop --bilagrid-opt`)
   Camera                     <- camera.rs
   Splats                     <- gaussian_splats.rs (render, from_safetensors / from_ply, from_point_cloud,
                                 from_random_config)
@@ -108,6 +113,7 @@ _TRAIN_LOOP_NAMES = ("train_scene", "TrainLog", "TrainLoop")
 # brush_amd.pose is imported on first use too: a run without pose refinement never loads it.
 _POSE_NAMES = ("se3_exp", "apply_delta", "PoseTable")
 _EXPOSURE_NAMES = ("apply_exposure", "ExposureTable")
+_BILAGRID_NAMES = ("apply_bilagrid", "bilagrid_identity", "bilagrid_tv", "BilagridTable")
 _CONTRIBUTION_NAMES = ("Contributions", "ContributionBuffers", "contributions_from_aux", "splat_contributions",
                        "prune_mask")
 _ERROR_SCORE_NAMES = ("ErrorScores", "ErrorScoreBuffers", "l1_error_map", "error_scores_from_aux", "splat_error_scores")
@@ -132,6 +138,9 @@ def __getattr__(name):
     if name in _EXPOSURE_NAMES:
         from . import exposure as _exposure
         return getattr(_exposure, name)
+    if name in _BILAGRID_NAMES:
+        from . import bilagrid as _bilagrid
+        return getattr(_bilagrid, name)
     if name in _CONTRIBUTION_NAMES:
         from . import contribution as _contribution
         return getattr(_contribution, name)

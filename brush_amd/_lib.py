@@ -100,6 +100,14 @@ class BrushExposureAdam(C.Structure):
     ]
 
 
+class BrushBilagridAdam(C.Structure):
+    """Hyper-parameters of brush_bilagrid_backward_adam (include/brush_hip.h: BrushBilagridAdam)."""
+    _fields_ = [
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("tv", C.c_float),
+        ("time", C.c_uint32),
+    ]
+
+
 class BrushDepthLoss(C.Structure):
     """Per-call configuration of brush_depth_loss (include/brush_hip.h: BrushDepthLoss)."""
     _fields_ = [
@@ -234,6 +242,15 @@ _SYMBOLS = [
     ("brush_exposure_backward", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
     ("brush_exposure_backward_adam", C.c_int,
      [_P, _P, C.POINTER(BrushExposureAdam), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_bilagrid_workspace_size", C.c_int,
+     [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("brush_bilagrid_forward", C.c_int,
+     [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
+    ("brush_bilagrid_backward", C.c_int,
+     [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_bilagrid_backward_adam", C.c_int,
+     [_P, _P, C.POINTER(BrushBilagridAdam), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P,
+      _P, _P, C.c_size_t, _P]),
     ("brush_compose_forward", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     ("brush_compose_backward", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     ("brush_depth_loss_workspace_size", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),

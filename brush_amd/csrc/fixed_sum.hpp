@@ -9,7 +9,7 @@
 //   across the waves : lane 0 of each wave puts its sum into LDS; behind a __syncthreads() the four are added
 //         sum_waves_in_order  ((r0 + r1) + r2) + r3 : k_view_grad, k_view_grad_finalize (pose_grad.hip),
 //             k_exposure_backward, k_exposure_finalize (exposure.hip), k_depth_loss, k_depth_loss_finalize
-//             (depth_loss.hip); block_sum_words is this order
+//             (depth_loss.hip), k_bilagrid_backward (bilagrid.hip, 48 words); block_sum_words is this order
 //         sum_waves_pairwise  (r0 + r1) + (r2 + r3) : k_eval_finalize (eval.hip), block_sum of k_l1_backward
 //             (train_step.hip)
 //       Neither is better.  Each kernel keeps the order it was written with, because its output is held to the bit;

@@ -79,6 +79,20 @@ class TrainConfig:
     lr_exposure: float = 1e-2
     lr_exposure_decay: float = 0.1
     exposure_reg: float = 1e-6
+    # Build extension: per-view bilateral grids (brush_amd/bilagrid.py; gsplat's use_bilateral_grid and Wang et al.,
+    # "Bilateral Guided Radiance Field Processing", are the models).  Each training view carries a lattice of
+    # bilagrid_shape = (GW, GH, GL) affine colour maps, read at (x, y, the pixel's luminance), sliced through the render
+    # before the loss and stepped by Adam on the device: what an exposure map cannot express (vignetting, local tone
+    # mapping, brightness-dependent colour).  lr_bilagrid decays by the total factor lr_bilagrid_decay over
+    # `total_steps` (formed like the exposure rate); bilagrid_tv weighs the total-variation prior that keeps a grid
+    # smooth (added to the grid's gradient, not to the reported loss).  2e-3, 0.01 and 10.0 are gsplat's values:
+    # hyper-parameter defaults, not measured here.  Not with exposure_opt (a constant grid is the affine map: one colour
+    # model per view), densify_by="error" or a multi-rank exchange.  Eval views are rendered as given.  DESIGN §8 row 24.
+    bilagrid_opt: bool = False
+    bilagrid_shape: Tuple[int, int, int] = (16, 16, 8)
+    lr_bilagrid: float = 2e-3
+    lr_bilagrid_decay: float = 0.01
+    bilagrid_tv: float = 10.0
     # Build extension: how the splat count evolves.  "default": refine_splats (clone / split / prune / opacity reset, the
     # reference's train.rs:395-579).  "mcmc": a fixed budget (brush_amd/mcmc.py; Kheradmand et al. 2024, gsplat's
     # MCMCStrategy): dead splats (opacity <= mcmc_min_opacity) are relocated onto live ones, the count grows by
@@ -224,6 +238,7 @@ class TrainConfig:
             raise ValueError("TrainConfig.filter3d cannot be combined with a multi-rank exchange: the 3D filter is "
                              "single-GPU")
         check_background(self.background)
+        self.check_bilagrid(multi_rank)
         self.check_densify()
         if self.densify_by == "error":
             # what the score pass cannot serve, in the order it is refused in
@@ -232,9 +247,30 @@ class TrainConfig:
                              (multi_rank, "a multi-rank exchange: the score pass is single-GPU"),
                              (self.pose_opt, "pose_opt: the score pass would have to render through the refined poses"),
                              (self.exposure_opt, "exposure_opt: the score pass would have to render through the "
-                                                 "refined exposure maps")):
+                                                 "refined exposure maps"),
+                             (self.bilagrid_opt, "bilagrid_opt: the score pass would have to render through the "
+                                                 "refined bilateral grids")):
                 if on:
                     raise ValueError(f"TrainConfig.densify_by='error' cannot be combined with {what}")
+
+    def check_bilagrid(self, multi_rank: bool = False):
+        """A ValueError naming what is wrong with the bilateral-grid fields."""
+        from .bilagrid import check_shape
+
+        try:
+            check_shape(self.bilagrid_shape)
+        except ValueError as e:
+            raise ValueError(f"TrainConfig.bilagrid_shape: {e}") from None
+        for name in ("lr_bilagrid", "lr_bilagrid_decay", "bilagrid_tv"):
+            x = getattr(self, name)
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not (math.isfinite(x) and x >= 0.0):
+                raise ValueError(f"TrainConfig.{name} must be finite and >= 0, got {x!r}")
+        if self.bilagrid_opt and self.exposure_opt:
+            raise ValueError("TrainConfig.bilagrid_opt cannot be combined with exposure_opt: a constant grid is the "
+                             "affine map, so one colour model per view")
+        if self.bilagrid_opt and multi_rank:
+            raise ValueError("TrainConfig.bilagrid_opt cannot be combined with a multi-rank exchange: the grids are "
+                             "single-GPU")
 
     def check_normal(self):
         """A ValueError naming what is wrong with the normal-consistency fields."""
@@ -711,6 +747,9 @@ class SplatTrainer:
     def _lr_exposure(self) -> float:
         return self._decayed(self.config.lr_exposure, self.config.lr_exposure_decay)
 
+    def _lr_bilagrid(self) -> float:
+        return self._decayed(self.config.lr_bilagrid, self.config.lr_bilagrid_decay)
+
     def _depth_weight(self) -> float:
         c = self.config
         if c.depth_weight_final is None or c.depth_weight <= 0.0 or c.depth_weight_final <= 0.0:
@@ -726,7 +765,7 @@ class SplatTrainer:
         distortion_from_step)."""
         return self.config.distortion_weight > 0.0 and self.iter >= self.config.distortion_from_step
 
-    def _check_step(self, grad_sync, exchange, view_index, poses, exposures, gt_depth):
+    def _check_step(self, grad_sync, exchange, view_index, poses, exposures, gt_depth, bilagrids=None):
         """Refuses the combinations of step's arguments and the configuration that no path serves, before anything is
         touched (neither the trainer's state nor the splats are looked at)."""
         c = self.config
@@ -741,9 +780,13 @@ class SplatTrainer:
                              (self._distortion_active(), "the distortion term (TrainConfig.distortion_weight)"),
                              (c.strategy == "mcmc", "the mcmc strategy"),
                              (poses is not None, "pose refinement"),
-                             (exposures is not None, "exposure compensation")):
+                             (exposures is not None, "exposure compensation"),
+                             (bilagrids is not None, "the bilateral grids")):
                 if on:
                     raise ValueError(f"{what} is single-view: it cannot be combined with exchange / grad_sync")
+        if bilagrids is not None and exposures is not None:
+            raise ValueError("bilagrids cannot be combined with exposures: a constant grid is the affine map, so one "
+                             "colour model per view")
         if self._distortion_active():
             # what the term's gradient replay cannot serve
             for on, what in ((poses is not None, "pose refinement (`poses`): the pose would get no gradient through "
@@ -757,10 +800,11 @@ class SplatTrainer:
             for on, what in ((c.strategy == "mcmc", "the mcmc strategy"),
                              (exchange is not None or grad_sync is not None, "exchange / grad_sync"),
                              (poses is not None, "pose refinement"),
-                             (exposures is not None, "exposure compensation")):
+                             (exposures is not None, "exposure compensation"),
+                             (bilagrids is not None, "the bilateral grids")):
                 if on:
                     raise ValueError(f"densify_by='error' cannot be combined with {what}")
-        for name, table in (("poses", poses), ("exposures", exposures)):
+        for name, table in (("poses", poses), ("exposures", exposures), ("bilagrids", bilagrids)):
             if table is not None and view_index is None:
                 raise ValueError(f"{name} needs view_index")
         if exchange is not None and grad_sync is not None:
@@ -768,15 +812,17 @@ class SplatTrainer:
         if c.antialiased and exchange is not None:
             raise ValueError("antialiased training has no data-parallel record path (brush_render_backward_records)")
 
-    def _loss(self, pred, gt_image, batch_views, loss_out, view_index, exposures, background, gt_mask):
-        """(loss [1], d loss / d pred at the raw render `pred`): exposure map, composition over the background and
-        under the mask, L1 / SSIM, and the same stages backwards, each only with its option."""
+    def _loss(self, pred, gt_image, batch_views, loss_out, view_index, exposures, background, gt_mask, bilagrids=None):
+        """(loss [1], d loss / d pred at the raw render `pred`): exposure map or bilateral grid, composition over the
+        background and under the mask, L1 / SSIM, and the same stages backwards, each only with its option."""
         from .compose import compose_backward, compose_forward
 
         c = self.config
         bg = None if background is None else self._background(background, pred.device)
         compose = bg is not None or gt_mask is not None
         seen = pred if exposures is None else exposures.forward(view_index, pred)
+        if bilagrids is not None:  # (never beside exposures: _check_step)
+            seen = bilagrids.forward(view_index, pred)
         target = gt_image
         if compose:
             seen, target = compose_forward(seen, gt_image, background=bg, mask=gt_mask)
@@ -785,6 +831,8 @@ class SplatTrainer:
             compose_backward(v_pred, background=bg, mask=gt_mask, out=v_pred)
         if exposures is not None:  # the loss saw the compensated image; the render backward takes the gradient at pred
             v_pred = exposures.backward_step(view_index, pred, v_pred, lr=self._lr_exposure())
+        if bilagrids is not None:
+            v_pred = bilagrids.backward_step(view_index, pred, v_pred, lr=self._lr_bilagrid())
         return loss, v_pred
 
     def _update_records(self, splats, exchange, cfg, size, params, norm_rot, fwd, want_stats):
@@ -873,7 +921,7 @@ class SplatTrainer:
              batch_views: int = 1, grad_sync: Optional[Callable] = None, exchange=None,
              loss_out: Optional[torch.Tensor] = None, view_index: Optional[int] = None, poses=None,
              exposures=None, gt_depth: Optional[torch.Tensor] = None, depth_scale: float = 1.0,
-             depth_offset: float = 0.0, background=None, gt_mask: Optional[torch.Tensor] = None):
+             depth_offset: float = 0.0, background=None, gt_mask: Optional[torch.Tensor] = None, bilagrids=None):
         """One reference training iteration on one view (batch size is 1 in the reference, train.rs:216-219).  Returns
         (loss [1] device tensor, the raw render, its aux).
         `gt_image`: [h,w,3|4] float32 (0..1) or uint8 (read as b / 255 by the loss kernels, the same bits as its float32
@@ -890,6 +938,12 @@ class SplatTrainer:
         `exposures` (a brush_amd.exposure.ExposureTable) with `view_index`: the view's affine colour map is applied to
         the render, the loss is taken on the result, and the table's backward returns the gradient at the raw render
         (which every backward path then receives beside the raw render) and steps the view's map, all on the device.
+        `bilagrids` (a brush_amd.bilagrid.BilagridTable) with `view_index`: the view's bilateral grid takes exactly the
+        place the exposure map takes: it is sliced through the raw render in front of the composition, the loss is taken
+        on the result, and behind brush_compose_backward the table's backward returns the gradient at the raw render
+        (through the colour map and through the luminance that indexes the grid) and steps the view's grid with the
+        total-variation prior, all on the device.  On every optimizer path; refused with `exposures` (one colour model
+        per view), `exchange` / `grad_sync` and densify_by = "error".
         `gt_depth` (the view's depth map, [h,w] uint16 or float32 on the device, read as raw * depth_scale +
         depth_offset; scene_loader keeps it there as stored) with a positive current TrainConfig.depth_weight: the view
         is rendered with its depth output, brush_depth_loss adds the depth term's alpha gradient into the colour loss's
@@ -909,9 +963,9 @@ class SplatTrainer:
         brush_adam_step on the raw parameters.
         TrainConfig.densify_by = "error": a refining step (will_refine) needs the scores of set_densify_scores for the
         current splats and is refused without them before anything is stepped; no step gathers the gradient statistics;
-        refused with strategy "mcmc", `exchange` / `grad_sync`, `poses` and `exposures`.
-        Single-view, that is refused with `exchange` / `grad_sync`: the 3D filter, `gt_depth`, strategy "mcmc", `poses`
-        and `exposures` (_check_step); TrainConfig.antialiased is refused with `exchange` alone.  The optimizer path
+        refused with strategy "mcmc", `exchange` / `grad_sync`, `poses`, `exposures` and `bilagrids`.
+        Single-view, that is refused with `exchange` / `grad_sync`: the 3D filter, `gt_depth`, strategy "mcmc", `poses`,
+        `exposures` and `bilagrids` (_check_step); TrainConfig.antialiased is refused with `exchange` alone.  The optimizer path
         (optimizer_path): the records path with `exchange`; the separate-call path (backward, then brush_adam_step)
         with `grad_sync`, strategy "mcmc", an active depth term or a 3D filter, whatever `fused_backward` says;
         otherwise the fused path (brush_render_backward_adam[_pose]) unless `fused_backward` is False.
@@ -932,7 +986,7 @@ class SplatTrainer:
         without them): the term's gradient goes through the blending weights and the depths into every geometric
         parameter.  Before distortion_from_step, or with weight 0, the step is the one without the option."""
         c = self.config
-        self._check_step(grad_sync, exchange, view_index, poses, exposures, gt_depth)
+        self._check_step(grad_sync, exchange, view_index, poses, exposures, gt_depth, bilagrids)
         use_mcmc = c.strategy == "mcmc"
         filt = self.filter3d
         depth_w = self._depth_weight() if gt_depth is not None else 0.0
@@ -981,7 +1035,8 @@ class SplatTrainer:
                                        lazy_sh=lazy, antialiased=c.antialiased, viewmat=viewmat, depth=depth_bufs)
         if exchange is not None:
             exchange.begin(aux)  # the per-view counts start travelling while the loss and the backward run
-        loss, v_pred = self._loss(pred, gt_image, batch_views, loss_out, view_index, exposures, background, gt_mask)
+        loss, v_pred = self._loss(pred, gt_image, batch_views, loss_out, view_index, exposures, background, gt_mask,
+                                  bilagrids)
         depth_grad = None
         if use_depth:  # on the raw render: alpha gradient into v_pred, the term into the step's loss, no read-back
             from .depth_loss import depth_loss_into

@@ -15,6 +15,7 @@ Command line (one line per eval and a last line; --json also writes the eval row
         [--eval-split-every K] [--eval-every N] [--eval-views V] [--init PLY] [--init-count 10000] [--sh-degree 3]
         [--seed 42] [--export OUT.ply] [--json LOG] [--antialiased] [--pose-opt] [--export-cameras CAMS.json]
         [--strategy default|mcmc] [--cap-max 1000000] [--exposure-opt] [--export-exposures EXP.json]
+        [--bilagrid-opt] [--bilagrid-shape 16,16,8] [--bilagrid-tv W] [--export-bilagrids GRIDS.npz]
         [--depth-weight W] [--depth-weight-final W] [--depth-mode depth|disparity]
         [--normal-weight W] [--normal-from-step S]
         [--distortion-weight W] [--distortion-from-step S] [--distortion-mode depth|ndc] [--distortion-far Z]
@@ -78,6 +79,11 @@ carry no correction and are rendered as given.
 brush_amd/exposure.py); --export-exposures writes the training views' names and maps as the run leaves them.  Eval views
 are rendered as given.
 
+--bilagrid-opt fits a bilateral grid (a GW x GH x GL lattice of affine colour maps read at pixel position and luminance,
+--bilagrid-shape) per training view beside the splats (TrainConfig.bilagrid_opt, brush_amd/bilagrid.py), smoothed by a
+total-variation prior of weight --bilagrid-tv; --export-bilagrids writes the training views' names and grids
+[V, GL, GH, GW, 12] as the run leaves them (.npz).  Not with --exposure-opt.  Eval views are rendered as given.
+
 BRUSH_DETERMINISTIC=1 makes the renders (and so a run with a fixed seed) bitwise repeatable.
 """
 from __future__ import annotations
@@ -120,6 +126,8 @@ class TrainLog:
     pose_deltas: Optional[List[List[float]]] = None  # pose_opt: the twist (omega, tau) of every training view
     exposure_opt: bool = False
     exposures: Optional[List[List[float]]] = None    # exposure_opt: the 3x4 map (12 floats, row-major) of every view
+    bilagrid_opt: bool = False                    # TrainConfig.bilagrid_opt: trained with per-view bilateral grids
+    bilagrid_shape: Optional[Tuple[int, int, int]] = None  # bilagrid_opt: (GW, GH, GL)
     downscales: List[Tuple[int, int]] = field(default_factory=list)  # (step, factor): the level switches that happened
     prunes: List[Tuple[int, int, int]] = field(default_factory=list)  # (step, splats before, after): contribution prunes
     background: object = None                     # TrainConfig.background as configured
@@ -135,6 +143,8 @@ class TrainLog:
         return {"steps": self.steps, "seconds": self.seconds, "train_seconds": self.train_seconds,
                 "image_bytes": self.image_bytes, "num_splats": self.num_splats, "pose_opt": self.pose_opt,
                 "pose_deltas": self.pose_deltas, "exposure_opt": self.exposure_opt, "exposures": self.exposures,
+                "bilagrid_opt": bool(self.bilagrid_opt),
+                "bilagrid_shape": None if self.bilagrid_shape is None else [int(x) for x in self.bilagrid_shape],
                 "downscales": [[int(s), int(f)] for s, f in self.downscales],
                 "prunes": [[int(s), int(b), int(a)] for s, b, a in self.prunes],
                 "background": list(self.background) if isinstance(self.background, tuple) else self.background,
@@ -217,6 +227,12 @@ class TrainLoop:
 
             self.exposures = ExposureTable(len(self.loader), self.device, self.config.lr_exposure,
                                            self.config.exposure_reg)
+        self.bilagrids = None
+        if self.config.bilagrid_opt:
+            from .bilagrid import BilagridTable
+
+            self.bilagrids = BilagridTable(len(self.loader), self.device, self.config.lr_bilagrid,
+                                           self.config.bilagrid_shape, self.config.bilagrid_tv)
         # 3D smoothing filter: the training views' records go to the device once, so that a refresh is launches only.
         # Full-size intrinsics and the dataset's poses, whatever level the downscale schedule trains at and whatever
         # pose_opt has moved: the filter bounds what the stored images can resolve.
@@ -314,8 +330,9 @@ class TrainLoop:
         i, view, gt = self.loader.next_indexed()
         self.trainer.step(self.splats, view.camera, gt, self.loader.scene_extent,
                           loss_out=self.losses[self.done:self.done + 1],
-                          view_index=i if (self.poses is not None or self.exposures is not None) else None,
-                          poses=self.poses, exposures=self.exposures,
+                          view_index=i if (self.poses is not None or self.exposures is not None
+                                           or self.bilagrids is not None) else None,
+                          poses=self.poses, exposures=self.exposures, bilagrids=self.bilagrids,
                           gt_depth=self.loader.depth(i) if self.config.depth_weight > 0.0 else None,
                           depth_scale=getattr(view, "depth_scale", 1.0),
                           depth_offset=getattr(view, "depth_offset", 0.0),
@@ -394,6 +411,9 @@ class TrainLoop:
         self.log.exposure_opt = self.exposures is not None
         if self.exposures is not None:
             self.log.exposures = self.exposures.exposures()
+        self.log.bilagrid_opt = self.bilagrids is not None
+        if self.bilagrids is not None:
+            self.log.bilagrid_shape = tuple(self.bilagrids.shape)
         self.log.losses = self.losses.cpu().numpy()  # synchronises
         self.log.seconds = time.perf_counter() - self._t0
         self.log.train_seconds = self.log.seconds - self._eval_seconds
@@ -508,6 +528,14 @@ def parser():
                    help="fit a per-view affine colour map (exposure / white balance) beside the splats")
     p.add_argument("--export-exposures", default=None, metavar="FILE.json",
                    help="write name and 3x4 exposure map of every training view after the run")
+    p.add_argument("--bilagrid-opt", action="store_true",
+                   help="fit a per-view bilateral grid (colour maps by pixel position and luminance) beside the splats")
+    p.add_argument("--bilagrid-shape", default=None, metavar="GW,GH,GL",
+                   help="--bilagrid-opt: the lattice of every view (default 16,16,8)")
+    p.add_argument("--bilagrid-tv", type=float, default=TrainConfig.bilagrid_tv, metavar="W",
+                   help="--bilagrid-opt: weight of the total-variation prior on the grids")
+    p.add_argument("--export-bilagrids", default=None, metavar="FILE.npz",
+                   help="write names and grids [V,GL,GH,GW,12] of the training views after the run")
     p.add_argument("--strategy", choices=("default", "mcmc"), default="default",
                    help="how the splat count evolves: clone / split / prune, or MCMC relocation with a fixed budget")
     p.add_argument("--cap-max", type=int, default=TrainConfig.mcmc_cap_max, metavar="N",
@@ -584,7 +612,14 @@ def main(argv=None) -> int:
         prune_at = () if args.contribution_prune_at is None else parse_prune_steps(args.contribution_prune_at)
         from .compose import parse_background
         background = None if args.background is None else parse_background(args.background)
-        config = TrainConfig(antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
+        shape = TrainConfig.bilagrid_shape
+        if args.bilagrid_shape is not None:
+            try:
+                shape = tuple(int(x) for x in args.bilagrid_shape.split(","))
+            except ValueError:
+                raise ValueError(f"--bilagrid-shape takes GW,GH,GL, got {args.bilagrid_shape!r}") from None
+        config = TrainConfig(bilagrid_opt=args.bilagrid_opt, bilagrid_shape=shape, bilagrid_tv=args.bilagrid_tv,
+                             antialiased=args.antialiased, pose_opt=args.pose_opt, strategy=args.strategy,
                              mcmc_cap_max=args.cap_max, exposure_opt=args.exposure_opt, depth_weight=args.depth_weight,
                              depth_weight_final=args.depth_weight_final, depth_mode=args.depth_mode,
                              downscale_schedule=schedule, contribution_prune_at=prune_at,
@@ -634,7 +669,11 @@ def main(argv=None) -> int:
 
     exposures = []
 
+    grids = []
+
     def on_finish(loop):
+        if loop.bilagrids is not None:
+            grids.append(loop.bilagrids.grids())
         if loop.exposures is not None:
             exposures.extend({"name": v.name, "exposure": [[float(x) for x in row] for row in m]}
                              for v, m in zip(loop.dataset.train.views, loop.exposures.matrices()))
@@ -661,6 +700,13 @@ def main(argv=None) -> int:
                                                            [0.0, 0.0, 1.0, 0.0]]} for v in data.train.views)
         with open(args.export_exposures, "w") as f:
             json.dump({"exposure_opt": bool(args.exposure_opt), "views": exposures}, f, indent=1)
+    if args.export_bilagrids:
+        from .bilagrid import bilagrid_identity
+
+        names = np.asarray([v.name for v in data.train.views])
+        g = grids[0] if grids else bilagrid_identity(config.bilagrid_shape).numpy()[None].repeat(len(names), axis=0)
+        with open(args.export_bilagrids, "wb") as f:
+            np.savez(f, names=names, grids=g)
     if args.json:
         res = {"dataset": os.path.abspath(args.dataset), "seed": args.seed, "sh_degree": args.sh_degree,
                "antialiased": bool(args.antialiased), "strategy": args.strategy,

@@ -535,6 +535,51 @@ int brush_exposure_backward_adam(const float *pred, const float *v_out, const Br
                                  uint32_t h, float *v_pred, float *exposure, float *moment1, float *moment2,
                                  float *v_exposure, void *workspace, size_t workspace_bytes, brush_stream_t stream);
 
+/* ---- per-view bilateral grids (build extension; gsplat's use_bilateral_grid, Wang et al. 2024) ------------------- */
+/* A training view carries a lattice grid[GL][GH][GW][12] f32, vertex-major, of the 3x4 affine colour maps above (identity
+ * [I | 0] at every vertex at the start), 2 <= GW, GH <= 64, 2 <= GL <= 8.  Pixel (x, y) of a [h][w][4] premultiplied
+ * render p = (r, g, b, alpha) reads it at (all f32, each operation rounded on its own, never contracted)
+ *   w == 1: i0 = 0, fx = 0;  otherwise n = x (GW-1), i0 = min(n div (w-1), GW-2), fx = float(n - i0 (w-1)) / float(w-1)
+ *   (y, h, GH give j0, fy the same way: align_corners, border clamp)
+ *   lum = (0.299f r + 0.587f g) + 0.114f b;  lc = lum > 0 ? min(lum, 1) : 0 (a NaN gives 0);  z = lc float(GL-1),
+ *   k0 = min((int) z, GL-2), fz = z - float(k0);  inside = lum > 0 && lum < 1
+ * and with lerp(a, b, f) = a + f (b - a), per word, for k in {k0, k0+1}
+ *   L_k = lerp(lerp(G[k][j0][i0], G[k][j0][i0+1], fx), lerp(G[k][j0+1][i0], G[k][j0+1][i0+1], fx), fy)
+ *   M = lerp(L_k0, L_k0+1, fz)     S = L_k0+1 - L_k0
+ *   out_c = ((M[4c] r + M[4c+1] g) + M[4c+2] b) + alpha M[4c+3]      out_alpha = alpha
+ * The identity grid returns pred bit for bit; a grid whose vertices all hold E returns brush_exposure_forward's bits.
+ * With v' = d L / d out the backward returns
+ *   q = inside ? float(GL-1) ((t_0 + t_1) + t_2) : 0,  t_c = v'_c (((S[4c] r + S[4c+1] g) + S[4c+2] b) + alpha S[4c+3])
+ *   v_pred.r = ((M[0] v'_0 + M[4] v'_1) + M[8] v'_2) + 0.299f q  (g, b: words 1 / 2, 0.587f / 0.114f)
+ *   v_pred.alpha = v'_alpha + ((M[3] v'_0 + M[7] v'_1) + M[11] v'_2)
+ *   v_grid[k][j][i][4c+m] = sum_pixels ((X Y) Z) (v'_c p_m)  (p_3 = alpha), X = 1 - fx at i = i0, fx at i = i0+1, 0
+ *   elsewhere, Y and Z likewise: float64 from the f32 fractions, summed in float64 in a fixed order with no atomics
+ *   and rounded to f32 once; a vertex no pixel reaches gets +0.  Every word of v_grid is written on every call.
+ * Images are 16-byte aligned, sides <= 32768, w h in [1, 2^28); grid is 16-byte aligned.  `out` may not alias `pred`;
+ * `v_pred` may alias `v_out`.  workspace: brush_bilagrid_workspace_size bytes (8-byte aligned), scratch, no state
+ * between calls.  All pointers are device pointers except `cfg`.  No allocation, no synchronisation: graph-capturable,
+ * and the same inputs give the same bits on every call. */
+int brush_bilagrid_workspace_size(uint32_t w, uint32_t h, uint32_t gw, uint32_t gh, uint32_t gl, size_t *bytes);
+int brush_bilagrid_forward(const float *pred, const float *grid, uint32_t gw, uint32_t gh, uint32_t gl, uint32_t w,
+                           uint32_t h, float *out, brush_stream_t stream);
+int brush_bilagrid_backward(const float *pred, const float *v_out, const float *grid, uint32_t gw, uint32_t gh,
+                            uint32_t gl, uint32_t w, uint32_t h, float *v_pred, float *v_grid, void *workspace,
+                            size_t workspace_bytes, brush_stream_t stream);
+/* brush_bilagrid_backward that also takes the Adam step of this view's grid inside its last kernel, as
+ * brush_exposure_backward_adam does for E, with the total-variation prior in place of the penalty: TV(G) = the sum over
+ * the three axes of the mean, over all adjacent vertex pairs along the axis and all 12 words, of (G[v+e] - G[v])^2, and
+ * g = v_grid's float64 sums + tv dTV/dG of the grid as it was BEFORE the step (taken in the launch that only reads the
+ * grid).  grid / moment1 / moment2: this view's GL GH GW 12 words each, updated in place; v_pred uses the grid as it
+ * was before the step; v_grid is written as by brush_bilagrid_backward (before the prior). */
+typedef struct BrushBilagridAdam {
+    float lr, beta1, beta2, epsilon, tv;
+    uint32_t time;
+} BrushBilagridAdam;
+int brush_bilagrid_backward_adam(const float *pred, const float *v_out, const BrushBilagridAdam *cfg, uint32_t gw,
+                                 uint32_t gh, uint32_t gl, uint32_t w, uint32_t h, float *v_pred, float *grid,
+                                 float *moment1, float *moment2, float *v_grid, void *workspace, size_t workspace_bytes,
+                                 brush_stream_t stream);
+
 /* ---- background colour and loss masks (build extension; gsplat's backgrounds / masks, nerfstudio's mask_path) ----- */
 /* Two element-wise maps that sit directly in front of the colour loss and behind it.  The op renders a premultiplied
  * image with no background; a trainer composes it, and the straight-alpha target, over a background colour b, and

@@ -77,6 +77,10 @@ crates/brush-render's public interface for the forward+backward rasterizer path:
                                 (brush_amd/distortion.py; build extension, 2DGS, GOF, RaDe-GS and gsplat's 2DGS path are
                                 the models; Splats.render_distortion, TrainConfig.distortion_weight,
                                 `python -m brush_amd.train_loop --distortion-weight`)
+  pack_splats / PackedSplats / morton_order  <- the chunk-quantised "compressed PLY" layout packed and unpacked on the
+                                device: Morton order, 256-row chunks, four words and one byte per higher-order SH value
+                                per splat (brush_amd/compress.py; build extension; Splats.to_compressed_ply,
+                                Splats.from_ply, `--export OUT.compressed.ply`, `python -m brush_amd.compress`)
   mcmc                       <- MCMC densification with a fixed splat budget (build extension; gsplat's MCMCStrategy
                                 is the model): TrainConfig(strategy="mcmc"), sample_by_weight, relocation, refine
 
@@ -123,6 +127,8 @@ _MEDIAN_DEPTH_NAMES = ("render_median_depth", "median_depth_from_aux")
 _FEATURE_NAMES = ("render_features", "splat_feature_sums", "lift_labels", "FeatureSums", "labels_from_sums",
                   "features_from_aux", "feature_grads_from_aux", "feature_sums_from_aux")
 _MESH_NAMES = ("Mesh", "mesh_to_ply", "mesh_from_ply", "default_bounds", "grid_for")
+# (brush_amd.compress is a command line as well)
+_COMPRESS_NAMES = ("pack_splats", "PackedSplats", "morton_order")
 
 
 def __getattr__(name):
@@ -159,6 +165,9 @@ def __getattr__(name):
     if name in _MESH_NAMES:
         from . import mesh as _mesh
         return getattr(_mesh, name)
+    if name in _COMPRESS_NAMES:
+        from . import compress as _compress
+        return getattr(_compress, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 __version__ = "0.4.0"

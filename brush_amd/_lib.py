@@ -301,6 +301,11 @@ _SYMBOLS = [
     ("brush_tsdf_mesh_count", C.c_int, [C.POINTER(BrushTsdfGrid), _P, C.c_uint32, _P, _P, C.c_size_t, _P]),
     ("brush_tsdf_mesh_emit", C.c_int,
      [C.POINTER(BrushTsdfGrid), _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_splat_pack_workspace_size", C.c_int, [C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("brush_splat_pack_keys", C.c_int,
+     [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("brush_splat_pack", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
+    ("brush_splat_unpack", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     ("brush_profiler_create", C.c_int, [C.POINTER(_P)]),
     ("brush_profiler_destroy", None, [_P]),
     ("brush_profiler_attach", None, [_P]),

@@ -75,10 +75,19 @@ class Splats(torch.nn.Module):
 
     @classmethod
     def from_ply(cls, path_or_bytes, device):
-        """crates/brush-dataset/src/splat_import.rs:183-312 (without the streaming updates)."""
-        from .ply import load_splat_from_ply
+        """crates/brush-dataset/src/splat_import.rs:183-312 (without the streaming updates).  Build extension: a
+        compressed PLY (ply.is_compressed_ply) is recognised; on a GPU device its packed arrays are uploaded as they are
+        and unpacked there (compress.PackedSplats), elsewhere it is unpacked in numpy (ply.unpack_compressed)."""
+        from .ply import _read_bytes, is_compressed_ply, load_splat_from_ply
 
-        d = load_splat_from_ply(path_or_bytes)
+        data = _read_bytes(path_or_bytes)
+        if torch.device(device).type == "cuda" and is_compressed_ply(data):
+            from .compress import PackedSplats
+
+            splats = PackedSplats.from_ply(data, device).unpack()
+            splats.norm_rotations()
+            return splats
+        d = load_splat_from_ply(data)
         t = lambda a: torch.as_tensor(a, dtype=torch.float32, device=device)
         splats = cls(t(d["means"]), t(d["sh_coeffs"]), t(d["rotation"]), t(d["raw_opacity"]), t(d["log_scales"]))
         splats.norm_rotations()  # every import ends with norm_rotations() (splat_import.rs:139,150)
@@ -97,6 +106,18 @@ class Splats(torch.nn.Module):
         self.sync()
         c = lambda p: p.detach().cpu().numpy()
         return splat_to_ply(c(self.means), c(self.log_scales), c(self.rotation), c(self.raw_opacity), c(self.sh_coeffs))
+
+    def to_compressed_ply(self, sh_degree=None) -> bytes:
+        """The chunk-quantised "compressed PLY" (brush_amd/compress.py): packed on the device, 16 B + 3K B per splat
+        read back instead of the float tensors.  `sh_degree`: the SH degree written (None: all bands; a lower one drops
+        the bands above it).  ValueError for CPU tensors (the packer runs on the device), for a non-finite parameter
+        and for SH degrees the layout does not have."""
+        from .compress import pack_splats
+
+        if not self.means.is_cuda:
+            raise ValueError("the packer runs on the device: Splats.to_compressed_ply needs the splats on a GPU "
+                             "(to_ply writes the float PLY from any device)")
+        return pack_splats(self, sh_degree=sh_degree).to_ply()
 
     def num_splats(self) -> int:
         return self.means.shape[0]

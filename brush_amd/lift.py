@@ -42,7 +42,9 @@ def parser():
                    help="a splat whose best class received no more than W pixels of full weight stays unlabelled (-1)")
     p.add_argument("--export-labels", default=None, metavar="OUT.npy", help="write the int32 [N] labels")
     p.add_argument("--select", type=int, default=None, metavar="CLASS", help="with --export: the class to cut out")
-    p.add_argument("--export", default=None, metavar="OUT.ply", help="write the splats of --select to this .ply")
+    p.add_argument("--export", default=None, metavar="OUT.ply",
+                   help="write the splats of --select to this .ply (a name ending in .compressed.ply: the "
+                        "chunk-quantised layout)")
     p.add_argument("--render-dir", default=None, metavar="DIR",
                    help="write the rendered label image of every eval view here")
     p.add_argument("--json", default=None, metavar="OUT.json", help="also write the results to this file")
@@ -175,8 +177,10 @@ def main(argv=None) -> int:
     if args.export_labels:
         np.save(args.export_labels, got.astype(np.int32))
     if args.export:
+        from .compress import ply_bytes_for  # OUT.compressed.ply: the compressed layout
+
         with open(args.export, "wb") as f:
-            f.write(splats.select(labels == args.select).to_ply())
+            f.write(ply_bytes_for(splats.select(labels == args.select), args.export))
     rendered = 0
     if args.render_dir and has_eval:
         from PIL import Image

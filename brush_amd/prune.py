@@ -29,7 +29,9 @@ def parser():
     p.add_argument("--views", choices=("train", "eval", "all"), default="train",
                    help="the views the contribution is measured over")
     p.add_argument("--antialiased", action="store_true", help="render in the antialiased mode")
-    p.add_argument("--export", default=None, metavar="OUT.ply", help="write the kept splats to this .ply")
+    p.add_argument("--export", default=None, metavar="OUT.ply",
+                   help="write the kept splats to this .ply (a name ending in .compressed.ply: the chunk-quantised "
+                        "layout)")
     p.add_argument("--json", default=None, metavar="OUT.json", help="also write the results to this file")
     p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
     p.add_argument("--eval-split-every", type=int, default=None)
@@ -103,8 +105,10 @@ def main(argv=None) -> int:
         print(f"eval ({before['views']} views)\tpsnr {before['psnr']:.4f} -> {after['psnr']:.4f}\t"
               f"ssim {before['ssim']:.6f} -> {after['ssim']:.6f}")
     if args.export:
+        from .compress import ply_bytes_for  # OUT.compressed.ply: the compressed layout
+
         with open(args.export, "wb") as f:
-            f.write(kept.to_ply())
+            f.write(ply_bytes_for(kept, args.export))
     if args.json:
         res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "rule": rule,
                "views": args.views, "num_views": len(views), "antialiased": bool(args.antialiased),

@@ -516,7 +516,9 @@ def parser():
     p.add_argument("--init-count", type=int, default=10000, help="random initial splats when there are no points")
     p.add_argument("--sh-degree", type=int, default=3)
     p.add_argument("--seed", type=int, default=42)
-    p.add_argument("--export", default=None, help="write the trained splats to this .ply")
+    p.add_argument("--export", default=None,
+                   help="write the trained splats to this .ply (a name ending in .compressed.ply: the "
+                        "chunk-quantised layout, brush_amd/compress.py)")
     p.add_argument("--json", default=None, help="write the eval rows and the loss curve to this file")
     p.add_argument("--antialiased", action="store_true",
                    help="train (and evaluate) in the antialiased mode: opacity compensation of the 2D blur")
@@ -689,8 +691,10 @@ def main(argv=None) -> int:
     print(f"done: {log.steps} steps in {log.seconds:.1f} s ({rate:.1f} it/s), {log.num_splats} splats, "
           f"final loss {final:.6f}, {log.image_bytes / 1e6:.1f} MB of images on the device")
     if args.export:
+        from .compress import ply_bytes_for  # OUT.compressed.ply: the compressed layout
+
         with open(args.export, "wb") as f:
-            f.write(splats.to_ply())
+            f.write(ply_bytes_for(splats, args.export))
     if args.export_cameras:
         with open(args.export_cameras, "w") as f:
             json.dump({"pose_opt": bool(args.pose_opt), "cameras": cameras}, f, indent=1)

@@ -1084,6 +1084,61 @@ int brush_tsdf_mesh_emit(const BrushTsdfGrid *h_grid, const uint32_t *volume, ui
                          uint32_t num_faces, float *vertices, uint8_t *colors, uint32_t *faces, void *workspace,
                          size_t workspace_bytes, brush_stream_t stream);
 
+/* ---- compressed splats: the chunk-quantised PLY layout, packed and unpacked on the device (build extension) ----- */
+/* The layout other trainers and viewers exchange as "compressed PLY": the splats sorted along a Morton curve, cut into
+ * chunks of BRUSH_SPLAT_CHUNK = 256 rows, each chunk with the min and max of nine quantities (18 floats:
+ * min_x min_y min_z max_x max_y max_z, the same of the scales, the same of the colours), each splat as four 32-bit
+ * words (position 11-10-11, rotation 2-10-10-10, scale 11-10-11, colour and opacity 8-8-8-8) plus one byte per
+ * higher-order SH value.  16 B + 3K B per splat, K = 0, 3, 8, 15 at SH degree 0..3, against 236 B in float at degree 3.
+ * Arithmetic: float32, every operation rounded on its own (no contraction), IEEE division and square root.  Every input
+ * value v is read as v + 0.0f (so -0 and +0 pack alike).
+ *   order      lo, hi = per-axis min, max of the means; q = 0 where hi == lo, else
+ *              min(1023, (uint32)(((x - lo) / (hi - lo)) * 1024.0f)); key = spread(qz) << 2 | spread(qy) << 1 |
+ *              spread(qx) (30-bit Morton code); a STABLE sort by key; rows 256 j .. 256 j + 255 form chunk j, the last
+ *              chunk holds the remainder and its min / max run over its real rows only.
+ *   quantities p = mean; s = clamp(log_scale, -20, 20); c = f_dc * 0.28209479177387814f + 0.5f.
+ *   norm(v, lo, hi) = 0 if v <= lo, else 1 if v >= hi, else 0 if hi - lo < 1e-5f, else (v - lo) / (hi - lo)
+ *   unorm(t, b)     = (uint32) min(2^b - 1, max(0, floor(t * (2^b - 1) + 0.5f)))
+ *   position   unorm(nx, 11) << 21 | unorm(ny, 10) << 11 | unorm(nz, 11); scale: the same over s
+ *   colour     unorm(nr, 8) << 24 | unorm(ng, 8) << 16 | unorm(nb, 8) << 8 | unorm(a, 8), a = 1 / (1 + det_expf(-raw))
+ *   rotation   a = (w, x, y, z) / sqrt(((w w + x x) + y y) + z z), (1, 0, 0, 0) when the norm is zero or not finite;
+ *              L = first index of the largest |a[i]|; all four negated if a[L] < 0; word = L, then for every i != L in
+ *              rising order word = word << 10 | unorm(a[i] * 0.70710678f + 0.5f, 10)
+ *   SH byte    min(255, max(0, floor((v / 8 + 0.5f) * 256))), stored channel-major: byte c K + (k - 1) of a row
+ * Unpacking: t = code / (2^b - 1), value = lo * (1 - t) + hi * t; f_dc = (c - 0.5f) / 0.28209479177387814f;
+ * raw_opacity = det_logf(a / (1 - a)) with a = clamp(code, 0.5, 254.5) / 255 (finite at codes 0 and 255); a stored
+ * rotation component is (code / 1023 - 0.5f) * 1.41421356f and the largest sqrt(max(0, 1 - ((a a + b b) + c c))), put
+ * back at index L; an SH value is ((byte + 0.5f) / 256 - 0.5f) * 8.
+ *
+ * Tensors are those of Splats: means [n,3], log_scales [n,3], rotation [n,4] (w, x, y, z; 16-byte aligned),
+ * raw_opacity [n], sh_coeffs [n,(sh_degree+1)^2,3] (16-byte aligned at degrees 1 and 3, whose rows are read and
+ * written as whole 16-byte words); sh_degree 0..3; n in [1, BRUSH_SPLAT_PACK_MAX].  All pointers are device pointers.
+ * Anything else, a NULL or misaligned pointer returns BRUSH_ERR_INVALID_ARG before any GPU call.  All three entries
+ * enqueue on `stream`, allocate nothing, synchronise nothing and use no atomics: the same inputs give the same bits.
+ *
+ * brush_splat_pack_keys: keys[n] and vals[n] (= 0 .. n-1) ready for brush_radix_argsort_u32 with sorting_bits = 30 and
+ * d_n = state; state[0] = n, state[1] = 1 when any word of any of the five tensors is an infinity or a NaN, else 0.
+ * workspace: brush_splat_pack_workspace_size(n) bytes, 256-byte aligned (the partial bounds).
+ * brush_splat_pack: `order` [n] is the sorted vals (row i of the output is input splat order[i]).  One workgroup per
+ * chunk.  chunks [C][18], C = ceil(n / 256); words [256 C][4] (16-byte aligned) and sh_out [256 C][3K] u8 (4-byte
+ * aligned; NULL at sh_degree_out 0) are allocated for whole chunks: the rows behind n are written as zeros, the SH bytes
+ * of a chunk leave as whole 32-bit words.  sh_degree_out <= sh_degree drops the bands above it.
+ * brush_splat_unpack: chunks [C][18], words [n][4] (16-byte aligned), sh_in [n][3K] u8 (4-byte aligned, n rows exactly)
+ * into the five tensors, in packed order, sh_coeffs [n,(sh_degree+1)^2,3]. */
+#define BRUSH_SPLAT_CHUNK 256u
+#define BRUSH_SPLAT_PACK_MAX (1u << 30)
+int brush_splat_pack_workspace_size(uint32_t n, size_t *bytes);
+int brush_splat_pack_keys(const float *means, const float *log_scales, const float *rotation,
+                          const float *raw_opacity, const float *sh_coeffs, uint32_t n, uint32_t sh_degree,
+                          uint32_t *keys, uint32_t *vals, uint32_t *state, void *workspace, size_t workspace_bytes,
+                          brush_stream_t stream);
+int brush_splat_pack(const float *means, const float *log_scales, const float *rotation, const float *raw_opacity,
+                     const float *sh_coeffs, uint32_t n, uint32_t sh_degree, uint32_t sh_degree_out,
+                     const uint32_t *order, float *chunks, uint32_t *words, uint8_t *sh_out, brush_stream_t stream);
+int brush_splat_unpack(const float *chunks, const uint32_t *words, const uint8_t *sh_in, uint32_t n, uint32_t sh_degree,
+                       float *means, float *log_scales, float *rotation, float *raw_opacity, float *sh_coeffs,
+                       brush_stream_t stream);
+
 /* ---- opt-in stage timing ---------------------------------------------------------------- */
 /* Counterpart of the reference's tracing spans + sync-span layer (render.rs:69-267,474-577;
  * crates/sync-span/src/lib.rs:12-49): when a profiler is attached to the calling host thread,

@@ -99,20 +99,23 @@ def _twin(cloud, u):
     return tw, z
 
 
-def _render_depth(dev, cloud, w, h, det, grad=False, camera=None):
-    """`camera` (here and below): a brush_amd.Camera in place of the reference test camera."""
+def _render_depth(dev, cloud, w, h, det, grad=False, camera=None, max_intersects=None):
+    """`camera` (here and below): a brush_amd.Camera in place of the reference test camera; `max_intersects`: an
+    intersection capacity in place of the default."""
     import brush_amd
 
     t = _tensors(cloud, dev, grad)
-    img, depth, aux = brush_amd.render_splats_depth(camera or _camera(w, h), (w, h), *_args(t), deterministic=det)
+    img, depth, aux = brush_amd.render_splats_depth(camera or _camera(w, h), (w, h), *_args(t),
+                                                    max_intersects=max_intersects, deterministic=det)
     return t, img, depth, aux
 
 
-def _render(dev, cloud, w, h, det, grad=False, camera=None):
+def _render(dev, cloud, w, h, det, grad=False, camera=None, max_intersects=None):
     import brush_amd
 
     t = _tensors(cloud, dev, grad)
-    img, aux = brush_amd.render_splats(camera or _camera(w, h), (w, h), *_args(t), deterministic=det)
+    img, aux = brush_amd.render_splats(camera or _camera(w, h), (w, h), *_args(t), max_intersects=max_intersects,
+                                       deterministic=det)
     return t, img, aux
 
 
@@ -141,7 +144,7 @@ def test_forward_matches_depth_as_colour_twin(dev, kind):
     check_forward_twin(dev, kind, *_scene(kind))
 
 
-def check_forward_twin(dev, kind, cloud, w, h, camera=None, max_risk=None):
+def check_forward_twin(dev, kind, cloud, w, h, camera=None, max_risk=None, max_intersects=None, det=False):
     """The body of test_forward_matches_depth_as_colour_twin; returns (V, worst err/tol against the GPU twin, worst
     err/tol against the oracle's twin).  `max_risk`: the largest share of flip-risk pixels the caller accepts."""
     import torch
@@ -149,10 +152,10 @@ def check_forward_twin(dev, kind, cloud, w, h, camera=None, max_risk=None):
     from brush_amd.render import uniforms_to_numpy
 
     with torch.no_grad():
-        _, img, depth, aux = _render_depth(dev, cloud, w, h, False, camera=camera)
+        _, img, depth, aux = _render_depth(dev, cloud, w, h, det, camera=camera, max_intersects=max_intersects)
         u = _u(aux, w, h, cloud, camera)
         tw, z = _twin(cloud, u)
-        _, timg, taux = _render(dev, tw, w, h, False, camera=camera)
+        _, timg, taux = _render(dev, tw, w, h, det, camera=camera, max_intersects=max_intersects)
     D, R = _np(depth).astype(np.float64), _np(timg)[..., 0].astype(np.float64)
     assert depth.shape == (h, w) and depth.dtype == torch.float32
     V = aux.read_num_visible()
@@ -169,7 +172,7 @@ def check_forward_twin(dev, kind, cloud, w, h, camera=None, max_risk=None):
     assert (err <= tol + 1e-30).all(), (kind, float(err.max()), int((err > tol).sum()))
     # the CPU oracle's twin, within the forward gate's colour margin scaled by the depth range
     o_out, o_aux = O.render_forward(uniforms_to_numpy(taux), tw["means"], tw["log_scales"], tw["quats"], tw["sh"],
-                                    tw["raw_opac"])
+                                    tw["raw_opac"], max_intersects=max_intersects)
     assert int(o_aux["num_visible"][0]) == V
     risk = o_aux["flip_risk"].astype(bool)
     assert max_risk is None or risk.mean() <= max_risk, (kind, int(risk.sum()))
@@ -203,36 +206,43 @@ def test_image_and_aux_bitwise_equal(dev, kind, det):
 
 
 # ---------------------------------------------------------------------------- 3. backward by linearity
-def _grads(dev, cloud, w, h, det, v_out, v_d=None, camera=None):
+def _grads(dev, cloud, w, h, det, v_out, v_d=None, camera=None, max_intersects=None):
     """Gradients of <img, v_out> (+ <depth, v_d>) into the six parents: the depth op when v_d is given, else
     render_splats."""
     import torch
 
     if v_d is None:
-        t, img, aux = _render(dev, cloud, w, h, det, grad=True, camera=camera)
+        t, img, aux = _render(dev, cloud, w, h, det, grad=True, camera=camera, max_intersects=max_intersects)
         outs, gos = [img], [v_out]
     else:
-        t, img, depth, aux = _render_depth(dev, cloud, w, h, det, grad=True, camera=camera)
+        t, img, depth, aux = _render_depth(dev, cloud, w, h, det, grad=True, camera=camera,
+                                           max_intersects=max_intersects)
         outs, gos = [img, depth], [v_out, v_d]
     ps = [t["means"], t["xy"], t["log_scales"], t["quats"], t["sh"], t["raw_opac"]]
     g = torch.autograd.grad(outs, ps, gos)
     return dict(zip(GRADS, (_np(x) for x in g))), img, aux
 
 
-def _linear_parts(dev, cloud, w, h, det, v_out, v_d, camera=None, column=False):
+def _linear_parts(dev, cloud, w, h, det, v_out, v_d, camera=None, column=False, max_intersects=None, control=None):
     """existing backward(v_out) + twin backward with v_out = (v_D, 0, 0, 0), v_z = v_sh_dc_r / C0 into v_means.
-    `column`: the mistaken depth term of _z_row, for the negative controls."""
+    `column`: the mistaken depth term of _z_row, for the negative controls; `control`: another mistaken reference,
+    "rotate_quadrants" or "no_depth_in_alpha" (arbiter_gate)."""
     import torch
 
-    base, _, aux = _grads(dev, cloud, w, h, det, v_out, camera=camera)
+    base, _, aux = _grads(dev, cloud, w, h, det, v_out, camera=camera, max_intersects=max_intersects)
     u = _u(aux, w, h, cloud, camera)
     tw, _ = _twin(cloud, u)
     vt = torch.zeros_like(v_out)
     vt[..., 0] = v_d
-    twin, _, _ = _grads(dev, tw, w, h, det, vt, camera=camera)
+    if control == "rotate_quadrants":
+        vt[..., 0] = torch.as_tensor(_quadrants_rotated(_np(v_d)), device=v_d.device)
+    elif control not in (None, "no_depth_in_alpha"):
+        raise ValueError(control)
+    twin, _, _ = _grads(dev, tw, w, h, det, vt, camera=camera, max_intersects=max_intersects)
     row = _z_row(u, column)
     v_z = twin["v_sh"][:, 0, 0].astype(np.float64) / float(C0)
-    want = {k: base[k].astype(np.float64) + (0.0 if k == "v_sh" else twin[k]) for k in GRADS}
+    omit = control == "no_depth_in_alpha"
+    want = {k: base[k].astype(np.float64) + (0.0 if k == "v_sh" or omit else twin[k]) for k in GRADS}
     want["v_means"] = want["v_means"] + v_z[:, None] * row[None, :]
     mags = {k: np.abs(base[k]) + (0.0 if k == "v_sh" else np.abs(twin[k])) for k in GRADS}
     mags["v_means"] = mags["v_means"] + np.abs(v_z[:, None] * row[None, :])
@@ -260,11 +270,13 @@ def _gate_ratio(got, want, rtol, atol):
     return float((np.abs(got - want) / (atol + rtol * np.abs(want))).max()) if got.size else 0.0
 
 
-def check_backward_linearity(dev, kind, det, cloud, w, h, camera=None, column=False):
+def check_backward_linearity(dev, kind, det, cloud, w, h, camera=None, column=False, max_intersects=None,
+                             control=None):
     """The body of test_backward_is_sum_of_colour_and_twin_parts; returns the worst err/tol per gradient."""
     v_out, v_d = _upstream(dev, w, h, seed=5)
-    got, _, _ = _grads(dev, cloud, w, h, det, v_out, v_d, camera=camera)
-    want, mags, _, _, _ = _linear_parts(dev, cloud, w, h, det, v_out, v_d, camera=camera, column=column)
+    got, _, _ = _grads(dev, cloud, w, h, det, v_out, v_d, camera=camera, max_intersects=max_intersects)
+    want, mags, _, _, _ = _linear_parts(dev, cloud, w, h, det, v_out, v_d, camera=camera, column=column,
+                                        max_intersects=max_intersects, control=control)
     ratios = {}
     for k in GRADS:
         scale = float(mags[k].max()) if mags[k].size else 0.0
@@ -311,6 +323,149 @@ def check_backward_oracle(dev, kind, cloud, w, h, camera=None, column=False):
         ratios[k] = _gate_ratio(got[k], want, rtol, 1e-4 * scale + 1e-12)
         assert ok, f"{kind} {k}: max_abs_err={err} bad={bad} scale={scale}"
     return ratios
+
+
+# ---------------------------------------------------------------------------- 3b. backward against the f64 arbiter
+# The depth gradient element by element, under the allowance the colour gradient is held to (test_gpu_render.
+# _assert_grad_parity: every term tied to a mechanism, none a fraction of a tensor's maximum).  By linearity the exact
+# value is arbiter(cloud, v_out) + arbiter(twin at SH degree 0, (v_D, 0, 0, 0)), the twin's v_sh left out and
+# v_z = twin v_sh[:, 0, 0] / C0 sent into v_means along row 2 of W; the kernel adds the two parts' terms in one f32
+# accumulator, so its allowance is the sum of the two calls' allowances, the v_z part priced like the value it is made
+# from.  One term is new: the twin's f32 colour fl(fl(C0 dc) + 0.5), dc = fl((z - 0.5) / C0), is z only to four
+# roundings, 4 eps32 (|z| + 0.5) per depth term, where the kernel works from z itself: 4 eps32 of the twin's mag_*.
+TWIN_COLOUR_ROUNDINGS = 4.0
+ARBITER_GRADS = ("v_means", "v_scales", "v_quats", "v_sh", "v_opac", "v_xy")
+
+
+def _np_u32(t):
+    return t.detach().cpu().numpy().astype(np.int32).view(np.uint32)
+
+
+def _quadrants_rotated(v_d):
+    """v_D with the four 8 x 8 quadrants of every 16 x 16 tile moved on by one (0 -> 1 -> 2 -> 3 -> 0, quadrant
+    q = (x / 8 & 1) + 2 (y / 8 & 1)): what a quadrant mix-up in the multi-quadrant forms would consume.  Zero-padded to
+    whole tiles first."""
+    h, w = v_d.shape
+    hp, wp = -(-h // 16) * 16, -(-w // 16) * 16
+    p = np.zeros((hp, wp), v_d.dtype)
+    p[:h, :w] = v_d
+    q = p.reshape(hp // 16, 2, 8, wp // 16, 2, 8).transpose(0, 3, 1, 4, 2, 5).reshape(hp // 16, wp // 16, 4, 8, 8)
+    q = np.roll(q, 1, axis=2)
+    p = q.reshape(hp // 16, wp // 16, 2, 2, 8, 8).transpose(0, 2, 4, 1, 3, 5).reshape(hp, wp)
+    return np.ascontiguousarray(p[:h, :w])
+
+
+def arbiter_state(dev, kind, det, cloud, w, h, camera=None, max_intersects=None, zero_v_out=False):
+    """One depth backward on the GPU and the two arbiter calls on the forward state it consumed: the oracle's aux of
+    the cloud (of the twin) with final_index replaced by the GPU's, and the GPU's own images.  Returns a dict with the
+    GPU's gradients (`got`), the float64 arbiter's and the f32-sum oracle's results of both calls, and what a control
+    needs to build another reference.  `zero_v_out`: v_out = 0, the depth gradient alone; every term of the colour
+    call then carries a factor 0, so its results and allowance are zeros and the call is not made."""
+    import torch
+
+    from brush_amd.render import uniforms_to_numpy
+    from tests import binning_check as BK
+
+    v_out, v_d = _upstream(dev, w, h, seed=5)
+    if zero_v_out:
+        v_out = torch.zeros_like(v_out)
+    got, img, aux = _grads(dev, cloud, w, h, det, v_out, v_d, camera=camera, max_intersects=max_intersects)
+    ud = uniforms_to_numpy(aux)
+    u = _u(aux, w, h, cloud, camera)
+    tw, _ = _twin(cloud, u)
+    with torch.no_grad():
+        _, timg, taux = _render(dev, tw, w, h, det, camera=camera, max_intersects=max_intersects)
+    # one forward state: the twin composites the same entries with the same alphas
+    assert bool(torch.equal(aux.final_index, taux.final_index)), kind
+    assert bool(torch.equal(img[..., 3], timg[..., 3])), kind
+    fin = _np_u32(aux.final_index)
+    ut = ud | {"sh_degree": 0}
+    o_img, o_aux = O.render_forward(ud, cloud["means"], cloud["log_scales"], cloud["quats"], cloud["sh"],
+                                    cloud["raw_opac"], max_intersects=aux.max_intersects)
+    BK.assert_integer_parity(BK.aux_arrays(aux, ud["num_visible"]), o_aux)  # the lists the arbiter walks are the GPU's
+    _, t_aux = O.render_forward(ut, tw["means"], tw["log_scales"], tw["quats"], tw["sh"], tw["raw_opac"],
+                                max_intersects=aux.max_intersects)
+    shared, t_shared = dict(o_aux, final_index=fin), dict(t_aux, final_index=fin)
+    g_img, g_timg = _np(img), _np(timg)
+    vo = _np(v_out)
+    vt = np.zeros((h, w, 4), np.float32)
+    vt[..., 0] = _np(v_d)
+    geo = (cloud["means"], cloud["log_scales"], cloud["quats"], cloud["raw_opac"])
+    st = dict(kind=kind, det=det, got=got, u=u, ut=ut, t_shared=t_shared, g_timg=g_timg, geo=geo, v_d=_np(v_d),
+              V=int(o_aux["num_visible"][0]), gids=o_aux["global_from_compact_gid"][:int(o_aux["num_visible"][0])],
+              twin64=O.render_backward_f64(ut, t_shared, *geo, g_timg, vt),
+              twin32=O.render_backward(ut, t_shared, *geo, g_timg, vt, f32_sums=True))
+    if zero_v_out:
+        zeros = {k: np.zeros(cloud["sh"].shape if k.endswith("sh") else v.shape) for k, v in st["twin64"].items()}
+        st.update(base64=zeros, base32={k: zeros[k] for k in ARBITER_GRADS})
+    else:
+        st.update(base64=O.render_backward_f64(ud, shared, *geo, g_img, vo),
+                  base32=O.render_backward(ud, shared, *geo, g_img, vo, f32_sums=True))
+    return st
+
+
+def _call_allowance(f64, f32, name):
+    """The allowance test_gpu_render._grad_ratio grants one arbiter call on tensor `name`, per element: its constants
+    and RTOL by import, the C_REF row term from the f32-sum oracle `f32` of the same call."""
+    from tests import test_gpu_render as TR
+
+    t = f64[name]
+    row_ref = TR._rowmax(np.abs(f32[name].astype(np.float64).reshape(t.shape) - t), t.shape)
+    _, _, parts = TR._grad_ratio(t, f64, row_ref, name, TR.CANDIDATES[TR.ACTIVE])
+    tol = np.zeros(t.shape)
+    for p in parts:
+        tol = tol + p
+    return tol
+
+
+def arbiter_gate(st, control=None):
+    """Asserts the GPU gradients of `st` (arbiter_state) within the allowance of the expected value, element by element;
+    returns, per tensor, dict(worst err/tol, worst_noflip: the same over the elements without a flip allowance).  `control` swaps in a WRONG expected value, the allowance unchanged, for the
+    negative controls: "column" (v_z along column 2 of W), "rotate_quadrants" (the twin backward fed v_D with every
+    tile's quadrants moved on by one), "no_depth_in_alpha" (the depth channel left out of the colour term of v_alpha:
+    of the twin only v_z survives, its v_opac / v_xy / conic parts and what they become are omitted)."""
+    base64, twin64 = st["base64"], st["twin64"]
+    src = twin64
+    if control == "rotate_quadrants":
+        vt = np.zeros(st["g_timg"].shape, np.float32)
+        vt[..., 0] = _quadrants_rotated(st["v_d"])
+        src = O.render_backward_f64(st["ut"], st["t_shared"], *st["geo"], st["g_timg"], vt)
+    elif control not in (None, "column", "no_depth_in_alpha"):
+        raise ValueError(control)
+    row = _z_row(st["u"], column=control == "column")
+    c0 = float(C0)
+    ratios, noflip = {}, {}
+    for k in ARBITER_GRADS:
+        mag, flip = "mag_" + k[2:], "flip_" + k[2:]
+        want, tol, flips = base64[k], _call_allowance(base64, st["base32"], k), base64[flip] != 0
+        if k != "v_sh":
+            if control != "no_depth_in_alpha":
+                want = want + src[k]
+            tol = tol + _call_allowance(twin64, st["twin32"], k) + TWIN_COLOUR_ROUNDINGS * EPS32 * twin64[mag]
+            flips = flips | (twin64[flip] != 0)
+        if k == "v_means":
+            flips = flips | (twin64["flip_sh"][:, 0, 0] != 0)[:, None]
+            want = want + (src["v_sh"][:, 0, 0] / c0)[:, None] * row[None, :]
+            tz = _call_allowance(twin64, st["twin32"], "v_sh")[:, 0, 0] + \
+                TWIN_COLOUR_ROUNDINGS * EPS32 * twin64["mag_sh"][:, 0, 0]
+            tol = tol + (tz / c0)[:, None] * np.abs(_z_row(st["u"]))[None, :]
+        err = np.abs(st["got"][k].astype(np.float64).reshape(want.shape) - want)
+        ratio = err / (tol + 1e-300)
+        i = int(np.argmax(ratio)) if ratio.size else 0
+        ratios[k] = float(ratio.reshape(-1)[i]) if ratio.size else 0.0
+        noflip[k] = float(ratio[~flips].max()) if (~flips).any() else 0.0
+        print(f"[depth arbiter {st['kind']} det={st['det']} control={control}] {k}: worst err/tol {ratios[k]:.3f} "
+              f"(err {float(err.reshape(-1)[i]) if ratio.size else 0.0:.3e}, want "
+              f"{float(want.reshape(-1)[i]) if ratio.size else 0.0:.3e}), {int((ratio > 1.0).sum())} of {ratio.size} over; "
+              f"off the {int(flips.sum())} elements with a flip allowance {noflip[k]:.3f}")
+    for k in ARBITER_GRADS:
+        assert ratios[k] <= 1.0, f"{st['kind']} det={st['det']} {k}: worst err/tol {ratios[k]:.3f} against the f64 arbiter"
+    return {k: dict(worst=ratios[k], worst_noflip=noflip[k]) for k in ARBITER_GRADS}
+
+
+def check_backward_arbiter(dev, kind, det, cloud, w, h, camera=None, max_intersects=None, control=None):
+    """The depth backward against the float64 arbiter, element by element; returns the worst err/tol per tensor."""
+    return arbiter_gate(arbiter_state(dev, kind, det, cloud, w, h, camera=camera, max_intersects=max_intersects), control)
 
 
 def test_deterministic_backward_bitwise(dev):

@@ -5,6 +5,9 @@ worst err/tol with the parts of the allowance at that element, the worst ratio o
 pixel figures.  Run it after a green `pytest -m gpu` whenever a kernel change moves the margins on purpose:
 
     python tools/update_parity_margins.py [--from gpurun_out/parity_margins.json] [--note "why"]
+
+With --merge it keeps the tracked entries of the tests the run did not execute (a run of some modules only) and replaces those
+of the tests it did.
 """
 import argparse
 import json
@@ -19,9 +22,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--from", dest="src", default=os.path.join(ROOT, "gpurun_out", "parity_margins.json"))
     ap.add_argument("--note", default="")
+    ap.add_argument("--merge", action="store_true")
     a = ap.parse_args()
     with open(a.src) as f:
         modes = json.load(f)
+    dst = os.path.join(ROOT, "profiles", "parity_margins.json")
+    if a.merge:
+        with open(dst) as f:
+            kept = json.load(f).get("modes", {})
+        for m, tests in modes.items():
+            kept.setdefault(m, {}).update(tests)
+        modes = kept
     try:
         head = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], text=True).strip()
     except Exception:
@@ -34,7 +45,6 @@ def main():
         "note": a.note,
         "modes": modes,
     }
-    dst = os.path.join(ROOT, "profiles", "parity_margins.json")
     with open(dst, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
     n = sum(len(v) for v in modes.values())

@@ -26,7 +26,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, cli
 from .ply import CHUNK, compressed_to_ply, load_compressed_ply, sh_rest_count
 
 _DEGREE_OF_COEFFS = {1: 0, 4: 1, 9: 2, 16: 3}
@@ -196,14 +196,10 @@ def parser():
     p.add_argument("--export", default=None, metavar="OUT.compressed.ply", help="write the compressed PLY here")
     p.add_argument("--dataset", default=None, metavar="DIR",
                    help="dataset directory or .zip: render its views from the original and the round-tripped splats")
-    p.add_argument("--views", choices=("train", "eval", "all"), default="eval", help="with --dataset: the views rendered")
-    p.add_argument("--antialiased", action="store_true", help="render in the antialiased mode")
-    p.add_argument("--json", default=None, metavar="OUT.json", help="also write the results to this file")
-    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
-    p.add_argument("--eval-split-every", type=int, default=None)
-    p.add_argument("--max-resolution", type=int, default=None)
-    p.add_argument("--no-undistort", action="store_true",
-                   help="use views with lens distortion as loaded, as if they were pinhole")
+    cli.add_views_option(p, "eval", "with --dataset: the views rendered")
+    cli.add_antialiased_option(p)
+    cli.add_json_option(p, metavar="OUT.json")
+    cli.add_dataset_options(p)
     return p
 
 
@@ -237,20 +233,12 @@ def roundtrip_errors(splats, packed: PackedSplats, back) -> dict:
 
 
 def main(argv=None) -> int:
-    import json
     import os
-    import sys
 
     args = parser().parse_args(argv)
-    from .gaussian_splats import Splats
-
-    data = None
-    if args.dataset:
-        from .eval import _load_dataset
-
-        data = _load_dataset(args)  # before any GPU work
-    dev = torch.device("cuda", torch.cuda.current_device())
-    splats = (Splats.from_safetensors if args.splats.endswith(".safetensors") else Splats.from_ply)(args.splats, dev)
+    data = cli.read_args_dataset(args) if args.dataset else None  # before any GPU work
+    dev = cli.cuda_device()
+    splats = cli.load_splats(args.splats, dev)
     packed = pack_splats(splats, sh_degree=args.sh_degree)
     blob = packed.to_ply()  # raises for non-finite parameters
     back = PackedSplats.from_ply(blob, dev).unpack()
@@ -269,11 +257,9 @@ def main(argv=None) -> int:
         from .undistort import undistort_for_cli
 
         data = undistort_for_cli(data, not args.no_undistort, dev)
-        ev = list(data.eval.views) if data.eval is not None else []
-        views = {"train": list(data.train.views), "eval": ev, "all": list(data.train.views) + ev}[args.views]
+        views = cli.chosen_views(data, args.views)
         if not views:
-            print(f"{args.dataset}: the dataset has no {args.views} views", file=sys.stderr)
-            return 2
+            return cli.no_views(args, args.views)
         scene = Scene(views)
         a = eval_stats(splats, scene, antialiased=args.antialiased)
         b = eval_stats(back, scene, antialiased=args.antialiased)
@@ -292,8 +278,7 @@ def main(argv=None) -> int:
         with open(args.export, "wb") as f:
             f.write(blob)
     if args.json:
-        with open(args.json, "w") as f:
-            json.dump(res, f, indent=1)
+        cli.write_json(args.json, res)
     return 0
 
 

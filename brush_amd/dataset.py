@@ -55,6 +55,10 @@ class DatasetFiles:
                 return "/".join(comps[:-len(parts)])
         return None
 
+    def names(self) -> List[str]:
+        """The relative paths of all files, sorted, with "/" between their parts."""
+        return list(self._names)
+
     def exists(self, path: str) -> bool:
         return path.lstrip("/") in self._names
 
@@ -550,6 +554,23 @@ def read_colmap(root: str, max_frames: Optional[int] = None, max_resolution: Opt
                 break
         (evals if eval_split_every is not None and i % eval_split_every == 0 else train).append(view)
     return Dataset.from_views(train, evals)
+
+
+def detect_format(root: str) -> str:
+    """'nerf' when the directory / zip holds a transforms_*.json, else 'colmap'."""
+    for n in DatasetFiles(root).names():
+        base = os.path.basename(n)
+        if base.startswith("transforms_") and base.endswith(".json"):
+            return "nerf"
+    return "colmap"
+
+
+def read_dataset(root: str, fmt: str = "auto", *, max_resolution: Optional[int] = None,
+                 eval_split_every: Optional[int] = None) -> Dataset:
+    """The Dataset of a directory or zip through the reader of `fmt` ('nerf', 'colmap', or 'auto': detect_format)."""
+    fmt = detect_format(root) if fmt == "auto" else fmt
+    reader = read_nerf_synthetic if fmt == "nerf" else read_colmap
+    return reader(root, max_resolution=max_resolution, eval_split_every=eval_split_every)
 
 
 def colmap_initial_points(root: str) -> Tuple[np.ndarray, np.ndarray]:

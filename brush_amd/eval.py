@@ -37,7 +37,8 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, cli
+from .dataset import detect_format  # noqa: F401  (its home is dataset.py; importable from here as before)
 
 
 def eval_metrics(pred: torch.Tensor, gt: torch.Tensor, window: int = 11,
@@ -142,42 +143,15 @@ def eval_stats(splats, scene, num_frames: Optional[int] = None, rng: Optional[np
     is the mean SSIM of the masked images as they are, zeroed pixels included: the blur mixes pixels across the mask's
     edge, so there is no exact per-pixel restriction of it.  With neither option in play the call is the one without
     them, launch for launch."""
-    from .pyramid import area_resize, check_factor
+    import math
+
+    from .compose import as_background, compose_forward
+    from .pyramid import check_factor
+    from .render import view_parts
 
     downscale = check_factor(downscale)
     views = scene.views
     idx = select_views(len(views), num_frames, rng)
-    dev = splats.means.device
-    if background is not None or (use_masks and any(getattr(views[i], "mask", None) is not None for i in idx)):
-        return _eval_stats_composed(splats, views, idx, window, keep_aux, antialiased, downscale, background, use_masks)
-    metrics = torch.empty((len(idx), 3), dtype=torch.float32, device=dev)
-    rendered = []
-    with torch.no_grad():
-        for row, i in enumerate(idx):
-            v = views[i]
-            img = np.require(v.image, requirements=["C", "W"])  # decoded images are read-only views: torch wants a copy
-            if img.ndim != 3 or img.dtype != np.uint8 or img.shape[2] not in (3, 4):
-                raise ValueError(f"{v.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
-            h, w = int(img.shape[0]), int(img.shape[1])
-            gt = torch.from_numpy(img).to(dev)  # u8, as the reference uploads to_rgb8() (the kernel divides by 255)
-            if downscale > 1:
-                gt = area_resize(gt, factor=downscale)
-                h, w = int(gt.shape[0]), int(gt.shape[1])
-            pred, aux = splats.render(v.camera, (w, h), False, antialiased=antialiased)
-            eval_metrics(pred, gt, window, out=metrics[row])
-            rendered.append((pred[..., :3], aux if keep_aux else None))
-    host = metrics.cpu().numpy()  # the one readback
-    return EvalStats([EvalView(views[i], r, float(host[k, 1]), float(host[k, 2]), a)
-                      for k, (i, (r, a)) in enumerate(zip(idx, rendered))])
-
-
-def _eval_stats_composed(splats, views, idx, window, keep_aux, antialiased, downscale, background, use_masks):
-    """eval_stats with a background and / or masked views (its docstring has the definition)."""
-    import math
-
-    from .compose import as_background, compose_forward
-    from .pyramid import area_resize, nearest_resize
-
     dev = splats.means.device
     if isinstance(background, str) and background == "random":
         raise ValueError("an eval has no 'random' background: score over a fixed colour")
@@ -189,25 +163,11 @@ def _eval_stats_composed(splats, views, idx, window, keep_aux, antialiased, down
     rendered = []
     with torch.no_grad():
         for row, i in enumerate(idx):
-            v = views[i]
-            img = np.require(v.image, requirements=["C", "W"])
-            if img.ndim != 3 or img.dtype != np.uint8 or img.shape[2] not in (3, 4):
-                raise ValueError(f"{v.name}: the view's image must be uint8 [h,w,3|4], got {img.dtype} {img.shape}")
-            gt = torch.from_numpy(img).to(dev)
-            mask = getattr(v, "mask", None) if use_masks else None
-            if mask is not None:
-                if mask.dtype != np.uint8 or tuple(mask.shape) != tuple(img.shape[:2]):
-                    raise ValueError(f"{v.name}: the view's mask must be uint8 [h,w] = {tuple(img.shape[:2])}, got "
-                                     f"{mask.dtype} {mask.shape}")
-                mask = torch.from_numpy(np.array(mask, copy=True, order="C")).to(dev)
-            if downscale > 1:
-                gt = area_resize(gt, factor=downscale)
-                if mask is not None:
-                    mask = nearest_resize(mask.to(torch.int16).view(torch.uint16),
-                                          factor=downscale).view(torch.int16).to(torch.uint8)
+            # the image as u8, as the reference uploads to_rgb8() (the kernel divides by 255)
+            camera, _, gt, mask = view_parts(views[i], dev, downscale=downscale, gt=True, mask=use_masks)
             h, w = int(gt.shape[0]), int(gt.shape[1])
-            pred, aux = splats.render(v.camera, (w, h), False, antialiased=antialiased)
-            if bg is None and mask is None:  # a plain view among masked ones
+            pred, aux = splats.render(camera, (w, h), False, antialiased=antialiased)
+            if bg is None and mask is None:  # a plain view, possibly among masked ones
                 eval_metrics(pred, gt, window, out=metrics[row])
                 shown = pred
             else:
@@ -217,7 +177,7 @@ def _eval_stats_composed(splats, views, idx, window, keep_aux, antialiased, down
                 kept[row] = torch.count_nonzero(mask)
                 pixels[row] = h * w
             rendered.append((shown[..., :3], aux if keep_aux else None))
-    host = metrics.cpu().numpy()  # the read-back of the metrics
+    host = metrics.cpu().numpy()  # the one read-back without masks
     host_kept = kept.cpu().numpy() if masked else None  # the one further read-back
     samples = []
     for k, (i, (r, a)) in enumerate(zip(idx, rendered)):
@@ -271,31 +231,41 @@ def eval_depth(splats, scene, *, mode: str = "depth", alpha_min: float = 0.5,
             for k, v in enumerate(views)]
 
 
-def write_depth_maps(splats, views, out_dir: str, median: bool = False):
-    """For each view: <stem>_depth.npy, the accumulated depth D = sum T alpha z (Splats.render_depth), and
-    <stem>_depth_norm.npy, D / max(alpha, 1e-6) with 0 where alpha is 0; both f32 [h,w].  `median`: also
-    <stem>_depth_median.npy, the median depth at level 0.5 (Splats.render_median_depth; 0 where alpha < 0.5).  Returns
-    the written paths."""
+def _write_maps(views, out_dir: str, render, save=None):
+    """The loop of the writers below: under no_grad, for each view, `render(camera, (w, h))` at the size of the view's
+    image gives pairs (suffix, device tensor), and each tensor is written to out_dir/<stem of the view's name><suffix>
+    by `save(path, tensor)` (None: np.save as float32).  Returns the written paths."""
     import os
 
+    if save is None:
+        save = lambda path, t: np.save(path, t.cpu().numpy().astype(np.float32))
     os.makedirs(out_dir, exist_ok=True)
     paths = []
     with torch.no_grad():
         for v in views:
             h, w = int(v.image.shape[0]), int(v.image.shape[1])
-            if median:
-                img, depth, med, _, _ = splats.render_median_depth(v.camera, (w, h))
-            else:
-                img, depth, _ = splats.render_depth(v.camera, (w, h))
-            alpha = img[..., 3]
-            norm = torch.where(alpha > 0, depth / torch.clamp(alpha, min=1e-6), torch.zeros_like(depth))
             stem = os.path.splitext(os.path.basename(v.name))[0]
-            maps = (("_depth.npy", depth), ("_depth_norm.npy", norm)) + ((("_depth_median.npy", med),) if median else ())
-            for suffix, t in maps:
-                path = os.path.join(out_dir, stem + suffix)
-                np.save(path, t.cpu().numpy().astype(np.float32))
-                paths.append(path)
+            for suffix, t in render(v.camera, (w, h)):
+                paths.append(os.path.join(out_dir, stem + suffix))
+                save(paths[-1], t)
     return paths
+
+
+def write_depth_maps(splats, views, out_dir: str, median: bool = False):
+    """For each view: <stem>_depth.npy, the accumulated depth D = sum T alpha z (Splats.render_depth), and
+    <stem>_depth_norm.npy, D / max(alpha, 1e-6) with 0 where alpha is 0; both f32 [h,w].  `median`: also
+    <stem>_depth_median.npy, the median depth at level 0.5 (Splats.render_median_depth; 0 where alpha < 0.5).  Returns
+    the written paths."""
+    def render(camera, size):
+        if median:
+            img, depth, med, _, _ = splats.render_median_depth(camera, size)
+        else:
+            img, depth, _ = splats.render_depth(camera, size)
+        alpha = img[..., 3]
+        norm = torch.where(alpha > 0, depth / torch.clamp(alpha, min=1e-6), torch.zeros_like(depth))
+        return (("_depth.npy", depth), ("_depth_norm.npy", norm)) + ((("_depth_median.npy", med),) if median else ())
+
+    return _write_maps(views, out_dir, render)
 
 
 def write_normal_maps(splats, views, out_dir: str, antialiased: bool = False):
@@ -303,44 +273,26 @@ def write_normal_maps(splats, views, out_dir: str, antialiased: bool = False):
     alpha >= 0.5, 0 elsewhere, and <stem>_normal_depth.npy, the normals the rendered depth map implies
     (normal_loss.depth_normals, alpha_min 0.5; 0 where invalid); both f32 [h,w,3], camera space.  Returns the written
     paths."""
-    import os
-
     from .normal_loss import depth_normals
 
-    os.makedirs(out_dir, exist_ok=True)
-    paths = []
-    with torch.no_grad():
-        for v in views:
-            h, w = int(v.image.shape[0]), int(v.image.shape[1])
-            img, depth, nimg, _ = splats.render_normals(v.camera, (w, h), antialiased=antialiased)
-            length = torch.sqrt((nimg * nimg).sum(dim=2, keepdim=True))
-            keep = (img[..., 3:4] >= 0.5) & (length > 0)
-            unit = torch.where(keep, nimg / torch.where(keep, length, torch.ones_like(length)), torch.zeros_like(nimg))
-            from_depth, _ = depth_normals(v.camera, (w, h), img, depth, alpha_min=0.5)
-            stem = os.path.splitext(os.path.basename(v.name))[0]
-            for suffix, t in (("_normal.npy", unit), ("_normal_depth.npy", from_depth)):
-                path = os.path.join(out_dir, stem + suffix)
-                np.save(path, t.cpu().numpy().astype(np.float32))
-                paths.append(path)
-    return paths
+    def render(camera, size):
+        img, depth, nimg, _ = splats.render_normals(camera, size, antialiased=antialiased)
+        length = torch.sqrt((nimg * nimg).sum(dim=2, keepdim=True))
+        keep = (img[..., 3:4] >= 0.5) & (length > 0)
+        unit = torch.where(keep, nimg / torch.where(keep, length, torch.ones_like(length)), torch.zeros_like(nimg))
+        from_depth, _ = depth_normals(camera, size, img, depth, alpha_min=0.5)
+        return ("_normal.npy", unit), ("_normal_depth.npy", from_depth)
+
+    return _write_maps(views, out_dir, render)
 
 
 def write_distortion_maps(splats, views, out_dir: str, antialiased: bool = False):
     """For each view: <stem>_distortion.npy, the depth-distortion map sum w_i w_j (z_i - z_j)^2 of the view
     (Splats.render_distortion, mode "depth"), f32 [h,w].  Returns the written paths."""
-    import os
+    def render(camera, size):
+        return (("_distortion.npy", splats.render_distortion(camera, size, antialiased=antialiased)[2]),)
 
-    os.makedirs(out_dir, exist_ok=True)
-    paths = []
-    with torch.no_grad():
-        for v in views:
-            h, w = int(v.image.shape[0]), int(v.image.shape[1])
-            _, _, dist, _ = splats.render_distortion(v.camera, (w, h), antialiased=antialiased)
-            stem = os.path.splitext(os.path.basename(v.name))[0]
-            path = os.path.join(out_dir, stem + "_distortion.npy")
-            np.save(path, dist.cpu().numpy().astype(np.float32))
-            paths.append(path)
-    return paths
+    return _write_maps(views, out_dir, render)
 
 
 def zoomed_camera(camera, img_size, zoom: float):
@@ -359,54 +311,23 @@ def write_zoomed_renders(splats, views, zoom: float, out_dir: str, antialiased: 
     """For each view: <stem>_zoom<zoom>.png, the view rendered through zoomed_camera at its own size, composed over
     `background` (an (r, g, b) tuple, "white" or "black"; None: black) and written as 8-bit RGB.  There is no ground
     truth for a zoom-in, so nothing is scored: the images are for inspection.  Returns the written paths."""
-    import os
-
     from PIL import Image
 
     from .compose import check_background
 
     bg = check_background(background)
     rgb = {None: (0.0, 0.0, 0.0), "black": (0.0, 0.0, 0.0), "white": (1.0, 1.0, 1.0)}.get(bg, bg)
-    os.makedirs(out_dir, exist_ok=True)
-    paths = []
-    with torch.no_grad():
-        for v in views:
-            h, w = int(v.image.shape[0]), int(v.image.shape[1])
-            img, _ = splats.render(zoomed_camera(v.camera, (w, h), zoom), (w, h), antialiased=antialiased)
-            colour = torch.tensor(rgb, dtype=torch.float32, device=img.device)
-            out = img[..., :3] + (1.0 - img[..., 3:4]) * colour
-            u8 = torch.clamp(torch.round(out * 255.0), 0, 255).to(torch.uint8).cpu().numpy()
-            stem = os.path.splitext(os.path.basename(v.name))[0]
-            path = os.path.join(out_dir, f"{stem}_zoom{zoom:g}.png")
-            Image.fromarray(u8).save(path)
-            paths.append(path)
-    return paths
+
+    def render(camera, size):
+        img, _ = splats.render(zoomed_camera(camera, size, zoom), size, antialiased=antialiased)
+        colour = torch.tensor(rgb, dtype=torch.float32, device=img.device)
+        out = img[..., :3] + (1.0 - img[..., 3:4]) * colour
+        return ((f"_zoom{zoom:g}.png", torch.clamp(torch.round(out * 255.0), 0, 255).to(torch.uint8)),)
+
+    return _write_maps(views, out_dir, render, save=lambda path, u8: Image.fromarray(u8.cpu().numpy()).save(path))
 
 
 # ---------------------------------------------------------------------------- command line
-def detect_format(dataset: str) -> str:
-    """'nerf' when the directory / zip holds a transforms_*.json, else 'colmap'."""
-    import os
-
-    from .dataset import DatasetFiles
-
-    files = DatasetFiles(dataset)
-    names = files._names
-    for n in names:
-        base = os.path.basename(n)
-        if base.startswith("transforms_") and base.endswith(".json"):
-            return "nerf"
-    return "colmap"
-
-
-def _load_dataset(args):
-    from . import dataset as D
-
-    fmt = detect_format(args.dataset) if args.format == "auto" else args.format
-    reader = D.read_nerf_synthetic if fmt == "nerf" else D.read_colmap
-    return reader(args.dataset, max_resolution=args.max_resolution, eval_split_every=args.eval_split_every)
-
-
 def parser():
     import argparse
 
@@ -414,13 +335,11 @@ def parser():
                                 description="PSNR / SSIM of a splat file on a dataset's eval views")
     p.add_argument("splats", help=".ply or .safetensors splat file")
     p.add_argument("dataset", help="dataset directory or .zip (NeRF-synthetic or COLMAP)")
-    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
-    p.add_argument("--eval-split-every", type=int, default=None)
-    p.add_argument("--max-resolution", type=int, default=None)
+    cli.add_dataset_options(p)
     p.add_argument("--num-frames", type=int, default=None)
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--window", type=int, default=11)
-    p.add_argument("--json", default=None, help="also write the results to this file")
+    cli.add_json_option(p)
     p.add_argument("--depth-dir", default=None,
                    help="also write every eval view's accumulated depth D (<view stem>_depth.npy, f32 [h,w]) and "
                         "D / alpha (<view stem>_depth_norm.npy, 0 where alpha is 0) to this directory")
@@ -434,9 +353,7 @@ def parser():
                    help="also write every eval view's rendered normal map (<view stem>_normal.npy, unit where alpha >= "
                         "0.5, else 0) and the normals its depth map implies (<view stem>_normal_depth.npy) to this "
                         "directory, f32 [h,w,3] in camera space")
-    p.add_argument("--antialiased", action="store_true",
-                   help="render in the antialiased mode (opacity compensation of the 2D blur), e.g. for splats "
-                        "trained with it")
+    cli.add_antialiased_option(p)
     p.add_argument("--depth-metrics", action="store_true",
                    help="also score the rendered depth of every eval view that has a depth map: mean absolute error "
                         "over the valid pixels and the valid fraction (eval_depth)")
@@ -455,9 +372,6 @@ def parser():
                         "principal point) and write the images for inspection; a zoom-in has no ground truth, so "
                         "nothing is scored (metrics across scales: --downscale)")
     p.add_argument("--image-dir", default=None, metavar="DIR", help="--zoom: where the zoomed renders go")
-    p.add_argument("--no-undistort", action="store_true",
-                   help="score views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
-                        "loaded, as if they were pinhole, instead of undistorting them first")
     return p
 
 
@@ -472,7 +386,6 @@ def parse_scales(text: str) -> List[int]:
 
 
 def main(argv=None) -> int:
-    import json
     import os
     import sys
 
@@ -502,20 +415,15 @@ def main(argv=None) -> int:
     if args.zoom is not None and not (args.zoom > 0 and args.zoom < float("inf")):
         p.error("--zoom must be a positive factor")
 
-    data = _load_dataset(args)  # before any GPU work
-    if data.eval is None or not data.eval.views:
+    data = cli.read_args_dataset(args)  # before any GPU work
+    if not cli.chosen_views(data, "eval"):
         print(f"{args.dataset}: the dataset has no eval views (try --eval-split-every K)", file=sys.stderr)
         return 2
-    from .gaussian_splats import Splats
-
-    dev = torch.device("cuda", torch.cuda.current_device())
     from .undistort import undistort_for_cli
 
+    dev = cli.cuda_device()
     data = undistort_for_cli(data, not args.no_undistort, dev)
-    if args.splats.endswith(".safetensors"):
-        splats = Splats.from_safetensors(args.splats, dev)
-    else:
-        splats = Splats.from_ply(args.splats, dev)
+    splats = cli.load_splats(args.splats, dev)
     rng = np.random.default_rng(args.seed)
     scale_rows = None
     if scales is None:
@@ -573,8 +481,7 @@ def main(argv=None) -> int:
                                    "valid_fraction": r.valid_fraction} for r in depth_rows]
             res["mean_depth_abs_error"] = (float(np.mean([r.mean_abs_error for r in depth_rows])) if depth_rows
                                            else float("nan"))
-        with open(args.json, "w") as f:
-            json.dump(res, f, indent=1)
+        cli.write_json(args.json, res)
     return 0
 
 

@@ -21,6 +21,8 @@ from __future__ import annotations
 
 import os
 
+from . import cli
+
 IGNORE = 255
 
 
@@ -34,23 +36,17 @@ def parser():
     p.add_argument("--labels", required=True, metavar="DIR", help="directory of 8-bit single-channel label PNGs")
     p.add_argument("--num-classes", type=int, default=None, metavar="K",
                    help="class ids are 0..K-1 (default: the largest id found below 255, plus one); at most 64")
-    p.add_argument("--views", choices=("train", "eval", "all"), default="train", help="the views that vote")
-    p.add_argument("--antialiased", action="store_true", help="render in the antialiased mode")
-    p.add_argument("--no-undistort", action="store_true",
-                   help="use views with lens distortion as loaded, as if they were pinhole")
+    cli.add_views_option(p, "train", "the views that vote")
+    cli.add_antialiased_option(p)
     p.add_argument("--min-weight", type=float, default=0.0, metavar="W",
                    help="a splat whose best class received no more than W pixels of full weight stays unlabelled (-1)")
     p.add_argument("--export-labels", default=None, metavar="OUT.npy", help="write the int32 [N] labels")
     p.add_argument("--select", type=int, default=None, metavar="CLASS", help="with --export: the class to cut out")
-    p.add_argument("--export", default=None, metavar="OUT.ply",
-                   help="write the splats of --select to this .ply (a name ending in .compressed.ply: the "
-                        "chunk-quantised layout)")
+    cli.add_export_option(p, "the splats of --select", metavar="OUT.ply")
     p.add_argument("--render-dir", default=None, metavar="DIR",
                    help="write the rendered label image of every eval view here")
-    p.add_argument("--json", default=None, metavar="OUT.json", help="also write the results to this file")
-    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
-    p.add_argument("--eval-split-every", type=int, default=None)
-    p.add_argument("--max-resolution", type=int, default=None)
+    cli.add_json_option(p, metavar="OUT.json")
+    cli.add_dataset_options(p)
     return p
 
 
@@ -124,7 +120,6 @@ def labels_of(view):
 
 
 def main(argv=None) -> int:
-    import json
     import sys
 
     p = parser()
@@ -137,25 +132,21 @@ def main(argv=None) -> int:
     import torch
 
     from .dataset import Dataset
-    from .eval import _load_dataset
     from .features import lift_labels
-    from .gaussian_splats import Splats
     from .undistort import undistort_for_cli
 
-    data = _load_dataset(args)  # before any GPU work
-    has_eval = data.eval is not None and bool(data.eval.views)
+    data = cli.read_args_dataset(args)  # before any GPU work
+    has_eval = bool(cli.chosen_views(data, "eval"))
     try:
-        train = with_labels_as_masks(data.train.views, args.labels) if args.views in ("train", "all") else []
-        evals = with_labels_as_masks(data.eval.views, args.labels) if has_eval and args.views in ("eval", "all") else []
+        voting = with_labels_as_masks(cli.chosen_views(data, args.views), args.labels)
     except ValueError as e:
         print(str(e), file=sys.stderr)
         return 2
-    if not train + evals:
-        print(f"{args.dataset}: the dataset has no {args.views} views", file=sys.stderr)
-        return 2
-    dev = torch.device("cuda", torch.cuda.current_device())
+    if not voting:
+        return cli.no_views(args, args.views)
+    dev = cli.cuda_device()
     # the voting views, labels in the mask field, through the same undistortion as every command line applies
-    voting = undistort_for_cli(Dataset.from_views(train + evals, []), not args.no_undistort, dev).train.views
+    voting = undistort_for_cli(Dataset.from_views(voting, []), not args.no_undistort, dev).train.views
     label_maps = [labels_of(v) for v in voting]
     k = args.num_classes
     if k is None:
@@ -163,7 +154,7 @@ def main(argv=None) -> int:
         if k > 64:
             print(f"the label images hold class ids up to {k - 1}: at most 64 classes, remap them", file=sys.stderr)
             return 2
-    splats = (Splats.from_safetensors if args.splats.endswith(".safetensors") else Splats.from_ply)(args.splats, dev)
+    splats = cli.load_splats(args.splats, dev)
     labels, sums = lift_labels(splats, voting, label_maps, k, min_weight=args.min_weight, antialiased=args.antialiased,
                                use_masks=False)  # (the loss masks are already in the labels)
     got = labels.cpu().numpy()
@@ -177,10 +168,7 @@ def main(argv=None) -> int:
     if args.export_labels:
         np.save(args.export_labels, got.astype(np.int32))
     if args.export:
-        from .compress import ply_bytes_for  # OUT.compressed.ply: the compressed layout
-
-        with open(args.export, "wb") as f:
-            f.write(ply_bytes_for(splats.select(labels == args.select), args.export))
+        cli.export_splats(args.export, splats.select(labels == args.select))
     rendered = 0
     if args.render_dir and has_eval:
         from PIL import Image
@@ -204,8 +192,7 @@ def main(argv=None) -> int:
                "num_splats": splats.num_splats(), "unlabelled": int((got < 0).sum()),
                "classes": [{"class": c, "splats": counts[c], "weight": weights[c]} for c in range(k)],
                "rendered_views": rendered}
-        with open(args.json, "w") as f:
-            json.dump(res, f, indent=1)
+        cli.write_json(args.json, res)
     return 0
 
 

@@ -21,6 +21,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import cli
+
 
 @dataclass
 class Mesh:
@@ -153,8 +155,8 @@ def parser():
     p.add_argument("--alpha-min", type=float, default=0.5, help="use pixels whose rendered alpha is at least this")
     p.add_argument("--max-depth", type=float, default=None, metavar="D", help="ignore pixels deeper than this")
     p.add_argument("--min-views", type=int, default=2, help="mesh only voxels that at least this many views observed")
-    p.add_argument("--views", choices=("train", "eval", "all"), default="train", help="the views to fuse")
-    p.add_argument("--antialiased", action="store_true", help="render in the antialiased mode")
+    cli.add_views_option(p, "train", "the views to fuse")
+    cli.add_antialiased_option(p)
     p.add_argument("--no-masks", action="store_true", help="ignore the dataset's loss masks")
     p.add_argument("--depth", choices=("expected", "median"), default="expected",
                    help="the depth to fuse: the expected depth D / alpha, or the median depth (the splat at which the "
@@ -162,12 +164,8 @@ def parser():
     p.add_argument("--median-level", type=float, default=0.5, metavar="L",
                    help="--depth median: the accumulated opacity at which the depth is taken, 0 < L < 1")
     p.add_argument("--export", default=None, metavar="OUT.ply", help="write the mesh to this .ply")
-    p.add_argument("--json", default=None, metavar="OUT.json", help="also write the numbers to this file")
-    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
-    p.add_argument("--eval-split-every", type=int, default=None)
-    p.add_argument("--max-resolution", type=int, default=None)
-    p.add_argument("--no-undistort", action="store_true",
-                   help="use views with lens distortion as loaded, as if they were pinhole")
+    cli.add_json_option(p, metavar="OUT.json")
+    cli.add_dataset_options(p)
     return p
 
 
@@ -210,9 +208,7 @@ def plan_from_args(args) -> dict:
 
 
 def main(argv=None) -> int:
-    import json
     import os
-    import sys
 
     p = parser()
     args = p.parse_args(argv)
@@ -220,27 +216,13 @@ def main(argv=None) -> int:
         plan = plan_from_args(args)
     except ValueError as e:
         p.error(str(e))
-    import torch
-
-    from .eval import _load_dataset
-    from .gaussian_splats import Splats
-    from .tsdf import TsdfVolume
-    from .undistort import undistort_for_cli
-
-    data = _load_dataset(args)  # before any GPU work
-    has_eval = data.eval is not None and bool(data.eval.views)
-
-    def chosen(d):
-        ev = list(d.eval.views) if has_eval else []
-        return {"train": list(d.train.views), "eval": ev, "all": list(d.train.views) + ev}[args.views]
-
-    if not chosen(data):
-        print(f"{args.dataset}: the dataset has no {args.views} views", file=sys.stderr)
+    got = cli.dataset_views(args, args.views)  # host work and the refusals first
+    if got is None:
         return 2
-    dev = torch.device("cuda", torch.cuda.current_device())
-    data = undistort_for_cli(data, not args.no_undistort, dev)
-    views = chosen(data)  # distorted views have become pinhole views
-    splats = (Splats.from_safetensors if args.splats.endswith(".safetensors") else Splats.from_ply)(args.splats, dev)
+    from .tsdf import TsdfVolume
+
+    _, views, dev = got
+    splats = cli.load_splats(args.splats, dev)
     grid = plan["grid"]
     if grid is None:
         try:
@@ -271,8 +253,7 @@ def main(argv=None) -> int:
                "use_masks": not args.no_masks, "alpha_min": args.alpha_min, "max_depth": args.max_depth,
                "min_views": args.min_views, "depth": args.depth, "median_level": args.median_level,
                "observed_fraction": observed, "vertices": nv, "faces": nf}
-        with open(args.json, "w") as f:
-            json.dump(res, f, indent=1)
+        cli.write_json(args.json, res)
     return 0
 
 

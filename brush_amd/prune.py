@@ -12,6 +12,8 @@ SSIM (eval_stats) before and after.  --json holds the same numbers plus the hist
 """
 from __future__ import annotations
 
+from . import cli
+
 
 def parser():
     import argparse
@@ -26,18 +28,11 @@ def parser():
     p.add_argument("--keep-fraction", type=float, default=None, metavar="F",
                    help="instead: keep the ceil(F N) splats that rank highest by --by")
     p.add_argument("--by", choices=("max", "sum"), default="max", help="--keep-fraction: the ranking key")
-    p.add_argument("--views", choices=("train", "eval", "all"), default="train",
-                   help="the views the contribution is measured over")
-    p.add_argument("--antialiased", action="store_true", help="render in the antialiased mode")
-    p.add_argument("--export", default=None, metavar="OUT.ply",
-                   help="write the kept splats to this .ply (a name ending in .compressed.ply: the chunk-quantised "
-                        "layout)")
-    p.add_argument("--json", default=None, metavar="OUT.json", help="also write the results to this file")
-    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
-    p.add_argument("--eval-split-every", type=int, default=None)
-    p.add_argument("--max-resolution", type=int, default=None)
-    p.add_argument("--no-undistort", action="store_true",
-                   help="use views with lens distortion as loaded, as if they were pinhole")
+    cli.add_views_option(p, "train", "the views the contribution is measured over")
+    cli.add_antialiased_option(p)
+    cli.add_export_option(p, "the kept splats", metavar="OUT.ply")
+    cli.add_json_option(p, metavar="OUT.json")
+    cli.add_dataset_options(p)
     return p
 
 
@@ -57,9 +52,7 @@ def rule_from_args(args) -> dict:
 
 
 def main(argv=None) -> int:
-    import json
     import os
-    import sys
 
     p = parser()
     args = p.parse_args(argv)
@@ -67,27 +60,15 @@ def main(argv=None) -> int:
         rule = rule_from_args(args)
     except ValueError as e:
         p.error(str(e))
-    import torch
-
-    from .contribution import max_histogram, prune_mask, splat_contributions
-    from .eval import _load_dataset, eval_stats
-    from .gaussian_splats import Splats
-    from .undistort import undistort_for_cli
-
-    data = _load_dataset(args)  # before any GPU work
-    has_eval = data.eval is not None and bool(data.eval.views)
-
-    def chosen(d):
-        ev = list(d.eval.views) if has_eval else []
-        return {"train": list(d.train.views), "eval": ev, "all": list(d.train.views) + ev}[args.views]
-
-    if not chosen(data):
-        print(f"{args.dataset}: the dataset has no {args.views} views", file=sys.stderr)
+    got = cli.dataset_views(args, args.views)  # host work and the refusals first
+    if got is None:
         return 2
-    dev = torch.device("cuda", torch.cuda.current_device())
-    data = undistort_for_cli(data, not args.no_undistort, dev)
-    views = chosen(data)  # distorted views have become pinhole views
-    splats = (Splats.from_safetensors if args.splats.endswith(".safetensors") else Splats.from_ply)(args.splats, dev)
+    from .contribution import max_histogram, prune_mask, splat_contributions
+    from .eval import eval_stats
+
+    data, views, dev = got
+    has_eval = bool(cli.chosen_views(data, "eval"))
+    splats = cli.load_splats(args.splats, dev)
 
     def score(s):
         if not has_eval:
@@ -105,17 +86,13 @@ def main(argv=None) -> int:
         print(f"eval ({before['views']} views)\tpsnr {before['psnr']:.4f} -> {after['psnr']:.4f}\t"
               f"ssim {before['ssim']:.6f} -> {after['ssim']:.6f}")
     if args.export:
-        from .compress import ply_bytes_for  # OUT.compressed.ply: the compressed layout
-
-        with open(args.export, "wb") as f:
-            f.write(ply_bytes_for(kept, args.export))
+        cli.export_splats(args.export, kept)
     if args.json:
         res = {"splats": os.path.abspath(args.splats), "dataset": os.path.abspath(args.dataset), "rule": rule,
                "views": args.views, "num_views": len(views), "antialiased": bool(args.antialiased),
                "splats_before": n0, "splats_after": n1, "eval_before": before, "eval_after": after,
                "max_histogram": max_histogram(c)}
-        with open(args.json, "w") as f:
-            json.dump(res, f, indent=1)
+        cli.write_json(args.json, res)
     return 0
 
 

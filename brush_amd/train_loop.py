@@ -96,6 +96,7 @@ from typing import Callable, List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import cli
 from .dataset import Dataset
 from .gaussian_splats import Splats
 from .scene_loader import SceneLoader
@@ -170,13 +171,10 @@ def _colmap_points(root: str) -> Optional[Tuple[np.ndarray, np.ndarray]]:
 def load_dataset(root: str, fmt: str = "auto", max_resolution: Optional[int] = None,
                  eval_split_every: Optional[int] = None):
     """(Dataset, COLMAP SfM points or None) of a dataset directory or zip; host only (no device work)."""
-    import argparse
-
-    from .eval import _load_dataset, detect_format
+    from .dataset import detect_format, read_dataset
 
     fmt = detect_format(root) if fmt == "auto" else fmt
-    data = _load_dataset(argparse.Namespace(dataset=root, format=fmt, max_resolution=max_resolution,
-                                            eval_split_every=eval_split_every))
+    data = read_dataset(root, fmt, max_resolution=max_resolution, eval_split_every=eval_split_every)
     return data, (_colmap_points(root) if fmt == "colmap" else None)
 
 
@@ -507,21 +505,16 @@ def parser():
                                 description="train splats on a dataset (NeRF-synthetic or COLMAP)")
     p.add_argument("dataset", help="dataset directory or .zip")
     p.add_argument("--steps", type=int, default=30000)
-    p.add_argument("--format", choices=("auto", "nerf", "colmap"), default="auto")
-    p.add_argument("--max-resolution", type=int, default=None)
-    p.add_argument("--eval-split-every", type=int, default=None)
+    cli.add_dataset_options(p)
     p.add_argument("--eval-every", type=int, default=0, help="eval every N steps (0: never)")
     p.add_argument("--eval-views", type=int, default=None, help="eval views per eval (default: all)")
     p.add_argument("--init", default=None, help="start from this .ply instead of the dataset's points / random splats")
     p.add_argument("--init-count", type=int, default=10000, help="random initial splats when there are no points")
     p.add_argument("--sh-degree", type=int, default=3)
     p.add_argument("--seed", type=int, default=42)
-    p.add_argument("--export", default=None,
-                   help="write the trained splats to this .ply (a name ending in .compressed.ply: the "
-                        "chunk-quantised layout, brush_amd/compress.py)")
-    p.add_argument("--json", default=None, help="write the eval rows and the loss curve to this file")
-    p.add_argument("--antialiased", action="store_true",
-                   help="train (and evaluate) in the antialiased mode: opacity compensation of the 2D blur")
+    cli.add_export_option(p, "the trained splats")
+    cli.add_json_option(p, help="write the eval rows and the loss curve to this file")
+    cli.add_antialiased_option(p, "train (and evaluate) in the antialiased mode: opacity compensation of the 2D blur")
     p.add_argument("--pose-opt", action="store_true",
                    help="refine the training views' camera poses beside the splats (eval views are rendered as given)")
     p.add_argument("--export-cameras", default=None, metavar="FILE.json",
@@ -596,14 +589,10 @@ def parser():
                    help="--densify-by error: never grow beyond this many splats")
     p.add_argument("--revised-opacity", action="store_true",
                    help="give the two splats a clone or split leaves the opacity 1 - sqrt(1 - o) of their source")
-    p.add_argument("--no-undistort", action="store_true",
-                   help="train on views with lens distortion (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) as "
-                        "loaded, as if they were pinhole, instead of undistorting them first")
     return p
 
 
 def main(argv=None) -> int:
-    import json
     import os
     import sys
 
@@ -653,11 +642,11 @@ def main(argv=None) -> int:
     if args.depth_weight > 0 and not any(v.depth is not None for v in data.train.views):
         print(f"{args.dataset}: --depth-weight needs training views with depth maps", file=sys.stderr)
         return 2
-    if args.eval_every > 0 and (data.eval is None or not data.eval.views):
+    if args.eval_every > 0 and not cli.chosen_views(data, "eval"):
         print(f"{args.dataset}: --eval-every needs eval views (try --eval-split-every K)", file=sys.stderr)
         return 2
 
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = cli.cuda_device()
     from .undistort import undistort_for_cli
 
     data = undistort_for_cli(data, not args.no_undistort, dev)  # distorted views become pinhole views, once
@@ -691,19 +680,14 @@ def main(argv=None) -> int:
     print(f"done: {log.steps} steps in {log.seconds:.1f} s ({rate:.1f} it/s), {log.num_splats} splats, "
           f"final loss {final:.6f}, {log.image_bytes / 1e6:.1f} MB of images on the device")
     if args.export:
-        from .compress import ply_bytes_for  # OUT.compressed.ply: the compressed layout
-
-        with open(args.export, "wb") as f:
-            f.write(ply_bytes_for(splats, args.export))
+        cli.export_splats(args.export, splats)
     if args.export_cameras:
-        with open(args.export_cameras, "w") as f:
-            json.dump({"pose_opt": bool(args.pose_opt), "cameras": cameras}, f, indent=1)
+        cli.write_json(args.export_cameras, {"pose_opt": bool(args.pose_opt), "cameras": cameras})
     if args.export_exposures:
         if not args.exposure_opt:
             exposures.extend({"name": v.name, "exposure": [[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0],
                                                            [0.0, 0.0, 1.0, 0.0]]} for v in data.train.views)
-        with open(args.export_exposures, "w") as f:
-            json.dump({"exposure_opt": bool(args.exposure_opt), "views": exposures}, f, indent=1)
+        cli.write_json(args.export_exposures, {"exposure_opt": bool(args.exposure_opt), "views": exposures})
     if args.export_bilagrids:
         from .bilagrid import bilagrid_identity
 
@@ -719,8 +703,7 @@ def main(argv=None) -> int:
                "densify_error_views": int(args.densify_error_views), "densify_growth": float(args.densify_growth),
                "max_splats": args.max_splats, "revised_opacity": bool(args.revised_opacity)}
         res.update(log.to_json())
-        with open(args.json, "w") as f:
-            json.dump(res, f, indent=1)
+        cli.write_json(args.json, res)
     return 0
 
 

@@ -460,6 +460,9 @@ def test_eval_over_white_and_with_masks(dev, deterministic, nerf_scene):
                 assert s.psnr == 10.0 * math.log10(f / float(met[0]))        # PSNR over the kept pixels
                 assert s.psnr < 10.0 * math.log10(1.0 / float(met[0]))
             assert np.float32(s.ssim).view(np.uint32) == met[2].view(np.uint32)  # the masked images as they are
+    # the plain view among masked ones is scored as the plain call over it alone scores it
+    among, alone = eval_stats(splats, scene).samples[3], eval_stats(splats, D.Scene([views[3]])).samples[0]
+    assert (among.psnr, among.ssim, among.valid_fraction) == (alone.psnr, alone.ssim, 1.0)
     # use_masks=False and no background: today's call
     off = eval_stats(splats, scene, use_masks=False)
     assert [(s.psnr, s.ssim, s.valid_fraction) for s in off.samples] == [(p.psnr, p.ssim, 1.0) for p in plain.samples]

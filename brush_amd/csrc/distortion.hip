@@ -2,7 +2,7 @@
 // reference renders colour only) through the compositing walk, both ways.  Two kernels, both replays of a FINISHED
 // brush_render_forward_depth's walk over the tile lists it left in the aux (replay_walk.hpp), and their launchers; the
 // ABI entries are brush_render_distortion and brush_distortion_compact_grads here and brush_render_backward_distortion
-// in render.hip.
+// in render_bwd.hip.
 //
 // Definitions.  Per pixel p a "hit" is an entry the forward added: the walk of replay_walk.hpp exactly (the 0.999 clamp,
 // the 1/255 test, the `next_T <= 1e-4` stop WITHOUT adding).  The hits i = 1..n in list order have

@@ -56,16 +56,28 @@ hipError_t tile_sort_launch(const uint32_t *keys_in, const uint32_t *vals_in, ui
                             uint32_t num_tiles);
 
 // rasterize.hip (forward), rasterize_bwd.hip (backward, zero-fill); raster_common.hpp, raster_zero_fill.hpp
+// What both compositing launches take from (uniforms, aux): the frame and the tile lists of one render
+// (render_host.hpp: raster_frame).  The forward writes tile_bins and final_index, the backward reads them.
+struct RasterFrame {
+    uint32_t w, h, tbx, tby;
+    const uint32_t *compact_gid_from_isect;
+    uint32_t *tile_bins;
+    const float *projected;
+    uint32_t *final_index;
+};
+// The forward's image and its optional depth outputs (brush_render_forward_depth: both or neither, float image only).
+struct RasterOut {
+    int raster_u32;              // img: packed rgba8 words, rows u32_pitch pixels apart; else [h][w] float4
+    uint32_t u32_pitch;
+    void *img;
+    const float *compact_depth;  // [n] z, compact order
+    float *out_depth;            // [h][w]: accumulated depth
+};
 // bin_edges != nullptr: the tile sort's last pass left (~start, end) per tile there (sort_launch: edges) instead of a
 // GetTileBinEdges launch; the kernel decodes them and writes tile_bins (every tile) for the aux / the backward.
-hipError_t launch_rasterize(uint32_t w, uint32_t h, uint32_t tbx, uint32_t tby,
-                            const uint32_t *compact_gid_from_isect, uint32_t *tile_bins, const uint32_t *bin_edges,
-                            const float *projected, int raster_u32, uint32_t u32_pitch, void *out_img,
-                            uint32_t *final_index, float *zero_rows /* nullable: [n][kCompactStride], the first
-                            *num_visible rows are zeroed (BrushAux::bwd_accum) */,
-                            const uint32_t *num_visible, uint32_t n, hipStream_t s,
-                            const float *compact_depth = nullptr /* brush_render_forward_depth: [n] z, compact order */,
-                            float *out_depth = nullptr /* [h][w]: accumulated depth (float image only) */);
+// zero_rows: nullable, [n][kCompactStride], the first *num_visible rows are zeroed (BrushAux::bwd_accum).
+hipError_t launch_rasterize(const RasterFrame &f, const RasterOut &out, const uint32_t *bin_edges, float *zero_rows,
+                            const uint32_t *num_visible, uint32_t n, hipStream_t s);
 // Zero-fill the compositing backward carries beside its arithmetic: the dense gradient arrays of the same backward
 // (render.rs:539-547,573-575 zero-fills them with separate launches).  The kernel is bound by VALU issue and moves
 // little memory, so its waves store the zeros in passing, one KiB (64 lanes x 16 B) per wave instruction, paced over
@@ -81,15 +93,18 @@ struct ZeroFill {
 // Fills `zf` for the given arrays (nullptr / 0 floats: skipped).  False — and an inactive `zf` — when an array is not
 // 16-byte aligned or too large for 32-bit chunk counts: the caller then keeps the zeros in the VJP kernel.
 bool make_zero_fill(ZeroFill *zf, float *const *arrays, const size_t *floats, uint32_t count);
-hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint32_t tby,
-                                     const uint32_t *compact_gid_from_isect, const uint32_t *tile_bins,
-                                     const float *projected, const uint32_t *final_index,
-                                     const float *out_img, const float *v_out, float *v_compact,
-                                     const uint32_t *unsorted_pos /* deterministic mode, else nullptr */,
-                                     float *rows /* deterministic mode: [max_intersects][12], else nullptr */,
-                                     const ZeroFill &fill, hipStream_t s,
-                                     const float *compact_depth = nullptr /* brush_render_backward_depth: [n] z */,
-                                     const float *v_depth = nullptr /* [h][w]: gradient of the accumulated depth */);
+// What the compositing backward reads and adds to; {}: no depth term, default mode.
+struct RasterGrads {
+    const float *out_img, *v_out;
+    float *v_compact;
+    // depth term (brush_render_backward_depth), both or neither
+    const float *compact_depth;  // [n] z, compact order
+    const float *v_depth;        // [h][w]: gradient of the accumulated depth
+    // deterministic mode, both or neither
+    const uint32_t *unsorted_pos;
+    float *rows;                 // [max_intersects][kCompactStride]
+};
+hipError_t launch_rasterize_backward(const RasterFrame &f, const RasterGrads &g, const ZeroFill &fill, hipStream_t s);
 
 // project_bwd.hip, view_records.hip
 // Optimizer state for the fused backward + Adam form (brush_render_backward_adam).

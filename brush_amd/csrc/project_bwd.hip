@@ -524,3 +524,30 @@ hipError_t launch_depth_means_grad(const ViewParams &vp, const uint32_t *num_vis
 }
 
 }  // namespace brush
+
+using namespace brush;
+
+// ---- the two entries of the deferred SH Adam (lazy_sh.hpp) that are no render call: the table of its steps' constants
+// (host only) and the flush that catches every row up ----------------------------------------------------------------
+
+extern "C" int brush_lazy_sh_fill_table(float beta1, float beta2, float lr_coeffs_dc, float sh_rest_lerp, uint32_t base,
+                                        uint32_t capacity, float *host_rows) {
+    if (!host_rows || base > 0xFFFFFFFFu - capacity) return BRUSH_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < capacity; i++) {
+        adam_bias_corrections(beta1, beta2, base + 1u + i, &host_rows[4 * i], &host_rows[4 * i + 1]);
+        host_rows[4 * i + 2] = lr_coeffs_dc;
+        host_rows[4 * i + 3] = sh_rest_lerp;
+    }
+    return BRUSH_OK;
+}
+
+extern "C" int brush_lazy_sh_flush(const BrushLazySh *h_lazy, float *sh, uint32_t n, uint32_t sh_degree,
+                                   brush_stream_t stream) {
+    LazySh lazy;
+    if (!h_lazy || sh_degree > 4 || !make_lazy_sh(h_lazy, sh_degree, &lazy)) return BRUSH_ERR_INVALID_ARG;
+    if (n == 0) return BRUSH_OK;
+    if (!sh || misaligned(sh, 16)) return BRUSH_ERR_INVALID_ARG;
+    BRUSH_HIP_CHECK(launch_lazy_sh_flush(lazy, sh, n, 3u * (sh_degree + 1u) * (sh_degree + 1u),
+                                         static_cast<hipStream_t>(stream)));
+    return BRUSH_OK;
+}

@@ -174,23 +174,20 @@ __global__ __launch_bounds__(kRasterThreads) void k_rasterize_quad(
 
 }  // namespace
 
-hipError_t launch_rasterize(uint32_t w, uint32_t h, uint32_t tbx, uint32_t tby,
-                            const uint32_t *compact_gid_from_isect, uint32_t *tile_bins, const uint32_t *bin_edges,
-                            const float *projected, int raster_u32, uint32_t u32_pitch, void *out_img,
-                            uint32_t *final_index, float *zero_rows, const uint32_t *num_visible, uint32_t n,
-                            hipStream_t s, const float *compact_depth, float *out_depth) {
-    const uint32_t tiles = tbx * tby;
+hipError_t launch_rasterize(const RasterFrame &f, const RasterOut &out, const uint32_t *bin_edges, float *zero_rows,
+                            const uint32_t *num_visible, uint32_t n, hipStream_t s) {
+    const uint32_t tiles = f.tbx * f.tby;
     if (tiles == 0) return hipSuccess;
     // one workgroup (4 quadrant waves) per tile
     const dim3 grid(ceil_div(tiles, 8u) * 8u), block(kRasterThreads);
-    if (out_depth && (raster_u32 || !compact_depth)) return hipErrorInvalidValue;
+    if (out.out_depth && (out.raster_u32 || !out.compact_depth)) return hipErrorInvalidValue;
     auto launch = [&](auto u32, const auto... depth) {
-        hipLaunchKernelGGL((k_rasterize_quad<u32(), std::decay_t<decltype(depth)>...>), grid, block, 0, s, w, h, tbx,
-                           tiles, compact_gid_from_isect, tile_bins, bin_edges, projected, out_img, final_index, u32_pitch,
-                           reinterpret_cast<float4 *>(zero_rows), num_visible, n, depth...);
+        hipLaunchKernelGGL((k_rasterize_quad<u32(), std::decay_t<decltype(depth)>...>), grid, block, 0, s, f.w, f.h,
+                           f.tbx, tiles, f.compact_gid_from_isect, f.tile_bins, bin_edges, f.projected, out.img,
+                           f.final_index, out.u32_pitch, reinterpret_cast<float4 *>(zero_rows), num_visible, n, depth...);
     };
-    if (out_depth) launch(std::false_type{}, DepthOut{compact_depth, out_depth});
-    else if (raster_u32) launch(std::true_type{});
+    if (out.out_depth) launch(std::false_type{}, DepthOut{out.compact_depth, out.out_depth});
+    else if (out.raster_u32) launch(std::true_type{});
     else launch(std::false_type{});
     return hipGetLastError();
 }

@@ -591,15 +591,11 @@ static uint32_t lds_pad_for(uint32_t units, uint32_t simds, uint32_t static_lds,
     return per_wg > static_lds ? per_wg - static_lds : 0u;
 }
 
-hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint32_t tby,
-                                     const uint32_t *compact_gid_from_isect, const uint32_t *tile_bins,
-                                     const float *projected, const uint32_t *final_index,
-                                     const float *out_img, const float *v_out, float *v_compact,
-                                     const uint32_t *unsorted_pos, float *rows, const ZeroFill &fill, hipStream_t s,
-                                     const float *compact_depth, const float *v_depth) {
-    const uint32_t tiles = tbx * tby;
+hipError_t launch_rasterize_backward(const RasterFrame &f, const RasterGrads &g, const ZeroFill &fill, hipStream_t s) {
+    const uint32_t tiles = f.tbx * f.tby;
     if (tiles == 0) return hipSuccess;
-    if (v_depth && !compact_depth) return hipErrorInvalidValue;
+    if (g.v_depth && !g.compact_depth) return hipErrorInvalidValue;
+    float *const rows = g.rows;  // deterministic mode, else nullptr
     // The one launch of k_rasterize_backward_quad<nq, det, kTilesPerBlock, Depth...>: tiles * 4 / nq waves, four to a
     // workgroup, the grid a multiple of 8 workgroups (xcd_contiguous_block).  Registers (kernel_diff.py --resources:
     // 96 / 98 VGPRs at NQ = 1, 104 / 108 at NQ = 2, 124 / 130 at NQ = 4, deterministic 124 / 128; without / with depth)
@@ -608,9 +604,10 @@ hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint3
         const uint32_t units = tiles * (4u / nq());
         const uint32_t lds_pad = lds_pad_for(units, device_simds(), bwd_static_lds<det(), sizeof...(depth) != 0>(), 4u);
         hipLaunchKernelGGL((k_rasterize_backward_quad<nq(), det(), kTilesPerBlock, std::decay_t<decltype(depth)>...>),
-                           dim3(ceil_div(ceil_div(units, kTilesPerBlock), 8u) * 8u), dim3(kRasterThreads), lds_pad, s, w,
-                           h, tbx, tiles, compact_gid_from_isect, tile_bins, projected, final_index, out_img, v_out,
-                           v_compact, det() ? unsorted_pos : nullptr, det() ? rows : nullptr, fill, depth...);
+                           dim3(ceil_div(ceil_div(units, kTilesPerBlock), 8u) * 8u), dim3(kRasterThreads), lds_pad, s, f.w,
+                           f.h, f.tbx, tiles, f.compact_gid_from_isect, f.tile_bins, f.projected, f.final_index,
+                           g.out_img, g.v_out, g.v_compact, det() ? g.unsorted_pos : nullptr, det() ? rows : nullptr,
+                           fill, depth...);
     };
     // deterministic mode (rows): one wave per tile, one stored row per intersection
     auto pick = [&](const auto... depth) {
@@ -621,7 +618,7 @@ hipError_t launch_rasterize_backward(uint32_t w, uint32_t h, uint32_t tbx, uint3
         else launch(NqC<1>{}, std::false_type{}, depth...);
     };
     // depth as a fourth channel: one more staged float per record, 10-component stage rows
-    v_depth ? pick(DepthGrad{compact_depth, v_depth}) : pick();
+    g.v_depth ? pick(DepthGrad{g.compact_depth, g.v_depth}) : pick();
     return hipGetLastError();
 }
 

@@ -4,7 +4,7 @@
 // argument, register or instruction is added.  In the trace build wave 0 of every workgroup keeps up to six s_memrealtime
 // stamps (100 MHz, one counter for the whole chip) — kernel entry, up to four marks each tied to the arrival of a value
 // (the device-side count the kernel starts from, the first data load, ...), last instruction before exit — and appends one record
-// to a ring the host reads back (brush_debug_trace_begin / brush_debug_trace_read, render.hip).  The record leaves
+// to a ring the host reads back (brush_debug_trace_begin / brush_debug_trace_read, profiler.hip).  The record leaves
 // through memory no kernel reads.  tools/debug/fwd_timeline.py turns the ring into the per-kernel table of
 // profiles/r04_small_kernel_timeline.json.  Quote the SHARES of that build, not its run time.
 #pragma once

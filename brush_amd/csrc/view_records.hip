@@ -8,9 +8,11 @@
 // k_reduce_view_records_*, one lane per GLOBAL splat id, adds the <= W records of its splat in view order 0..W-1.
 // No atomics: the sum is the same bit pattern on every rank and from run to run, so replicated parameters stay
 // replicated.  The sums leave as the single-view backward's do (grad_out.hpp): dense rows, or the per-wave Adam step.
-// Compiled with -ffp-contract=off, like project_bwd.hip.
+// Compiled with -ffp-contract=off, like project_bwd.hip.  The reduction's ABI entries are at the end of this file
+// (brush_render_backward_records: render_bwd.hip, on the backward's shared opening).
 #include "det_sums.hpp"
 #include "grad_out.hpp"
+#include "render_host.hpp"
 #include "splat_vjp.hpp"
 
 namespace brush {
@@ -253,3 +255,53 @@ hipError_t launch_reduce_view_records(const float *records, uint32_t num_views, 
 }
 
 }  // namespace brush
+
+using namespace brush;
+
+extern "C" int brush_view_index_size(uint32_t n, uint32_t num_views, size_t *bytes) {
+    if (!bytes) return BRUSH_ERR_INVALID_ARG;
+    *bytes = sizeof(uint32_t) * (size_t)(n ? n : 1) * (num_views ? num_views : 1);
+    return BRUSH_OK;
+}
+
+static int reduce_views_impl(const float *records, uint32_t num_views, uint32_t rows_per_view, const uint32_t *view_rows,
+                             const uint32_t *view_offsets, const float *campos, const float *means, uint32_t n,
+                             uint32_t sh_degree, float *v_means, float *v_scales, float *v_quats, float *v_sh,
+                             float *v_opac, const AdamFuse *adam, void *view_index, size_t view_index_bytes,
+                             brush_stream_t stream) {
+    if (sh_degree > 4 || num_views == 0) return BRUSH_ERR_INVALID_ARG;
+    if (n == 0) return BRUSH_OK;
+    if (!means || !view_index || !view_rows || !campos || (rows_per_view > 0 && !records)) return BRUSH_ERR_INVALID_ARG;
+    if (misaligned(records, 16)) return BRUSH_ERR_INVALID_ARG;
+    if (!adam && (!v_means || !v_scales || !v_quats || !v_sh || !v_opac)) return BRUSH_ERR_INVALID_ARG;
+    if (view_index_bytes < sizeof(uint32_t) * (size_t)n * num_views) return BRUSH_ERR_WORKSPACE_SMALL;
+    if (!view_offsets && (uint64_t)num_views * rows_per_view > 0xFFFFFFFFull) return BRUSH_ERR_INVALID_ARG;
+    BRUSH_HIP_CHECK(launch_reduce_view_records(records, num_views, rows_per_view, view_rows, view_offsets, campos, means, n,
+                                               sh_degree, static_cast<uint32_t *>(view_index), v_means, v_scales, v_quats,
+                                               v_sh, v_opac, adam, static_cast<hipStream_t>(stream)));
+    return BRUSH_OK;
+}
+
+extern "C" int brush_reduce_view_records(const float *records, uint32_t num_views, uint32_t rows_per_view,
+                                         const uint32_t *view_rows, const uint32_t *view_offsets, const float *campos,
+                                         const float *means, uint32_t n, uint32_t sh_degree, float *v_means,
+                                         float *v_scales, float *v_quats, float *v_sh, float *v_opac, void *view_index,
+                                         size_t view_index_bytes, brush_stream_t stream) {
+    return reduce_views_impl(records, num_views, rows_per_view, view_rows, view_offsets, campos, means, n, sh_degree, v_means,
+                             v_scales, v_quats, v_sh, v_opac, nullptr, view_index, view_index_bytes, stream);
+}
+
+extern "C" int brush_reduce_view_records_adam(const float *records, uint32_t num_views, uint32_t rows_per_view,
+                                              const uint32_t *view_rows, const uint32_t *view_offsets,
+                                              const float *campos, const BrushAdamConfig *cfg, uint32_t width, uint32_t height,
+                                              float *means, float *log_scales, float *rotation, float *raw_opacity,
+                                              float *sh, uint32_t n, uint32_t sh_degree, float *moment1, float *moment2,
+                                              float *next_quats_fed, float *grad_2d_accum, float *xy_grad_counts,
+                                              void *view_index, size_t view_index_bytes, brush_stream_t stream) {
+    AdamFuse af{};
+    if (!fill_adam_fuse(cfg, means, log_scales, rotation, raw_opacity, sh, n, moment1, moment2, next_quats_fed,
+                        grad_2d_accum, xy_grad_counts, width, height, sh_degree, &af))
+        return BRUSH_ERR_INVALID_ARG;
+    return reduce_views_impl(records, num_views, rows_per_view, view_rows, view_offsets, campos, means, n, sh_degree,
+                             nullptr, nullptr, nullptr, nullptr, nullptr, &af, view_index, view_index_bytes, stream);
+}

@@ -1,7 +1,7 @@
 """Float64 reference of the depth-distortion replays (brush_amd/csrc/distortion.hip: brush_render_distortion,
 brush_distortion_compact_grads) and their mechanism-based allowances.
 
-The walk is contrib_ref64.walk's (the forward's, rasterize.wgsl:57-101, in float64 on the float32 inputs, with the
+The walk is tests/replay_ref.py's (the forward's, rasterize.wgsl:57-101, in float64 on the float32 inputs, with the
 float32 values of the constants), extended with a per-case `compact_depth` (seeded_depth: non-decreasing along the compact
 order, with equal neighbours).  Per pixel, over the hits i = 1..n in list order (entries the forward added):
 
@@ -16,7 +16,7 @@ order, with equal neighbours).  Per pixel, over the hits i = 1..n in list order 
       mu'(z) sum v dL/dm_i         (dx = mean.x - pixel.x, gx = a dx + b dy, gy = b dx + c dy, o the drawn opacity)
 
 Allowances, from named mechanisms only (U = 2^-24; d_fac = fac (rel(alpha) + rel(T) + U) and rel(alpha), rel(T) exactly
-as contrib_ref64 derives them, before its calibration factor):
+as replay_ref derives them, before its calibration factor):
   m       "depth": exact.  "ndc": the kernels carry m~ = -(A near) / z, which differs from m by the constant A: the
           float32 A near (its subtraction, division and product) and the division by z round at the size of
           A near / z:  d_m = 4 U A near / z.
@@ -41,7 +41,8 @@ Each times C_DIST.  No constant is a fraction of a tensor's maximum.
 import numpy as np
 
 from tests import contrib_cases as CC
-from tests.contrib_ref64 import CLAMP, INV255, K_EXP, K_POW, K_SIG_A, K_SIG_B, K_SIG_C, K_T, T_STOP, U
+from tests.replay_ref import (CLAMP, INV255, K_EXP, K_POW, K_SIG_A, K_SIG_B, K_SIG_C, K_T, T_STOP, U,  # noqa: F401
+                              arrays, ratio, tiles, walk64)
 
 C_DIST = 1.0  # calibration factor of every allowance; raised only as far as a measured worst ratio on the GPU demands
 K_TREE = 6.0  # levels of the wave64 reduction tree
@@ -119,10 +120,7 @@ def walk(case, depth, v=None, mode="depth", near=0.2, far=None, mutate=None):
     Z = np.asarray(depth, np.float32).astype(np.float64)
     V = np.zeros((h, w)) if v is None else np.asarray(v, np.float32).astype(np.float64)
     assert V.shape == (h, w)
-    proj = np.asarray(case["projected"], np.float32).astype(np.float64)
-    bins = np.asarray(case["tile_bins"]).astype(np.int64)
-    isect = np.asarray(case["isect"]).astype(np.int64)
-    g_from_c = np.asarray(case["g_from_c"]).astype(np.int64)
+    proj, bins, isect, g_from_c = arrays(case)
     stats, tol_stats = np.zeros((h, w, 4)), np.zeros((h, w, 4))
     sum_wg = np.zeros((h, w))
     added_img = np.zeros((h, w), bool)
@@ -131,133 +129,106 @@ def walk(case, depth, v=None, mode="depth", near=0.2, far=None, mutate=None):
     touched = np.zeros(n, bool)
     risk = np.full(n, np.inf)
     twice = 2.0 if mutate == "pairs_twice" else 1.0
-    for ty in range(bins.shape[0]):
-        for tx in range(bins.shape[1]):
-            y0, x0 = ty * 16, tx * 16
-            ys, xs = np.meshgrid(np.arange(y0, min(y0 + 16, h)), np.arange(x0, min(x0 + 16, w)), indexing="ij")
-            pcx, pcy = xs + 0.5, ys + 0.5
-            quad = ((ys - y0) // 8) * 2 + (xs - x0) // 8
-            vt = V[ys, xs]
-            T = np.ones(xs.shape)
-            relT = np.zeros(xs.shape)
-            live = np.ones(xs.shape, bool)
-            recs = []  # the records with an added entry, in list order
-            for i in range(int(bins[ty, tx, 0]), int(bins[ty, tx, 1])):
-                if not live.any():
-                    break
-                c = int(isect[i])
-                m_x, m_y, ca, cb, cc = proj[c, 0], proj[c, 1], proj[c, 2], proj[c, 3], proj[c, 4]
-                o = proj[c, 8]
-                dx, dy = m_x - pcx, m_y - pcy
-                A, Cc, B = 0.5 * ca * dx * dx, 0.5 * cc * dy * dy, cb * dx * dy
-                sigma = A + Cc + B
-                d_sigma = U * (K_SIG_A * np.abs(A) + K_SIG_C * np.abs(Cc) + K_SIG_B * np.abs(B))
-                vis = np.exp(-sigma)
-                alpha_u = o * vis
-                rel_a = d_sigma + U * (K_POW * np.abs(sigma) + K_EXP + 1.0)
-                d_alpha_u = alpha_u * rel_a
-                passed = live & (sigma >= 0.0) & (alpha_u >= INV255)
-                alpha = np.minimum(CLAMP, alpha_u)
-                next_T = T * (1.0 - alpha)
-                rel_next = relT + d_alpha_u / np.maximum(1.0 - alpha, 1e-300) + K_T * U
-                stop = passed & (next_T <= T_STOP)
-                hit = passed & ~stop
-                added = (hit | stop) if mutate == "stop_added" else hit
-                if 0 <= c < n:  # the distance of the record's tests to their thresholds, in allowances
-                    with np.errstate(divide="ignore", invalid="ignore"):
-                        dists = [np.where(d_alpha_u > 0, np.abs(alpha_u - INV255) / d_alpha_u, np.inf)[live],
-                                 np.where(d_sigma > 0, np.abs(sigma) / d_sigma, np.inf)[live],
-                                 (np.abs(next_T - T_STOP) / np.maximum(next_T * rel_next, 1e-300))[passed],
-                                 np.where(d_alpha_u > 0, np.abs(alpha_u - CLAMP) / d_alpha_u, np.inf)[passed]]
-                    risk[c] = min([risk[c]] + [float(x.min()) for x in dists if x.size])
-                if added.any():
-                    fac = np.where(added, alpha if mutate == "ignore_T" else alpha * T, 0.0)
-                    recs.append(dict(c=c, H=added, w=fac, d_w=np.where(added, fac * (rel_a + relT + U), 0.0),
-                                     alpha=alpha, T=T.copy(), relT=relT.copy(), rel_a=rel_a, vis=vis, o=o,
-                                     d_alpha=np.where(alpha_u > CLAMP, 0.0, d_alpha_u),
-                                     clamped=(alpha_u > CLAMP) & (mutate != "clamp_grad"), dx=dx, dy=dy,
-                                     conic=(ca, cb, cc)))
-                T = np.where(hit, next_T, T)
-                relT = np.where(hit, rel_next, relT)
-                live = live & ~stop
-            if not recs:
+    for tile in tiles(bins, h, w):
+        ys, xs = tile.ys, tile.xs
+        quad = ((ys - tile.y0) // 8) * 2 + (xs - tile.x0) // 8
+        vt = V[ys, xs]
+        recs = []  # the records with an added entry, in list order
+        for e in walk64(proj, isect, tile):
+            c, a_u, d_a_u = e.c, e.alpha_u, e.d_alpha_u
+            added = (e.hit | e.stop) if mutate == "stop_added" else e.hit
+            if 0 <= c < n:  # the distance of the record's tests to their thresholds, in allowances
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    dists = [np.where(d_a_u > 0, np.abs(a_u - INV255) / d_a_u, np.inf)[e.live],
+                             np.where(e.d_sigma > 0, np.abs(e.sigma) / e.d_sigma, np.inf)[e.live],
+                             (np.abs(e.next_T - T_STOP) / np.maximum(e.next_T * e.rel_next, 1e-300))[e.passed],
+                             np.where(d_a_u > 0, np.abs(a_u - CLAMP) / d_a_u, np.inf)[e.passed]]
+                risk[c] = min([risk[c]] + [float(x.min()) for x in dists if x.size])
+            if added.any():
+                fac = np.where(added, e.alpha if mutate == "ignore_T" else e.alpha * e.T, 0.0)
+                recs.append(dict(c=c, H=added, w=fac, d_w=np.where(added, fac * (e.rel_a + e.relT + U), 0.0),
+                                 alpha=e.alpha, T=e.T, relT=e.relT, rel_a=e.rel_a, vis=e.vis, o=e.o,
+                                 d_alpha=np.where(a_u > CLAMP, 0.0, d_a_u),
+                                 clamped=(a_u > CLAMP) & (mutate != "clamp_grad"), dx=e.dx, dy=e.dy,
+                                 conic=e.conic))
+        if not recs:
+            continue
+        K = len(recs)
+        st = lambda key: np.stack([r[key] for r in recs])  # noqa: E731  [K, ph, pw]
+        H, W_k, dW_k = st("H"), st("w"), st("d_w")
+        cg = np.array([r["c"] for r in recs])
+        m_k, dmu_k, d_m_k = mu(Z[cg], mode, near, far)
+        first = np.argmax(H, axis=0)  # the first hit of a pixel (0 where it has none: masked by H below)
+        m0, d_m0 = m_k[first], d_m_k[first]
+        c_k = np.where(H, m_k[:, None, None] - m0[None], 0.0)
+        d_c = np.where(H, d_m_k[:, None, None] + d_m0[None] + U * np.abs(c_k), 0.0)
+        idx = np.cumsum(H, axis=0) - H  # hits in front of the entry
+        wc, wc2, wca = W_k * c_k, W_k * c_k * c_k, W_k * np.abs(c_k)
+        Wi, M1i, M2i, M1ai = (np.cumsum(a, axis=0) for a in (W_k, wc, wc2, wca))
+        Wx, M1x, M2x, M1ax = Wi - W_k, M1i - wc, M2i - wc2, M1ai - wca
+        g_run = c_k * c_k * Wx - 2.0 * c_k * M1x + M2x
+        L_run = np.cumsum(W_k * g_run, axis=0)
+        L, Wt, M1, M2, M1a = L_run[-1], Wi[-1], M1i[-1], M2i[-1], M1ai[-1]
+        # the gradient, from the totals
+        g = np.where(H, c_k * c_k * Wt - 2.0 * c_k * M1 + M2, 0.0)
+        cwm = np.where(H, c_k * Wt - M1, 0.0)
+        dLdm = 2.0 * W_k * cwm
+        # ---- allowance of the stats
+        E_run = c_k * c_k * Wx + 2.0 * np.abs(c_k) * M1ax + M2x
+        n_hits = H.sum(axis=0)
+        t_in = lambda gw, gc: (gw * dW_k + gc * d_c).sum(axis=0)  # noqa: E731  the inputs through exact partials
+        tol_L = t_in(g, np.abs(dLdm)) + (W_k * U * (idx + 3.0) * E_run).sum(axis=0) + U * np.abs(L_run).sum(axis=0)
+        tol_W = dW_k.sum(axis=0) + U * Wi.sum(axis=0)
+        tol_M1 = t_in(np.abs(c_k), W_k) + U * (wca.sum(axis=0) + M1ai.sum(axis=0))
+        tol_M2 = t_in(c_k * c_k, 2.0 * wca) + U * (2.0 * wc2.sum(axis=0) + M2i.sum(axis=0))
+        stats[ys, xs] = np.stack([twice * L, Wt, M1, M2], axis=-1)
+        tol_stats[ys, xs] = C_DIST * np.stack([twice * tol_L, tol_W, tol_M1, tol_M2], axis=-1)
+        added_img[ys, xs] = n_hits > 0
+        # ---- dL/dalpha and its allowance
+        alpha, Tk, relT_k, rel_a_k = st("alpha"), st("T"), st("relT"), st("rel_a")
+        om = 1.0 - alpha
+        E_tot = c_k * c_k * Wt + 2.0 * np.abs(c_k) * M1a + M2
+        d_g = np.where(H, c_k * c_k * tol_W + 2.0 * np.abs(c_k) * tol_M1 + tol_M2 + 2.0 * np.abs(cwm) * d_c
+                       + 3.0 * U * E_tot, 0.0)
+        wg = W_k * g
+        P = np.cumsum(wg, axis=0)
+        d_P = np.cumsum(g * dW_k + W_k * d_g, axis=0) + U * np.cumsum(np.abs(P), axis=0)
+        sum_wg[ys, xs] = P[-1]
+        rest = 2.0 * L - (P - wg if mutate == "suffix_incl" else P)
+        D = rest / om
+        d_D = (2.0 * tol_L + d_P + U * np.abs(rest)) / om + np.abs(D) * (2.0 * U + st("d_alpha") / om)
+        dLda = np.where(H & ~st("clamped"), Tk * g - D, 0.0)
+        d_dLda = np.where(H & ~st("clamped"), Tk * g * relT_k + Tk * d_g + d_D + U * (np.abs(Tk * g) + np.abs(D)), 0.0)
+        vis = st("vis")
+        vva = twice * vis * vt[None] * dLda
+        d_vva = np.abs(vt)[None] * vis * d_dLda + np.abs(vva) * (rel_a_k + 2.0 * U)
+        vm = twice * vt[None] * dLdm  # word 9's terms, before mu'
+        d_cwm = np.where(H, np.abs(c_k) * tol_W + Wt * d_c + tol_M1 + U * (np.abs(c_k) * Wt + np.abs(M1)), 0.0)
+        d_vm = np.abs(vt)[None] * (2.0 * dW_k * np.abs(cwm) + 2.0 * W_k * d_cwm) + 2.0 * U * np.abs(vm)
+        for k, r in enumerate(recs):
+            c = r["c"]
+            row = c if mutate != "global_row" else int(g_from_c[c])
+            if not 0 <= row < n:
                 continue
-            K = len(recs)
-            st = lambda key: np.stack([r[key] for r in recs])  # noqa: E731  [K, ph, pw]
-            H, W_k, dW_k = st("H"), st("w"), st("d_w")
-            cg = np.array([r["c"] for r in recs])
-            m_k, dmu_k, d_m_k = mu(Z[cg], mode, near, far)
-            first = np.argmax(H, axis=0)  # the first hit of a pixel (0 where it has none: masked by H below)
-            m0, d_m0 = m_k[first], d_m_k[first]
-            c_k = np.where(H, m_k[:, None, None] - m0[None], 0.0)
-            d_c = np.where(H, d_m_k[:, None, None] + d_m0[None] + U * np.abs(c_k), 0.0)
-            idx = np.cumsum(H, axis=0) - H  # hits in front of the entry
-            wc, wc2, wca = W_k * c_k, W_k * c_k * c_k, W_k * np.abs(c_k)
-            Wi, M1i, M2i, M1ai = (np.cumsum(a, axis=0) for a in (W_k, wc, wc2, wca))
-            Wx, M1x, M2x, M1ax = Wi - W_k, M1i - wc, M2i - wc2, M1ai - wca
-            g_run = c_k * c_k * Wx - 2.0 * c_k * M1x + M2x
-            L_run = np.cumsum(W_k * g_run, axis=0)
-            L, Wt, M1, M2, M1a = L_run[-1], Wi[-1], M1i[-1], M2i[-1], M1ai[-1]
-            # the gradient, from the totals
-            g = np.where(H, c_k * c_k * Wt - 2.0 * c_k * M1 + M2, 0.0)
-            cwm = np.where(H, c_k * Wt - M1, 0.0)
-            dLdm = 2.0 * W_k * cwm
-            # ---- allowance of the stats
-            E_run = c_k * c_k * Wx + 2.0 * np.abs(c_k) * M1ax + M2x
-            n_hits = H.sum(axis=0)
-            t_in = lambda gw, gc: (gw * dW_k + gc * d_c).sum(axis=0)  # noqa: E731  the inputs through exact partials
-            tol_L = t_in(g, np.abs(dLdm)) + (W_k * U * (idx + 3.0) * E_run).sum(axis=0) + U * np.abs(L_run).sum(axis=0)
-            tol_W = dW_k.sum(axis=0) + U * Wi.sum(axis=0)
-            tol_M1 = t_in(np.abs(c_k), W_k) + U * (wca.sum(axis=0) + M1ai.sum(axis=0))
-            tol_M2 = t_in(c_k * c_k, 2.0 * wca) + U * (2.0 * wc2.sum(axis=0) + M2i.sum(axis=0))
-            stats[ys, xs] = np.stack([twice * L, Wt, M1, M2], axis=-1)
-            tol_stats[ys, xs] = C_DIST * np.stack([twice * tol_L, tol_W, tol_M1, tol_M2], axis=-1)
-            added_img[ys, xs] = n_hits > 0
-            # ---- dL/dalpha and its allowance
-            alpha, Tk, relT_k, rel_a_k = st("alpha"), st("T"), st("relT"), st("rel_a")
-            om = 1.0 - alpha
-            E_tot = c_k * c_k * Wt + 2.0 * np.abs(c_k) * M1a + M2
-            d_g = np.where(H, c_k * c_k * tol_W + 2.0 * np.abs(c_k) * tol_M1 + tol_M2 + 2.0 * np.abs(cwm) * d_c
-                           + 3.0 * U * E_tot, 0.0)
-            wg = W_k * g
-            P = np.cumsum(wg, axis=0)
-            d_P = np.cumsum(g * dW_k + W_k * d_g, axis=0) + U * np.cumsum(np.abs(P), axis=0)
-            sum_wg[ys, xs] = P[-1]
-            rest = 2.0 * L - (P - wg if mutate == "suffix_incl" else P)
-            D = rest / om
-            d_D = (2.0 * tol_L + d_P + U * np.abs(rest)) / om + np.abs(D) * (2.0 * U + st("d_alpha") / om)
-            dLda = np.where(H & ~st("clamped"), Tk * g - D, 0.0)
-            d_dLda = np.where(H & ~st("clamped"), Tk * g * relT_k + Tk * d_g + d_D + U * (np.abs(Tk * g) + np.abs(D)), 0.0)
-            vis = st("vis")
-            vva = twice * vis * vt[None] * dLda
-            d_vva = np.abs(vt)[None] * vis * d_dLda + np.abs(vva) * (rel_a_k + 2.0 * U)
-            vm = twice * vt[None] * dLdm  # word 9's terms, before mu'
-            d_cwm = np.where(H, np.abs(c_k) * tol_W + Wt * d_c + tol_M1 + U * (np.abs(c_k) * Wt + np.abs(M1)), 0.0)
-            d_vm = np.abs(vt)[None] * (2.0 * dW_k * np.abs(cwm) + 2.0 * W_k * d_cwm) + 2.0 * U * np.abs(vm)
-            for k, r in enumerate(recs):
-                c = r["c"]
-                row = c if mutate != "global_row" else int(g_from_c[c])
-                if not 0 <= row < n:
-                    continue
-                ca, cb, cc = r["conic"]
-                dx, dy, o = r["dx"], r["dy"], r["o"]
-                # (geometry factor, the magnitude of the terms it is formed from, the per-record factor)
-                geo = ((ca * dx + cb * dy, np.abs(ca * dx) + np.abs(cb * dy), -o),
-                       (cb * dx + cc * dy, np.abs(cb * dx) + np.abs(cc * dy), -o),
-                       (dx * dx, dx * dx, -0.5 * o), (dx * dy, np.abs(dx * dy), -o), (dy * dy, dy * dy, -0.5 * o),
-                       (np.ones_like(dx), np.zeros_like(dx), 1.0))
-                Hk = H[k]
-                P_k = len(np.unique(quad[Hk]))
-                touched[row] = True
-                partials[row] += P_k
-                for j, (f, fmag, scale) in enumerate(geo):
-                    rows[row, j] += scale * (vva[k] * f)[Hk].sum()
-                    abs_rows[row, j] += abs(scale) * np.abs(vva[k] * f)[Hk].sum()
-                    tol_rows[row, j] += C_DIST * abs(scale) * (d_vva[k] * np.abs(f) + K_GEO * U * np.abs(vva[k]) * fmag)[Hk].sum()
-                s9 = 1.0 if mutate == "no_dmu" else dmu_k[k]
-                rows[row, 6] += s9 * vm[k][Hk].sum()
-                abs_rows[row, 6] += abs(s9) * np.abs(vm[k])[Hk].sum()
-                tol_rows[row, 6] += C_DIST * abs(s9) * (d_vm[k] + (3.0 * U if mode == "ndc" else 0.0) * np.abs(vm[k]))[Hk].sum()
+            ca, cb, cc = r["conic"]
+            dx, dy, o = r["dx"], r["dy"], r["o"]
+            # (geometry factor, the magnitude of the terms it is formed from, the per-record factor)
+            geo = ((ca * dx + cb * dy, np.abs(ca * dx) + np.abs(cb * dy), -o),
+                   (cb * dx + cc * dy, np.abs(cb * dx) + np.abs(cc * dy), -o),
+                   (dx * dx, dx * dx, -0.5 * o), (dx * dy, np.abs(dx * dy), -o), (dy * dy, dy * dy, -0.5 * o),
+                   (np.ones_like(dx), np.zeros_like(dx), 1.0))
+            Hk = H[k]
+            P_k = len(np.unique(quad[Hk]))
+            touched[row] = True
+            partials[row] += P_k
+            for j, (f, fmag, scale) in enumerate(geo):
+                rows[row, j] += scale * (vva[k] * f)[Hk].sum()
+                abs_rows[row, j] += abs(scale) * np.abs(vva[k] * f)[Hk].sum()
+                tol_rows[row, j] += C_DIST * abs(scale) * (d_vva[k] * np.abs(f) + K_GEO * U * np.abs(vva[k]) * fmag)[Hk].sum()
+            s9 = 1.0 if mutate == "no_dmu" else dmu_k[k]
+            rows[row, 6] += s9 * vm[k][Hk].sum()
+            abs_rows[row, 6] += abs(s9) * np.abs(vm[k])[Hk].sum()
+            tol_rows[row, 6] += C_DIST * abs(s9) * (d_vm[k] + (3.0 * U if mode == "ndc" else 0.0) * np.abs(vm[k]))[Hk].sum()
     tol_rows += C_DIST * (K_TREE + 1.0 + partials)[:, None] * U * abs_rows
     return dict(stats=stats, tol_stats=tol_stats, added=added_img, sum_wg=sum_wg, rows=rows, tol_rows=tol_rows, abs_rows=abs_rows,
                 partials=partials, touched=touched, risk=risk / C_DIST)
@@ -265,7 +236,8 @@ def walk(case, depth, v=None, mode="depth", near=0.2, far=None, mutate=None):
 
 def brute_force(case, depth, mode="depth", near=0.2, far=None):
     """L [h,w] as the O(n^2) sum over the unordered pairs of every pixel's hits, in float64, from a walk of its own that
-    keeps the (w, m) of every hit: sum_{j<i} w_i w_j (m_i - m_j)^2 with the raw m (no shift)."""
+    keeps the (w, m) of every hit: sum_{j<i} w_i w_j (m_i - m_j)^2 with the raw m (no shift).
+    Deliberately independent of replay_ref's walk, which the running form is tested against: do not rebuild it on it."""
     w, h = int(case["w"]), int(case["h"])
     Z = np.asarray(depth, np.float32).astype(np.float64)
     proj = np.asarray(case["projected"], np.float32).astype(np.float64)
@@ -295,16 +267,6 @@ def brute_force(case, depth, mode="depth", near=0.2, far=None):
                     acc += ws[i] * ws[j] * (ms[i] - ms[j]) ** 2
             out[y, x] = acc
     return out
-
-
-def ratio(got, want, tol):
-    """The worst |got - want| / tol (0 / 0 = 0: where the allowance is zero the value must be exact, any difference
-    there is inf; a NaN anywhere is inf)."""
-    d = np.abs(np.asarray(got, np.float64) - want)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(d == 0, 0.0, d / tol)
-    r = np.where(np.isnan(r), np.inf, r)
-    return float(np.max(r)) if r.size else 0.0
 
 
 def gate(ref, stats=None, rows=None, extra_rows_tol=None):

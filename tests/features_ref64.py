@@ -1,14 +1,14 @@
 """Float64 reference of the feature replays (brush_amd/csrc/features.hip: brush_render_features,
 brush_render_features_backward, brush_render_feature_sums) and their mechanism-based allowances.
 
-The walk is contrib_ref64.walk's (the forward's, rasterize.wgsl:57-101, in float64 on the float32 inputs, with the
+The walk is tests/replay_ref.py's (the forward's, rasterize.wgsl:57-101, in float64 on the float32 inputs, with the
 float32 values of the constants), extended with C channels: every hit (an entry the forward added, fac = alpha T)
 
     forward    out[p, c]  += fac f[g, c]                 f [n,C] float32, rows by GLOBAL id
     transpose  grad[g, c] += fac v[p, c]                 v [h,w,C] float32, arbitrary
     sums       q[g, c]    += fac m[p, c]                 m = min(max(M, 0), 1) of a float32 map M (a NaN counts as 0)
 
-Allowances, from named mechanisms only (U = 2^-24; d_fac = fac (rel(alpha) + rel(T) + U) exactly as contrib_ref64
+Allowances, from named mechanisms only (U = 2^-24; d_fac = fac (rel(alpha) + rel(T) + U) exactly as replay_ref
 derives it, before its calibration factor):
   forward    per hit |f| d_fac for the weight, plus |f fac| U for the fused multiply-add's one rounding (the running sum is
              bounded by the sum of the |terms|); summed over the pixel's hits.
@@ -20,7 +20,8 @@ Each times C_FEAT.  No constant is a fraction of a tensor's maximum.
 """
 import numpy as np
 
-from tests.contrib_ref64 import CLAMP, INV255, K_EXP, K_POW, K_SIG_A, K_SIG_B, K_SIG_C, K_T, Q24, T_STOP, U
+from tests.replay_ref import (CLAMP, INV255, K_EXP, K_POW, K_SIG_A, K_SIG_B, K_SIG_C, K_T, Q24, T_STOP, U,  # noqa: F401
+                              arrays, fma, ratio, tiles, walk32, walk64)
 from tests.error_ref64 import clamp_map
 
 C_FEAT = 1.0  # calibration factor of every allowance; raised only as far as a measured worst ratio demands
@@ -70,69 +71,39 @@ def walk(case, features, v=None, maps=None, mutate=None):
         V, M = _as_chw(V), _as_chw(M)
     if mutate == "channel_off_by_one":
         F = np.roll(F, -1, axis=1)
-    proj = np.asarray(case["projected"], np.float32).astype(np.float64)
-    bins = np.asarray(case["tile_bins"]).astype(np.int64)
-    isect = np.asarray(case["isect"]).astype(np.int64)
-    g_from_c = np.asarray(case["g_from_c"]).astype(np.int64)
+    proj, bins, isect, g_from_c = arrays(case)
     out, tol_out = np.zeros((h, w, nc)), np.zeros((h, w, nc))
     added_img = np.zeros((h, w), bool)
     grad, tol_grad, abs_grad = np.zeros((n, nc)), np.zeros((n, nc)), np.zeros((n, nc))
     q, tol_q = np.zeros((n, nc)), np.zeros((n, nc))
     touched = np.zeros(n, bool)
     partials = np.zeros(n)
-    for ty in range(bins.shape[0]):
-        for tx in range(bins.shape[1]):
-            y0, x0 = ty * 16, tx * 16
-            ys, xs = np.meshgrid(np.arange(y0, min(y0 + 16, h)), np.arange(x0, min(x0 + 16, w)), indexing="ij")
-            pcx, pcy = xs + 0.5, ys + 0.5
-            quad = ((ys - y0) // 8) * 2 + (xs - x0) // 8
-            vt, mt = V[ys, xs], M[ys, xs]
-            o_t, tol_t = np.zeros(xs.shape + (nc,)), np.zeros(xs.shape + (nc,))
-            T = np.ones(xs.shape)
-            relT = np.zeros(xs.shape)
-            live = np.ones(xs.shape, bool)
-            any_added = np.zeros(xs.shape, bool)
-            for i in range(int(bins[ty, tx, 0]), int(bins[ty, tx, 1])):
-                if not live.any():
-                    break
-                c = int(isect[i])
-                g = c if mutate == "compact_row" else int(g_from_c[c])
-                m_x, m_y, ca, cb, cc = proj[c, 0], proj[c, 1], proj[c, 2], proj[c, 3], proj[c, 4]
-                o = proj[c, 8]
-                dx, dy = m_x - pcx, m_y - pcy
-                A, Cc, B = 0.5 * ca * dx * dx, 0.5 * cc * dy * dy, cb * dx * dy
-                sigma = A + Cc + B
-                d_sigma = U * (K_SIG_A * np.abs(A) + K_SIG_C * np.abs(Cc) + K_SIG_B * np.abs(B))
-                alpha_u = o * np.exp(-sigma)
-                rel_a = d_sigma + U * (K_POW * np.abs(sigma) + K_EXP + 1.0)
-                d_alpha_u = alpha_u * rel_a
-                passed = live & (sigma >= 0.0) & (alpha_u >= INV255)
-                alpha = np.minimum(CLAMP, alpha_u)
-                next_T = T * (1.0 - alpha)
-                rel_next = relT + d_alpha_u / np.maximum(1.0 - alpha, 1e-300) + K_T * U
-                stop = passed & (next_T <= T_STOP)
-                hit = passed & ~stop
-                added = (hit | stop) if mutate == "stop_added" else hit
-                fac = np.where(added, alpha if mutate == "ignore_T" else alpha * T, 0.0)
-                d_fac = np.where(added, fac * (rel_a + relT + U), 0.0)
-                if added.any():
-                    f = F[g] if g < n else np.zeros(nc)
-                    fa, dfa = fac[..., None], d_fac[..., None]
-                    o_t += fa * f
-                    tol_t += C_FEAT * (np.abs(f) * dfa + np.abs(f) * fa * U)
-                    any_added |= added
-                    if g < n:
-                        touched[g] = True
-                        partials[g] += len(np.unique(quad[added]))
-                        grad[g] += (fa * vt).sum(axis=(0, 1))
-                        abs_grad[g] += (fa * np.abs(vt)).sum(axis=(0, 1))
-                        tol_grad[g] += C_FEAT * (np.abs(vt) * dfa + np.abs(vt) * fa * U).sum(axis=(0, 1))
-                        q[g] += (fa * mt).sum(axis=(0, 1))
-                        tol_q[g] += C_FEAT * ((mt * dfa + mt * fa * U).sum(axis=(0, 1)) + 0.5 / Q24 * int(added.sum()))
-                T = np.where(hit, next_T, T)
-                relT = np.where(hit, rel_next, relT)
-                live = live & ~stop
-            out[ys, xs], tol_out[ys, xs], added_img[ys, xs] = o_t, tol_t, any_added
+    for tile in tiles(bins, h, w):
+        ys, xs = tile.ys, tile.xs
+        quad = ((ys - tile.y0) // 8) * 2 + (xs - tile.x0) // 8
+        vt, mt = V[ys, xs], M[ys, xs]
+        o_t, tol_t = np.zeros(xs.shape + (nc,)), np.zeros(xs.shape + (nc,))
+        any_added = np.zeros(xs.shape, bool)
+        for e in walk64(proj, isect, tile):
+            g = e.c if mutate == "compact_row" else int(g_from_c[e.c])
+            added = (e.hit | e.stop) if mutate == "stop_added" else e.hit
+            fac = np.where(added, e.alpha if mutate == "ignore_T" else e.alpha * e.T, 0.0)
+            d_fac = np.where(added, fac * (e.rel_a + e.relT + U), 0.0)
+            if added.any():
+                f = F[g] if g < n else np.zeros(nc)
+                fa, dfa = fac[..., None], d_fac[..., None]
+                o_t += fa * f
+                tol_t += C_FEAT * (np.abs(f) * dfa + np.abs(f) * fa * U)
+                any_added |= added
+                if g < n:
+                    touched[g] = True
+                    partials[g] += len(np.unique(quad[added]))
+                    grad[g] += (fa * vt).sum(axis=(0, 1))
+                    abs_grad[g] += (fa * np.abs(vt)).sum(axis=(0, 1))
+                    tol_grad[g] += C_FEAT * (np.abs(vt) * dfa + np.abs(vt) * fa * U).sum(axis=(0, 1))
+                    q[g] += (fa * mt).sum(axis=(0, 1))
+                    tol_q[g] += C_FEAT * ((mt * dfa + mt * fa * U).sum(axis=(0, 1)) + 0.5 / Q24 * int(added.sum()))
+        out[ys, xs], tol_out[ys, xs], added_img[ys, xs] = o_t, tol_t, any_added
     tol_grad += C_FEAT * (K_TREE + partials)[:, None] * U * abs_grad
     if mutate == "chw":
         out, tol_out = _as_chw(out), _as_chw(tol_out)
@@ -140,16 +111,6 @@ def walk(case, features, v=None, maps=None, mutate=None):
         grad, tol_grad, abs_grad, q, tol_q = (np.roll(a, -1, axis=1) for a in (grad, tol_grad, abs_grad, q, tol_q))
     return dict(out=out, tol_out=tol_out, added=added_img, grad=grad, tol_grad=tol_grad, abs_grad=abs_grad, q=q,
                 tol_q=tol_q, touched=touched, partials=partials)
-
-
-def ratio(got, want, tol):
-    """The worst |got - want| / tol (0 / 0 = 0: where the allowance is zero the value must be exact, any difference
-    there is inf; a NaN anywhere is inf)."""
-    d = np.abs(np.asarray(got, np.float64) - want)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(d == 0, 0.0, d / tol)
-    r = np.where(np.isnan(r), np.inf, r)
-    return float(np.max(r)) if r.size else 0.0
 
 
 def gate(ref, out=None, grad=None, q=None):
@@ -170,7 +131,7 @@ def passes(r):
 
 
 def emulate32(case, features, v=None, maps=None):
-    """The kernels' arithmetic restated in numpy float32 (as contrib_ref64.emulate32: fused multiply-adds through
+    """The kernels' arithmetic restated in numpy float32 (replay_ref.walk32: fused multiply-adds through
     float64 with one rounding, exp2 through float64): a stand-in for the device in tests that run anywhere.  Returns
     dict(out float32 [h,w,C], grad float32 [n,C] (per record and 8x8 quadrant a float32 sum of the float32 products,
     added to the row in float32: one of the orders the atomics may take), q int64 [n,C])."""
@@ -180,53 +141,25 @@ def emulate32(case, features, v=None, maps=None):
     nc = F.shape[1]
     V = np.zeros((h, w, nc), f32) if v is None else np.asarray(v, f32)
     M = np.zeros((h, w, nc), f32) if maps is None else clamp_map(maps).astype(f32)
-    proj = np.asarray(case["projected"], f32)
-    bins = np.asarray(case["tile_bins"]).astype(np.int64)
-    isect = np.asarray(case["isect"]).astype(np.int64)
-    g_from_c = np.asarray(case["g_from_c"]).astype(np.int64)
+    proj, bins, isect, g_from_c = arrays(case, f32)
     out = np.zeros((h, w, nc), f32)
     grad = np.zeros((n, nc), f32)
     q = np.zeros((n, nc), np.int64)
-
-    def fma(a, b, c):
-        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(f32)
-
-    neg_log2e = f32(-1.44269504088896341)
-    for ty in range(bins.shape[0]):
-        for tx in range(bins.shape[1]):
-            y0, x0 = ty * 16, tx * 16
-            ys, xs = np.meshgrid(np.arange(y0, min(y0 + 16, h)), np.arange(x0, min(x0 + 16, w)), indexing="ij")
-            pcx, pcy = (xs + 0.5).astype(f32), (ys + 0.5).astype(f32)
-            quad = ((ys - y0) // 8) * 2 + (xs - x0) // 8
-            vt, mt = V[ys, xs], M[ys, xs]
-            acc = np.zeros(xs.shape + (nc,), f32)
-            T = np.ones(xs.shape, f32)
-            live = np.ones(xs.shape, bool)
-            for i in range(int(bins[ty, tx, 0]), int(bins[ty, tx, 1])):
-                if not live.any():
-                    break
-                c = int(isect[i])
-                g = int(g_from_c[c])
-                p = proj[c]
-                dx, dy = p[0] - pcx, p[1] - pcy
-                sigma = fma(np.full_like(dx, 0.5), fma(p[2] * dx, dx, (p[4] * dy) * dy), (p[3] * dy) * dx)
-                power = sigma * neg_log2e
-                alpha_u = p[8] * np.exp2(power.astype(np.float64)).astype(f32)
-                passed = live & (power <= 0) & (alpha_u >= f32(1.0) / f32(255.0))
-                alpha = np.minimum(f32(0.999), alpha_u)
-                next_T = T * (f32(1.0) - alpha)
-                stop = passed & (next_T <= f32(1e-4))
-                hit = passed & ~stop
-                fac = np.where(hit, alpha * T, f32(0))
-                if hit.any():
-                    fa = fac[..., None]
-                    acc = np.where(hit[..., None], fma(np.broadcast_to(F[g], acc.shape), np.broadcast_to(fa, acc.shape),
-                                                       acc), acc)
-                    prod = (fa * vt).astype(f32)
-                    for s in np.unique(quad[hit]):
-                        grad[g] = grad[g] + prod[quad == s].sum(axis=0, dtype=f32)
-                    q[g] += np.rint((fa * mt).astype(f32).astype(np.float64) * Q24).astype(np.int64).sum(axis=(0, 1))
-                T = np.where(hit, next_T, T)
-                live = live & ~stop
-            out[ys, xs] = acc
+    for tile in tiles(bins, h, w):
+        ys, xs = tile.ys, tile.xs
+        quad = ((ys - tile.y0) // 8) * 2 + (xs - tile.x0) // 8
+        vt, mt = V[ys, xs], M[ys, xs]
+        acc = np.zeros(xs.shape + (nc,), f32)
+        for e in walk32(proj, isect, tile):
+            g, hit = int(g_from_c[e.c]), e.hit
+            fac = np.where(hit, e.alpha * e.T, f32(0))
+            if hit.any():
+                fa = fac[..., None]
+                acc = np.where(hit[..., None], fma(np.broadcast_to(F[g], acc.shape), np.broadcast_to(fa, acc.shape),
+                                                   acc), acc)
+                prod = (fa * vt).astype(f32)
+                for s in np.unique(quad[hit]):
+                    grad[g] = grad[g] + prod[quad == s].sum(axis=0, dtype=f32)
+                q[g] += np.rint((fa * mt).astype(f32).astype(np.float64) * Q24).astype(np.int64).sum(axis=(0, 1))
+        out[ys, xs] = acc
     return dict(out=out, grad=grad, q=q)

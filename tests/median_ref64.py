@@ -1,6 +1,6 @@
 """Float64 reference of brush_render_median_depth (brush_amd/csrc/median_depth.hip) and its gate.
 
-The walk is the one of tests/contrib_ref64.py (same inputs, constants and allowances, imported from there), on a case
+The walk is the one of tests/replay_ref.py (inputs, constants and allowances; C_CONTRIB is contrib_ref64's), on a case
 with a float32 z per compact id (tests/median_cases.py).  Per pixel the median entry is the first ADDED entry with
 
     next_T <= t_level,      t_level = float32(1) - float32(level)      (the entry point's one f32 subtraction)
@@ -11,14 +11,16 @@ tell.  For every level test a pixel makes up to and including its crossing the r
 
     |next_T - t_level| / (next_T rel(next_T))
 
-with rel from contrib_ref64's T mechanism; a pixel whose nearest test lies within UNDECIDED = 8 allowances is undecided,
+with rel from replay_ref's T mechanism; a pixel whose nearest test lies within UNDECIDED = 8 allowances is undecided,
 and for it the reference also finds the crossing with the threshold moved down and up by 8 allowances of each entry:
 the device's pick must lie between those two list positions.  A distance of exactly 0 on exactly computed values (sigma
 = 0, nothing in front, 1 - alpha exact in float32) is decided: float32 computes the same tie.
 """
 import numpy as np
 
-from tests.contrib_ref64 import (C_CONTRIB, CLAMP, INV255, K_EXP, K_POW, K_SIG_A, K_SIG_B, K_SIG_C, K_T, T_STOP, U)
+from tests.contrib_ref64 import C_CONTRIB
+from tests.replay_ref import (CLAMP, INV255, K_EXP, K_POW, K_SIG_A, K_SIG_B, K_SIG_C, K_T, T_STOP, U,  # noqa: F401
+                              arrays, tiles, walk32, walk64)
 
 UNDECIDED = 8.0
 NEVER = np.iinfo(np.int64).max  # the list position of "no entry crosses"
@@ -38,69 +40,40 @@ def walk(case, level, mutate=None):
     assert mutate is None or mutate in MUTATIONS, mutate
     w, h = int(case["w"]), int(case["h"])
     t_level = t_level_of(level)
-    proj = np.asarray(case["projected"], np.float32).astype(np.float64)
-    bins = np.asarray(case["tile_bins"]).astype(np.int64)
-    isect = np.asarray(case["isect"]).astype(np.int64)
-    g_from_c = np.asarray(case["g_from_c"]).astype(np.int64)
+    proj, bins, isect, g_from_c = arrays(case)
     z = np.asarray(case["z"], np.float32)
     out = dict(id=np.full((h, w), -1, np.int64), depth=np.zeros((h, w), np.float32),
                pos=np.full((h, w), NEVER, np.int64), pos_lo=np.full((h, w), NEVER, np.int64),
                pos_hi=np.full((h, w), NEVER, np.int64), dist=np.full((h, w), np.inf))
-    for ty in range(bins.shape[0]):
-        for tx in range(bins.shape[1]):
-            y0, x0 = ty * 16, tx * 16
-            ys, xs = np.meshgrid(np.arange(y0, min(y0 + 16, h)), np.arange(x0, min(x0 + 16, w)), indexing="ij")
-            pcx, pcy = xs + 0.5, ys + 0.5
-            T = np.ones(xs.shape)
-            relT = np.zeros(xs.shape)
-            live = np.ones(xs.shape, bool)      # not stopped (the walk goes on behind the crossing, for pos_hi)
-            pos = np.full(xs.shape, NEVER, np.int64)
-            pos_lo, pos_hi = pos.copy(), pos.copy()
-            dist = np.full(xs.shape, np.inf)
-            for i in range(int(bins[ty, tx, 0]), int(bins[ty, tx, 1])):
-                if not live.any():
-                    break
-                c = int(isect[i])
-                m_x, m_y, ca, cb, cc = proj[c, 0], proj[c, 1], proj[c, 2], proj[c, 3], proj[c, 4]
-                o = proj[c, 8]
-                dx, dy = m_x - pcx, m_y - pcy
-                A, Cc, B = 0.5 * ca * dx * dx, 0.5 * cc * dy * dy, cb * dx * dy
-                sigma = A + Cc + B
-                d_sigma = U * (K_SIG_A * np.abs(A) + K_SIG_C * np.abs(Cc) + K_SIG_B * np.abs(B))
-                alpha_u = o * np.exp(-sigma)
-                rel_a = d_sigma + U * (K_POW * np.abs(sigma) + K_EXP + 1.0)
-                d_alpha_u = alpha_u * rel_a
-                passed = live & (sigma >= 0.0) & (alpha_u >= INV255)
-                alpha = np.minimum(CLAMP, alpha_u)
-                next_T = T * (1.0 - alpha)
-                rel_next = relT + d_alpha_u / np.maximum(1.0 - alpha, 1e-300) + K_T * U
-                stop = passed & (next_T <= T_STOP)
-                hit = passed & ~stop
-                tested = (passed if mutate == "stop_counts" else hit)
-                value = T if mutate == "before" else next_T
-                tol = C_CONTRIB * np.maximum(next_T * rel_next, 1e-300)
-                # computed exactly in float32 too: nothing in front, exp2(-0) = 1, alpha = o, and 1 - o representable
-                exact = (sigma == 0.0) & (relT == 0.0) & (alpha_u <= CLAMP) & \
-                    (next_T.astype(np.float32).astype(np.float64) == next_T)
-                d = np.where(exact & (next_T == t_level), np.inf, np.abs(next_T - t_level) / tol)
-                open_ = tested & (pos == NEVER)
-                dist = np.where(open_, np.minimum(dist, d), dist)
-                crossed = tested & ((value < t_level) if mutate == "lt" else (value <= t_level))
-                if mutate == "last":
-                    pos = np.where(crossed, i, pos)
-                else:
-                    pos = np.where(crossed & (pos == NEVER), i, pos)
-                pos_lo = np.where(tested & (pos_lo == NEVER) & (value - UNDECIDED * tol <= t_level), i, pos_lo)
-                pos_hi = np.where(tested & (pos_hi == NEVER) & (value + UNDECIDED * tol <= t_level), i, pos_hi)
-                T = np.where(hit, next_T, T)
-                relT = np.where(hit, rel_next, relT)
-                live = live & ~stop
-            has = pos != NEVER
-            cid = isect[np.where(has, pos, 0)]
-            out["id"][ys, xs] = np.where(has, g_from_c[cid], -1)
-            out["depth"][ys, xs] = np.where(has, z[cid], np.float32(0.0))
-            out["pos"][ys, xs], out["pos_lo"][ys, xs], out["pos_hi"][ys, xs] = pos, pos_lo, pos_hi
-            out["dist"][ys, xs] = dist
+    for tile in tiles(bins, h, w):
+        ys, xs = tile.ys, tile.xs
+        pos = np.full(xs.shape, NEVER, np.int64)
+        pos_lo, pos_hi = pos.copy(), pos.copy()
+        dist = np.full(xs.shape, np.inf)
+        for e in walk64(proj, isect, tile):  # the walk goes on behind the crossing, for pos_hi
+            i, next_T = e.i, e.next_T
+            tested = (e.passed if mutate == "stop_counts" else e.hit)
+            value = e.T if mutate == "before" else next_T
+            tol = C_CONTRIB * np.maximum(next_T * e.rel_next, 1e-300)
+            # computed exactly in float32 too: nothing in front, exp2(-0) = 1, alpha = o, and 1 - o representable
+            exact = (e.sigma == 0.0) & (e.relT == 0.0) & (e.alpha_u <= CLAMP) & \
+                (next_T.astype(np.float32).astype(np.float64) == next_T)
+            d = np.where(exact & (next_T == t_level), np.inf, np.abs(next_T - t_level) / tol)
+            open_ = tested & (pos == NEVER)
+            dist = np.where(open_, np.minimum(dist, d), dist)
+            crossed = tested & ((value < t_level) if mutate == "lt" else (value <= t_level))
+            if mutate == "last":
+                pos = np.where(crossed, i, pos)
+            else:
+                pos = np.where(crossed & (pos == NEVER), i, pos)
+            pos_lo = np.where(tested & (pos_lo == NEVER) & (value - UNDECIDED * tol <= t_level), i, pos_lo)
+            pos_hi = np.where(tested & (pos_hi == NEVER) & (value + UNDECIDED * tol <= t_level), i, pos_hi)
+        has = pos != NEVER
+        cid = isect[np.where(has, pos, 0)]
+        out["id"][ys, xs] = np.where(has, g_from_c[cid], -1)
+        out["depth"][ys, xs] = np.where(has, z[cid], np.float32(0.0))
+        out["pos"][ys, xs], out["pos_lo"][ys, xs], out["pos_hi"][ys, xs] = pos, pos_lo, pos_hi
+        out["dist"][ys, xs] = dist
     out["undecided"] = out["dist"] <= UNDECIDED
     return out
 
@@ -108,20 +81,15 @@ def walk(case, level, mutate=None):
 def positions_of(case, ids):
     """The list position of every pixel's global id in its tile's list (NEVER for -1, -2 for an id the list lacks)."""
     w, h = int(case["w"]), int(case["h"])
-    bins = np.asarray(case["tile_bins"]).astype(np.int64)
-    isect = np.asarray(case["isect"]).astype(np.int64)
-    g_from_c = np.asarray(case["g_from_c"]).astype(np.int64)
+    _, bins, isect, g_from_c = arrays(case)
     ids = np.asarray(ids).astype(np.int64).reshape(h, w)
     pos = np.full((h, w), -2, np.int64)
-    for ty in range(bins.shape[0]):
-        for tx in range(bins.shape[1]):
-            r0, r1 = int(bins[ty, tx, 0]), int(bins[ty, tx, 1])
-            first = {}
-            for i in range(r1 - 1, r0 - 1, -1):
-                first[int(g_from_c[isect[i]])] = i
-            first[-1] = NEVER
-            sl = (slice(ty * 16, min(ty * 16 + 16, h)), slice(tx * 16, min(tx * 16 + 16, w)))
-            pos[sl] = np.vectorize(lambda g: first.get(int(g), -2), otypes=[np.int64])(ids[sl])
+    for tile in tiles(bins, h, w):
+        first = {}
+        for i in range(tile.r1 - 1, tile.r0 - 1, -1):
+            first[int(g_from_c[isect[i]])] = i
+        first[-1] = NEVER
+        pos[tile.ys, tile.xs] = np.vectorize(lambda g: first.get(int(g), -2), otypes=[np.int64])(ids[tile.ys, tile.xs])
     return pos
 
 
@@ -147,51 +115,26 @@ def gate(case, got_id, got_depth, ref):
 
 
 def emulate32(case, level):
-    """The kernel's arithmetic restated in numpy float32 (contrib_ref64.emulate32's expressions: fused multiply-adds in
+    """The kernel's arithmetic restated in numpy float32 (replay_ref.walk32: fused multiply-adds in
     float64 with one rounding, exp2 through float64): a stand-in for the device in tests that run anywhere.  Returns
     (ids [h,w] int32, depth [h,w] float32)."""
     f32 = np.float32
     w, h = int(case["w"]), int(case["h"])
     t_level = f32(1.0) - f32(level)
-    proj = np.asarray(case["projected"], f32)
-    bins = np.asarray(case["tile_bins"]).astype(np.int64)
-    isect = np.asarray(case["isect"]).astype(np.int64)
-    g_from_c = np.asarray(case["g_from_c"]).astype(np.int64)
+    proj, bins, isect, g_from_c = arrays(case, f32)
     z = np.asarray(case["z"], f32)
     ids = np.full((h, w), -1, np.int32)
     depth = np.zeros((h, w), f32)
-
-    def fma(a, b, c):
-        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(f32)
-
-    neg_log2e = f32(-1.44269504088896341)
-    for ty in range(bins.shape[0]):
-        for tx in range(bins.shape[1]):
-            y0, x0 = ty * 16, tx * 16
-            ys, xs = np.meshgrid(np.arange(y0, min(y0 + 16, h)), np.arange(x0, min(x0 + 16, w)), indexing="ij")
-            pcx, pcy = (xs + 0.5).astype(f32), (ys + 0.5).astype(f32)
-            T = np.ones(xs.shape, f32)
-            live = np.ones(xs.shape, bool)  # neither crossed nor stopped
-            tid = np.full(xs.shape, -1, np.int32)
-            tz = np.zeros(xs.shape, f32)
-            for i in range(int(bins[ty, tx, 0]), int(bins[ty, tx, 1])):
-                if not live.any():
-                    break
-                c = int(isect[i])
-                p = proj[c]
-                dx, dy = p[0] - pcx, p[1] - pcy
-                sigma = fma(np.full_like(dx, 0.5), fma(p[2] * dx, dx, (p[4] * dy) * dy), (p[3] * dy) * dx)
-                power = sigma * neg_log2e
-                alpha_u = p[8] * np.exp2(power.astype(np.float64)).astype(f32)
-                passed = live & (power <= 0) & (alpha_u >= f32(1.0) / f32(255.0))
-                alpha = np.minimum(f32(0.999), alpha_u)
-                next_T = T * (f32(1.0) - alpha)
-                stop = passed & (next_T <= f32(1e-4))
-                hit = passed & ~stop
-                cross = hit & (next_T <= t_level)
-                T = np.where(hit, next_T, T)
-                tid = np.where(cross, np.int32(g_from_c[c]), tid)
-                tz = np.where(cross, z[c], tz)
-                live = live & ~stop & ~cross
-            ids[ys, xs], depth[ys, xs] = tid, tz
+    for tile in tiles(bins, h, w):
+        open_ = np.ones(tile.xs.shape, bool)  # not crossed: the kernel retires a pixel at its crossing
+        tid = np.full(tile.xs.shape, -1, np.int32)
+        tz = np.zeros(tile.xs.shape, f32)
+        for e in walk32(proj, isect, tile):
+            if not (e.live & open_).any():
+                break
+            cross = e.hit & open_ & (e.next_T <= t_level)
+            tid = np.where(cross, np.int32(g_from_c[e.c]), tid)
+            tz = np.where(cross, z[e.c], tz)
+            open_ = open_ & ~cross
+        ids[tile.ys, tile.xs], depth[tile.ys, tile.xs] = tid, tz
     return ids, depth
